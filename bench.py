@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the STEP hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,11 +11,21 @@ already resident in HBM.  A "step" is one forward over one batch.  With N GPUs e
 own batch (clips shard by clip, no data-path collective, weak scaling); value = clips of all ranks /
 max-over-ranks time.
 
-One JSON line is printed by rank 0: the contract fields plus
+A plain run sets up, runs W warm-up steps, times K steps and prints one JSON line from rank 0 with the
+contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step).
+
+--full additionally measures, and adds to the line:
+  "sustained"    the same loop for --sustained-seconds (default 2) before the timed steps, with clocks;
+  "one_batch_in_flight", "fp16", "fed"   the same steps one batch at a time, in fp16 storage, and fed
+                 from pinned host uint8 frames (c2 on one GPU);
   "roofline"     for the dominant kernel of the step (largest share of GPU time), from HIP events
                  recorded around every launch on the launch stream during an instrumented pass;
   "cpu_baseline" the torch-CPU fp32 restatement of the same backbone (oracle/i3d_ref.py) timed on
                  this box's host cores on a bounded sample (rank 0, N=1 only).
+
+--dump-outputs DIR writes what the last timed step computed (what a caller of the step receives) as
+DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed, seeded sample of a larger output).
+Inputs and weights are seeded, so two runs with the same arguments see the same inputs.
 """
 import argparse
 import json
@@ -42,6 +52,33 @@ PROFILE_ROUND = "r06"                                           # the profiles/ 
 # algorithmic work of BaseNet at C2 per clip: 109.29 GFLOP, 304.9 MB activations + 15.0 MB weights/batch
 GFLOP_PER_CLIP = 109.29
 ACT_MB_PER_CLIP, W_MB = 304.9, 15.0
+DUMP_BYTES = 60 * 10 ** 6                                       # --dump-outputs data in all (+ the .npy headers: under 64 MB)
+
+
+def snapshot(arrays):
+    """name -> tensor / ndarray / number, copied to host memory now (later loops of --full overwrite the step's buffers):
+    64-bit floats and integers as float64, everything else as float32."""
+    out = {}
+    for name, v in arrays.items():
+        t = torch.as_tensor(v).detach()
+        wide = t.dtype == torch.float64 or not (t.dtype.is_floating_point or t.dtype == torch.bool)
+        out[name] = t.to("cpu", torch.float64 if wide else torch.float32).clone()
+    return out
+
+
+def dump_outputs(d, arrays):
+    """Write snapshot() arrays as d/<name>.npy, DUMP_BYTES in all: an array larger than its share is replaced by a fixed,
+    seeded sample of its elements (torch.randperm(numel, seed 0), the first m in ascending order) -- the same elements every run."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    left, items = DUMP_BYTES, sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        m = left // (len(items) - i) // t.element_size()
+        if t.numel() > m:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:m].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), t.numpy())
+        left -= t.numel() * t.element_size()
 
 
 def cfg():
@@ -765,8 +802,9 @@ def main():
                     help="c2 / c5: independent batches kept in flight on separate HIP streams (each step is still one batch; default 2)")
     ap.add_argument("--clips", type=int, default=None, help="clips per GPU (default: the config's: c2 8, c5 4, c3 4, c4 1)")
     ap.add_argument("--tubes", type=int, default=None, help="c3 / c4: tubes per clip (default: c3 11, c4 5)")
-    ap.add_argument("--sustained-seconds", type=float, default=2.0,
-                    help="c2 / c5: length of the second, sustained loop of the same captured step reported under 'sustained' (0 = skip)")
+    ap.add_argument("--sustained-seconds", type=float, default=None,
+                    help="c2 / c5: length of the second, sustained loop of the same captured step reported under 'sustained' "
+                         "(default 2 with --full, else 0 = skip)")
     ap.add_argument("--force-exchange", action="store_true",
                     help="c4 on ONE GPU: initialise a one-rank RCCL process group and issue the bucketed gradient all-reduces all the same "
                          "(identities there) -- the multi-rank program, captured in the step's HIP graph, on a one-GPU box")
@@ -781,15 +819,22 @@ def main():
                     help="tuning aid: a planner option of the library (include/step_amd.h step_set_option), e.g. conv_group_pw=0; repeatable")
     ap.add_argument("--no-fp16-leg", action="store_true", help="c2: skip the fp16 leg (the same loop with fp16 storage, reported under 'fp16')")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: sustained loop, one-batch / fp16 / fed loops, roofline and kernel table, CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     a = ap.parse_args()
+    if a.sustained_seconds is None:
+        a.sustained_seconds = 2.0 if a.full else 0.0
     global CLIPS_PER_GPU, T_IN, HW_IN, GFLOP_PER_CLIP, ACT_MB_PER_CLIP
     c = CONFIGS[a.config]
     CLIPS_PER_GPU, T_IN, HW_IN, GFLOP_PER_CLIP, ACT_MB_PER_CLIP = a.clips or c["clips"], c["T"], c["HW"], c["gflop"], c["act_mb"]
     a.dtype = a.dtype or c["dtype"]
     if a.feed is None:
         # the headline config also times the FED loop by default on ONE GPU (the driver's command has no --feed); with several
-        # ranks it stays opt-in (`--feed u8`): the scaling run's line must not depend on a loop that has never run on more than one device
-        a.feed = "u8" if (a.config == "c2" and a.gpus == 1) else "none"
+        # ranks it stays opt-in (`--feed u8`): the scaling run's line must not depend on a loop that has never run on more than one device;
+        # a plain run (no --full) times the headline loop only
+        a.feed = "u8" if (a.full and a.config == "c2" and a.gpus == 1) else "none"
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -897,12 +942,13 @@ def main():
                             yi = net(xi)
                     flights.append((si, gi, xi, yi))
             torch.cuda.synchronize()
-            if many:
+            if many and a.full:
                 graph.replay(); flights[0][1].replay()
                 torch.cuda.synchronize()
                 assert torch.equal(y, flights[0][3]), "the throughput profile changed the result"
 
         _timed_hook = [None]
+        eager_out = [None]
 
         def timed(nfl):
             """W warm-up steps, then K steps between barrier + synchronize on both sides; nfl batches in flight (round-robin)."""
@@ -910,7 +956,7 @@ def main():
                 if _timed_hook[0] is not None:
                     _timed_hook[0](k)
                 if graph is None:
-                    net(x)
+                    eager_out[0] = net(x)
                 elif nfl == 1:
                     graph.replay()
                 else:
@@ -961,11 +1007,15 @@ def main():
             timed(nfl)
             a.steps, a.warmup = keep_steps, keep_warm
         el = timed(nfl)
+        if a.dump_outputs and rank == 0:
+            # the conv feature map of the batch the last timed step processed
+            last = eager_out[0] if graph is None else (y if nfl == 1 else flights[(a.steps - 1) % nfl][3])
+            dump_outputs(a.dump_outputs, snapshot({"conv_feat": last}))
         # the one-batch-at-a-time window: first ~0.5 s of that loop (the DPM state after two batches in flight is not the state a
         # one-batch loop settles in; the driver's round-5 box read 1.45 ms here against 1.23 ms on every other box),
         # with the EFFECTIVE clock sampled beside it, then the same K steps
         one_clock = None
-        if nfl > 1:
+        if nfl > 1 and a.full:
             keep_steps, keep_warm = a.steps, a.warmup
             a.steps, a.warmup = max(keep_steps, int(0.5 / max(el / keep_steps, 1e-5)) + 1), 0
             ec = EffClock(dev, stream=flights[1][0])                # (the second batch's stream: idle in this loop)
@@ -975,10 +1025,10 @@ def main():
             _timed_hook[0] = None
             one_clock = ec.result()
             a.steps, a.warmup = keep_steps, keep_warm
-        el_one = timed(1) if nfl > 1 else el                   # the same K steps one batch at a time (reported beside the headline)
+        el_one = timed(1) if (nfl > 1 and a.full) else el      # the same K steps one batch at a time (reported beside the headline)
         # (the fp16 leg first: it runs on the bf16 loop's own streams; behind the fed loop -- which creates three streams of its own -- its two
         # batches overlapped half as well, 6.75 k against 7.26 k clips/s)
-        fp16 = fp16_leg(a, net, x, dev, nfl, thr_profile, streams=[fl[0] for fl in flights]) if (a.config == "c2" and a.dtype == "bf16" and graph is not None and world == 1 and not a.no_fp16_leg) else None
+        fp16 = fp16_leg(a, net, x, dev, nfl, thr_profile, streams=[fl[0] for fl in flights]) if (a.full and a.config == "c2" and a.dtype == "bf16" and graph is not None and world == 1 and not a.no_fp16_leg) else None
         fed = fed_loop(a, net, flights, x, dev, tdt, dist, el / a.steps) if (a.feed == "u8" and graph is not None) else None
     if dist is not None:
         t = torch.tensor([el, el_one, sus[1] if sus else 0.0], device=dev if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
@@ -1001,13 +1051,14 @@ def main():
                                                                     "hipGraph replay, %d batches in flight (one captured step per batch, %d HIP streams, round-robin%s)" % (
                                                                         nfl, nfl, "; steps captured under the library's `throughput` planner profile, bit-identical to the default" if thr_profile else "")),
                           "batches_in_flight": nfl},
-               "one_batch_in_flight": {"value": round(clips / el_one, 2), "ms_per_step": round(el_one / a.steps * 1e3, 4), "clock_effective": one_clock,
-                                       "note": "the same K steps replayed one after the other on one stream (the loop of rounds 1-2), after ~0.5 s of that same loop; "
-                                               "clock_effective = step_clock_sample beside that 0.5 s loop (s_memtime / s_memrealtime, GHz)"},
-               "planner_profile": {"value": "throughput" if thr_profile else "default", "one_batch_in_flight": "default", "roofline": "default",
-                                   "note": "planner option `throughput` (include/step_amd.h) under which the steps of each loop were captured; results bit-identical (asserted in this run)"},
                "ranks": {"world_size": world, "backend": (dist.get_backend() + " (RCCL over xGMI)" if dist.get_backend() == "nccl" else dist.get_backend()) if dist is not None else None,
                          "devices_visible": ndev}}
+        if a.full:
+            out["one_batch_in_flight"] = {"value": round(clips / el_one, 2), "ms_per_step": round(el_one / a.steps * 1e3, 4), "clock_effective": one_clock,
+                                          "note": "the same K steps replayed one after the other on one stream (the loop of rounds 1-2), after ~0.5 s of that same loop; "
+                                                  "clock_effective = step_clock_sample beside that 0.5 s loop (s_memtime / s_memrealtime, GHz)"}
+            out["planner_profile"] = {"value": "throughput" if thr_profile else "default", "one_batch_in_flight": "default", "roofline": "default",
+                                      "note": "planner option `throughput` (include/step_amd.h) under which the steps of each loop were captured; results bit-identical (asserted in this run)"}
         if sus:
             out["sustained"] = {"seconds": round(sus[1], 3), "steps": sus[0], "value": round(world * CLIPS_PER_GPU * sus[0] / sus[1], 2),
                                 "ms_per_step": round(sus[1] / sus[0] * 1e3, 4), "clock_ghz": sus[4] if sus[4] else sus[2], "clock_samples": sus[5] if sus[4] else sus[3],
@@ -1028,7 +1079,7 @@ def main():
             "note": "whole-backbone algorithmic bytes (BASELINE.md sec. 2: %.1f MB/clip + 15 MB weights/batch) and FLOPs (%.2f GFLOP/clip) " % (ACT_MB_PER_CLIP, GFLOP_PER_CLIP) +
                     "per second per GPU over the 8 TB/s HBM and dense MFMA peaks"}
     # roofline of the dominant kernel (every rank could, rank 0 reports)
-    if rank == 0:
+    if rank == 0 and a.full:
         with torch.no_grad():
             rl, table, gpu_ms, seq = roofline(net, x, a.dtype)
         out["roofline"] = rl
@@ -1053,6 +1104,7 @@ def main():
                 print("%9.4f ms %3d x  %8.1f TFLOP/s  %s" % (ms, cnt, gfs, n_), file=sys.stderr)
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(net)
+    if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()
@@ -1108,10 +1160,11 @@ def pipeline_bench(a, c, dev, tdt, rank, world, dist):
         streams.append(si)
 
     def run(k_steps, n):
+        """Returns what the last step returned (c3: the post-processed detections; c4: the loss)."""
         if n == 1:
             for _ in range(k_steps):
-                w.step()
-            return
+                r = w.step()
+            return r
         pending = None
         for k in range(k_steps):
             i = k % n
@@ -1122,7 +1175,9 @@ def pipeline_bench(a, c, dev, tdt, rank, world, dist):
                     ws[pending[0]].finish(pending[1])
             pending = (i, h)
         with torch.cuda.stream(streams[pending[0]]):
-            ws[pending[0]].finish(pending[1])
+            return ws[pending[0]].finish(pending[1])
+
+    last = [None]
 
     def timed(n):
         run(max(a.warmup, 2), n)
@@ -1131,7 +1186,7 @@ def pipeline_bench(a, c, dev, tdt, rank, world, dist):
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(a.steps, n)
+        last[0] = run(a.steps, n)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -1139,19 +1194,33 @@ def pipeline_bench(a, c, dev, tdt, rank, world, dist):
         return time.perf_counter() - t0
 
     el = timed(nfl)
-    el_one = timed(1) if nfl > 1 else el
+    if a.dump_outputs and rank == 0:
+        if a.config == "c3":
+            # per refinement iteration, the detections of all clips of the batch concatenated, with the clip index of each row
+            arrays = {}
+            for it, clips in enumerate(last[0]):
+                for key in ("boxes", "scores", "labels", "tubes"):
+                    arrays["iter%d_%s" % (it, key)] = torch.cat([cl[key].detach().cpu() for cl in clips])
+                arrays["iter%d_clip" % it] = torch.cat([torch.full((len(cl["scores"]),), j, dtype=torch.int64) for j, cl in enumerate(clips)])
+        else:
+            # the loss of the last step and the weights it left (FlatAdam's flat fp32 parameter arena)
+            arrays = {"loss": last[0], "params": w.opt.flat_param}
+        dump_outputs(a.dump_outputs, snapshot(arrays))
+    el_one = timed(1) if (nfl > 1 and a.full) else el
     if dist is not None:
         t = torch.tensor([el, el_one], device=dev if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el, el_one = float(t[0].item()), float(t[1].item())
-    # dominant kernel of one eager, single-stream, instrumented step -- run by EVERY rank (the C4 step contains the
-    # gradient all-reduce: a collective issued by rank 0 alone would dead-lock against the others' final barrier)
-    ops.PROFILE = []
-    saved, backbone.BRANCH_STREAMS = backbone.BRANCH_STREAMS, False
-    (w.eager if a.config == "c3" else getattr(w, "_eager_step", w.step))()
-    torch.cuda.synchronize()
-    backbone.BRANCH_STREAMS = saved
-    REC, ops.PROFILE = ops.PROFILE, None
+    REC = []
+    if a.full:
+        # dominant kernel of one eager, single-stream, instrumented step -- run by EVERY rank (the C4 step contains the
+        # gradient all-reduce: a collective issued by rank 0 alone would dead-lock against the others' final barrier)
+        ops.PROFILE = []
+        saved, backbone.BRANCH_STREAMS = backbone.BRANCH_STREAMS, False
+        (w.eager if a.config == "c3" else getattr(w, "_eager_step", w.step))()
+        torch.cuda.synchronize()
+        backbone.BRANCH_STREAMS = saved
+        REC, ops.PROFILE = ops.PROFILE, None
     if rank == 0:
         val = world * CLIPS_PER_GPU * a.steps / el
         out = {"metric": metric, "value": round(val, 2), "unit": "clips/s", "n_gpus": world, "steps": a.steps, "warmup": max(a.warmup, 2),
@@ -1175,7 +1244,7 @@ def pipeline_bench(a, c, dev, tdt, rank, world, dist):
                                                if getattr(getattr(w, "reducer", None), "active", False) else None},
                "ranks": {"world_size": world, "backend": (dist.get_backend() + " (RCCL over xGMI)" if dist.get_backend() == "nccl" else dist.get_backend()) if dist is not None else None,
                          "devices_visible": torch.cuda.device_count()}}
-        if nfl > 1:
+        if nfl > 1 and a.full:
             out["one_batch_in_flight"] = {"value": round(world * CLIPS_PER_GPU * a.steps / el_one, 2), "ms_per_step": round(el_one / a.steps * 1e3, 4),
                                           "note": "the same K steps one after the other on one stream (the loop of rounds 1-2)"}
         rec = REC
@@ -1211,7 +1280,7 @@ def pipeline_bench(a, c, dev, tdt, rank, world, dist):
                                "launches_per_step": cnt, "avg_launch_ms": round(ms / cnt, 4),
                                "share_of_instrumented_kernel_time": round(ms / sum(v[1] for v in agg.values()), 3),
                                "note": "instrumented launches of step_amd.ops: conv / stem / pool forward, the data-gradient convs and conv weight gradients (torch glue kernels are not in this table)"}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_pipeline_baseline(a.config, w, tubes)
         print(json.dumps(out))
     if dist is not None:

@@ -10,7 +10,6 @@ C restatement (oracle/step_oracle.c: bit-identical to the reference's own CPU op
 """
 import importlib.util
 import os
-import subprocess
 import sys
 import types
 
@@ -24,9 +23,10 @@ REF = os.environ.get("STEP_REFERENCE", "/root/reference")
 def main():
     if not os.path.isdir(REF):
         raise SystemExit("the reference tree is not available (%s): build-container check only" % REF)
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "emul"), "-j8"])
-    os.environ["STEP_AMD_LIB"] = os.path.join(ROOT, "tests", "emul", "_build", "libstep_amd_emul.so")
     sys.path.insert(0, ROOT)
+    from tests.emul.emul_lib import build as build_emul                 # the host build, under the lock the test workers share
+    build_emul()
+    os.environ["STEP_AMD_LIB"] = os.path.join(ROOT, "tests", "emul", "_build", "libstep_amd_emul.so")
     sys.path.insert(0, REF)
     import torch
     spec = importlib.util.spec_from_file_location("external.maskrcnn_benchmark.roi_layers._C", os.path.join(ROOT, "integration", "_C.py"))

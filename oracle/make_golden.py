@@ -816,8 +816,20 @@ def full_size_main():
     np.savez_compressed(os.path.join(OUT, "full_size_golden.npz"), **g)
 
 
+def ref_ops_main():
+    """tests/test_oracle_vs_reference.py: what the reference's own compiled operators (oracle/_ref/_C.so) return on its seeded cases."""
+    import oracle
+    sys.path.insert(0, os.path.dirname(HERE))
+    from tests.test_oracle_vs_reference import all_cases
+    refC = oracle.load_reference_C()
+    g = {key: call(refC) for key, call in all_cases().items()}
+    np.savez_compressed(os.path.join(OUT, "ref_ops_golden.npz"), **g)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "full_size":
+    if len(sys.argv) > 1 and sys.argv[1] == "ref_ops":
+        ref_ops_main()
+    elif len(sys.argv) > 1 and sys.argv[1] == "full_size":
         full_size_main()
     elif len(sys.argv) > 1 and sys.argv[1] == "bn_train":
         bn_train_main()

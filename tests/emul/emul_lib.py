@@ -2,6 +2,7 @@
 interpreter, tests/emul/hipemu.*).  TEST INFRASTRUCTURE ONLY: lets the kernel index logic be
 checked against the oracle on the CPU-only build container.  Never used by step_amd."""
 import ctypes
+import fcntl
 import os
 import subprocess
 
@@ -16,10 +17,18 @@ _lib = None
 NP_DT = {_capi.F32: np.float32, _capi.BF16: np.uint16, _capi.F16: np.float16}
 
 
+def build():
+    """make the host build, one process at a time: parallel test workers (pytest -n) share tests/emul/_build."""
+    os.makedirs(os.path.join(_HERE, "_build"), exist_ok=True)
+    with open(os.path.join(_HERE, "_build", ".lock"), "w") as lk:
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        subprocess.check_call(["make", "-s", "-C", _HERE, "-j8"])
+
+
 def lib():
     global _lib
     if _lib is None:
-        subprocess.check_call(["make", "-s", "-C", _HERE, "-j8"])
+        build()
         _lib = _capi.declare(ctypes.CDLL(_PATH))
     return _lib
 

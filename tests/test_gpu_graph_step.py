@@ -208,7 +208,7 @@ def test_bench_fed_loop_reports_both_forms():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--feed", "u8", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--sustained-seconds", "0.3"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--feed", "u8", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--sustained-seconds", "0.3"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=560, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
