@@ -7,7 +7,7 @@
  *     (/root/reference/external/maskrcnn_benchmark/csrc/vision.cpp:30-36)
  * and the cuDNN calls behind torch.nn.Conv3d/BatchNorm3d/MaxPool3d/AvgPool3d/Conv2d/Linear that
  * models/i3dpt.py and models/two_branch.py lean on -- forward, and for the training step (train.py:257-348) their
- * backward (data / weight gradients, pool and activation gradients) and the Adam update.  INTEGRATION.md shows the
+ * backward (data / weight gradients, pool and activation gradients) and the Adam / SGD updates.  INTEGRATION.md shows the
  * binding a maintainer of the reference adds.
  *
  * Conventions
@@ -580,6 +580,34 @@ STEP_API int step_adam_flat_amp(float* param, float* grad, float* exp_avg, float
                                 double beta2, double eps, long long* step_dev, float* bias_corr, float grad_scale, int zero_grad,
                                 float* amp_state, float growth_factor, float backoff_factor, int growth_interval,
                                 step_stream_t stream);
+
+/* Fused multi-tensor SGD with momentum over flat fp32 arenas: replaces optimizer.step() of the reference's DEFAULT optimizer,
+ * optim.SGD(params, lr=args.det_lr, momentum=args.momentum, weight_decay=args.weight_decay) (train.py:123-124,348; config.py:51-57),
+ * over the same single-tensor groups.  param / grad / momentum_buf: n fp32 elements each (n % 4 == 0, 16-byte aligned); segments and
+ * the three DEVICE tables as for step_adam_flat (n_seg <= 4096).
+ * Arithmetic = torch/optim/sgd.py::_single_tensor_sgd (maximize off), per element and in this order: g = grad*grad_scale (+ wd*p);
+ * buf = g on the FIRST step (torch clones the gradient: no dampening), buf = momentum*buf + (1-dampening)*g afterwards; g = g +
+ * momentum*buf with nesterov, else g = buf; p -= lr*g.  momentum / dampening are doubles as in torch (1 - dampening is taken in
+ * double).  step counts from 1; step == 1 is the first step.  momentum == 0: no buffer is read or written and momentum_buf may be
+ * NULL.  nesterov with momentum <= 0 or dampening != 0 is refused, as torch raises.  grad_scale / zero_grad as for step_adam_flat.
+ * 12 B read + 8 B written per element (+4 B with the gradient clear). */
+STEP_API int step_sgd_flat(float* param, float* grad, float* momentum_buf, long long n, const long long* seg_end,
+                           const float* seg_lr, const float* seg_wd, int n_seg, double momentum, double dampening, int nesterov,
+                           int step, float grad_scale, int zero_grad, step_stream_t stream);
+/* The same update with the step counter ON THE DEVICE, for a captured training step: "first step" is *step_dev == 0 (int64, device) as
+ * the main pass finds it; a one-thread kernel BEHIND the pass increments the counter, so a replayed graph initialises the buffer once
+ * and runs the recurrence ever after.  Same arithmetic as step_sgd_flat, bit for bit. */
+STEP_API int step_sgd_flat_dev(float* param, float* grad, float* momentum_buf, long long n, const long long* seg_end,
+                               const float* seg_lr, const float* seg_wd, int n_seg, double momentum, double dampening, int nesterov,
+                               long long* step_dev, float grad_scale, int zero_grad, step_stream_t stream);
+/* step_sgd_flat_dev under dynamic loss scaling: the three stages and the amp_state layout of step_adam_flat_amp (one LossScaler
+ * serves both optimizers).  A step skipped for overflow leaves parameters, buffer AND counter as they are, so an overflow on the very
+ * first step leaves the first CLEAN step to initialise the buffer with buf = g (torch.amp.GradScaler + SGD: a skipped step() leaves
+ * `momentum_buffer` absent). */
+STEP_API int step_sgd_flat_amp(float* param, float* grad, float* momentum_buf, long long n, const long long* seg_end,
+                               const float* seg_lr, const float* seg_wd, int n_seg, double momentum, double dampening, int nesterov,
+                               long long* step_dev, float grad_scale, int zero_grad, float* amp_state, float growth_factor,
+                               float backoff_factor, int growth_interval, step_stream_t stream);
 
 /* The tail of TwoBranchNet.forward (models/two_branch.py:246-342) behind its last two GEMMs, as ONE launch (and one for its backward):
  * the class logits averaged over a tube's frames and their sigmoid, the box regressions (local_loc = columns 0..3 of the fused

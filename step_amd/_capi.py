@@ -5,7 +5,7 @@ import ctypes as C
 F32, BF16, F16 = 0, 1, 2
 NCHW, NHWC = 0, 1
 ROI_BWD_GATHER, ROI_BWD_ATOMIC = 0, 1
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 vp, fp, ip, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # raw device addresses
 i, f, ll, sz = C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -119,6 +119,9 @@ SIGNATURES = {
     "step_adam_flat": (i, [fp, fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, C.c_double, i, f, i, vp]),
     "step_adam_flat_dev": (i, [fp, fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, C.c_double, vp, fp, f, i, vp]),
     "step_adam_flat_amp": (i, [fp, fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, C.c_double, vp, fp, f, i, fp, f, f, i, vp]),
+    "step_sgd_flat": (i, [fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, i, i, f, i, vp]),
+    "step_sgd_flat_dev": (i, [fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, i, vp, f, i, vp]),
+    "step_sgd_flat_amp": (i, [fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, i, vp, f, i, fp, f, f, i, vp]),
 }
 
 

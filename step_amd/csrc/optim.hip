@@ -1,4 +1,4 @@
-// step_amd/csrc/optim.hip -- fused multi-tensor Adam over a flat fp32 parameter arena.
+// step_amd/csrc/optim.hip -- fused multi-tensor Adam and SGD-with-momentum over flat fp32 parameter arenas.
 //
 // Replaces optimizer.step() of torch.optim.Adam(params, lr=args.det_lr) (reference train.py:126,348) over the 159+
 // single-tensor parameter groups utils/solver.py:12-93 builds (per-group lr and weight_decay): the reference runs
@@ -103,6 +103,71 @@ __global__ void loss_scale_update_kernel(float* amp, float growth, float backoff
             else amp[1] = t;
         }
         amp[2] = 0.f;
+    }
+}
+
+// ---- SGD with momentum (the reference's DEFAULT optimizer: config.py:51 `--optimizer sgd`, train.py:123-124) ----------------------
+// optim.SGD(params, lr=args.det_lr, momentum=args.momentum, weight_decay=args.weight_decay) over the same single-tensor groups, on
+// THREE arenas (parameters, gradients, one momentum buffer): 12 B read + 8 B written per element (+4 B for the fused gradient clear),
+// against Adam's 16 + 12.  Arithmetic follows torch/optim/sgd.py::_single_tensor_sgd (maximize=False), in its order:
+//   g   = grad * grad_scale (+ weight_decay * p)
+//   buf = g                                     on the FIRST step (torch clones the gradient: no dampening)
+//   buf = momentum * buf + (1 - dampening) * g  afterwards
+//   g   = g + momentum * buf  (nesterov)   |   g = buf
+//   p  -= lr * g
+// "first step" is a host scalar (step_sgd_flat: step == 1) or the OLD value of the device counter (step_sgd_flat_dev / _amp: *step_dev
+// == 0), read once per thread ahead of the loop; sgd_count_kernel advances the counter BEHIND this pass on the same stream, so no
+// thread of this launch reads a value another thread of it writes.  MOM = false (momentum == 0): no buffer is read or written.
+template <int MAXSEG, bool MOM>
+__global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf, long long nvec,
+                                                       const long long* __restrict__ seg_end, const float* __restrict__ seg_lr,
+                                                       const float* __restrict__ seg_wd, int n_seg, float mu, float omd, int nesterov,
+                                                       int first, float gscale, int zero_grad, const long long* __restrict__ step_dev,
+                                                       const float* __restrict__ amp) {
+    __shared__ long long s_end[MAXSEG];
+    if (step_dev) first = *step_dev == 0;                  // no clean step yet (a skipped step does not count): this one initialises the buffer
+    bool skip = false;                                     // dynamic loss scaling: as adam_flat_kernel
+    if (amp) { skip = amp[2] != 0.f; gscale = gscale * (1.f / amp[0]); }
+    for (int i = threadIdx.x; i < n_seg; i += blockDim.x) s_end[i] = seg_end[i];
+    __syncthreads();
+    for (long long vec = (long long)blockIdx.x * blockDim.x + threadIdx.x; vec < nvec; vec += (long long)blockDim.x * gridDim.x) {
+        const long long e = vec * 4;
+        if (skip) {
+            if (zero_grad) *(f32x4*)(g + e) = f32x4{0.f, 0.f, 0.f, 0.f};
+            continue;
+        }
+        int lo = 0, hi = n_seg - 1;                       // first segment whose end lies beyond e
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_end[mid] > e) hi = mid; else lo = mid + 1;
+        }
+        const float lr = seg_lr[lo], wd = seg_wd[lo];
+        f32x4 P = *(const f32x4*)(p + e), G = *(const f32x4*)(g + e), B = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (MOM && !first) B = *(const f32x4*)(buf + e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gj = G[j] * gscale;
+            if (wd != 0.f) gj = gj + wd * P[j];
+            if (MOM) {
+                const float bj = first ? gj : mu * B[j] + omd * gj;
+                B[j] = bj;
+                gj = nesterov ? gj + mu * bj : bj;
+            }
+            P[j] = P[j] - lr * gj;
+        }
+        *(f32x4*)(p + e) = P;
+        if (MOM) *(f32x4*)(buf + e) = B;
+        if (zero_grad) *(f32x4*)(g + e) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+// the tail of a device-counted SGD step: one thread advances the counter once the main pass has read it (stream order).  A step
+// skipped for overflow does not count, so the first CLEAN step is still the one that finds the counter at 0 and sets buf = g
+// (torch.amp.GradScaler + SGD: a skipped step() leaves `momentum_buffer` absent).
+__global__ void sgd_count_kernel(long long* step, const float* amp) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (amp && amp[2] != 0.f) return;
+        *step = *step + 1;
     }
 }
 
@@ -236,6 +301,14 @@ using namespace step;
 
 extern "C" {
 
+// overflow scan of the gradient arena ahead of a loss-scaled step (step_adam_flat_amp, step_sgd_flat_amp)
+static void grad_scan_launch(const float* grad, long long n, float* amp_state, step_stream_t stream) {
+    const long long nvec = n >> 2;
+    long long blocks = (nvec + 255) / 256;
+    if (blocks > 256LL * 32) blocks = 256LL * 32;
+    STEP_LAUNCH(grad_scan_kernel, dim3((unsigned)blocks), dim3(256), stream, grad, nvec, amp_state);
+}
+
 static int adam_flat_launch(float* param, float* grad, float* exp_avg, float* exp_avg_sq, long long n, const long long* seg_end,
                             const float* seg_lr, const float* seg_wd, int n_seg, double beta1, double beta2, double eps, int step_no,
                             long long* step_dev, float* bc_dev, float grad_scale, int zero_grad, step_stream_t stream,
@@ -290,13 +363,83 @@ int step_adam_flat_amp(float* param, float* grad, float* exp_avg, float* exp_avg
     if (n > 0) {
         if (!grad) return STEP_E_NULL;
         if ((uintptr_t)grad & 15) return STEP_E_ALIGN;
-        const long long nvec = n >> 2;
-        long long blocks = (nvec + 255) / 256;
-        if (blocks > 256LL * 32) blocks = 256LL * 32;
-        STEP_LAUNCH(grad_scan_kernel, dim3((unsigned)blocks), dim3(256), stream, grad, nvec, amp_state);
+        grad_scan_launch(grad, n, amp_state, stream);
     }
     const int rc = adam_flat_launch(param, grad, exp_avg, exp_avg_sq, n, seg_end, seg_lr, seg_wd, n_seg, beta1, beta2, eps, 0, step_dev, bias_corr,
                                     grad_scale, zero_grad, stream, amp_state);
+    if (rc) return rc;
+    STEP_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), stream, amp_state, growth_factor, backoff_factor, growth_interval);
+    return STEP_LAUNCH_CHECK();
+}
+
+// every argument is checked before the first launch: a refused call has written nothing
+static int sgd_flat_check(float* param, float* grad, float* buf, long long n, const long long* seg_end, const float* seg_lr,
+                          const float* seg_wd, int n_seg, double momentum, double dampening, int nesterov, int step_no,
+                          const long long* step_dev) {
+    if (n < 0 || (n & 3) || n_seg <= 0 || n_seg > ADAM_MAX_SEG || (!step_dev && step_no < 1)) return STEP_E_SHAPE;
+    if (!(momentum >= 0.) || !std::isfinite(momentum) || !std::isfinite(dampening)) return STEP_E_SHAPE;
+    if (nesterov && (momentum <= 0. || dampening != 0.)) return STEP_E_SHAPE;     // torch: "Nesterov momentum requires a momentum and zero dampening"
+    if (n == 0) return STEP_OK;
+    if (!param || !grad || (momentum != 0. && !buf) || !seg_end || !seg_lr || !seg_wd) return STEP_E_NULL;
+    if ((((uintptr_t)param) | ((uintptr_t)grad) | (momentum != 0. ? (uintptr_t)buf : 0)) & 15) return STEP_E_ALIGN;
+    return STEP_OK;
+}
+
+static int sgd_flat_launch(float* param, float* grad, float* buf, long long n, const long long* seg_end, const float* seg_lr,
+                           const float* seg_wd, int n_seg, double momentum, double dampening, int nesterov, int step_no,
+                           long long* step_dev, float grad_scale, int zero_grad, step_stream_t stream, const float* amp = nullptr) {
+    if (n > 0) {
+        const long long nvec = n >> 2;
+        long long blocks = (nvec + 255) / 256;
+        constexpr int per_cu = 64;
+        if (blocks > 256LL * per_cu) blocks = 256LL * per_cu;   // as the Adam pass: 64 workgroups per CU, grid-stride beyond
+        // the scalars are Python doubles in torch: 1 - dampening is taken in double
+        const float mu = (float)momentum, omd = (float)(1.0 - dampening);
+        const int first = step_no == 1;
+#define STEP_SGD_LAUNCH(MAXSEG, MOM)                                                                                                  \
+    STEP_LAUNCH((sgd_flat_kernel<MAXSEG, MOM>), dim3((unsigned)blocks), dim3(256), stream, param, grad, buf, nvec, seg_end, seg_lr, seg_wd, \
+                n_seg, mu, omd, nesterov, first, grad_scale, zero_grad, (const long long*)step_dev, amp)
+        if (momentum != 0.) {
+            if (n_seg <= 512) STEP_SGD_LAUNCH(512, true); else STEP_SGD_LAUNCH(ADAM_MAX_SEG, true);
+        } else {
+            if (n_seg <= 512) STEP_SGD_LAUNCH(512, false); else STEP_SGD_LAUNCH(ADAM_MAX_SEG, false);
+        }
+#undef STEP_SGD_LAUNCH
+    }
+    if (step_dev) STEP_LAUNCH(sgd_count_kernel, dim3(1), dim3(64), stream, step_dev, amp);   // (also for an empty arena: the step counts)
+    return (n > 0 || step_dev) ? STEP_LAUNCH_CHECK() : STEP_OK;
+}
+
+int step_sgd_flat(float* param, float* grad, float* momentum_buf, long long n, const long long* seg_end, const float* seg_lr,
+                  const float* seg_wd, int n_seg, double momentum, double dampening, int nesterov, int step_no, float grad_scale,
+                  int zero_grad, step_stream_t stream) {
+    const int rc = sgd_flat_check(param, grad, momentum_buf, n, seg_end, seg_lr, seg_wd, n_seg, momentum, dampening, nesterov, step_no, nullptr);
+    if (rc) return rc;
+    return sgd_flat_launch(param, grad, momentum_buf, n, seg_end, seg_lr, seg_wd, n_seg, momentum, dampening, nesterov, step_no, nullptr,
+                           grad_scale, zero_grad, stream);
+}
+
+int step_sgd_flat_dev(float* param, float* grad, float* momentum_buf, long long n, const long long* seg_end, const float* seg_lr,
+                      const float* seg_wd, int n_seg, double momentum, double dampening, int nesterov, long long* step_dev,
+                      float grad_scale, int zero_grad, step_stream_t stream) {
+    if (!step_dev) return STEP_E_NULL;
+    const int rc = sgd_flat_check(param, grad, momentum_buf, n, seg_end, seg_lr, seg_wd, n_seg, momentum, dampening, nesterov, 0, step_dev);
+    if (rc) return rc;
+    return sgd_flat_launch(param, grad, momentum_buf, n, seg_end, seg_lr, seg_wd, n_seg, momentum, dampening, nesterov, 0, step_dev,
+                           grad_scale, zero_grad, stream);
+}
+
+int step_sgd_flat_amp(float* param, float* grad, float* momentum_buf, long long n, const long long* seg_end, const float* seg_lr,
+                      const float* seg_wd, int n_seg, double momentum, double dampening, int nesterov, long long* step_dev,
+                      float grad_scale, int zero_grad, float* amp_state, float growth_factor, float backoff_factor, int growth_interval,
+                      step_stream_t stream) {
+    if (!step_dev || !amp_state) return STEP_E_NULL;
+    if (growth_interval < 1 || !(growth_factor >= 1.f) || !(backoff_factor > 0.f && backoff_factor <= 1.f)) return STEP_E_SHAPE;
+    int rc = sgd_flat_check(param, grad, momentum_buf, n, seg_end, seg_lr, seg_wd, n_seg, momentum, dampening, nesterov, 0, step_dev);
+    if (rc) return rc;
+    if (n > 0) grad_scan_launch(grad, n, amp_state, stream);
+    rc = sgd_flat_launch(param, grad, momentum_buf, n, seg_end, seg_lr, seg_wd, n_seg, momentum, dampening, nesterov, 0, step_dev, grad_scale,
+                         zero_grad, stream, amp_state);
     if (rc) return rc;
     STEP_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), stream, amp_state, growth_factor, backoff_factor, growth_interval);
     return STEP_LAUNCH_CHECK();

@@ -1,4 +1,4 @@
-"""step_amd/optim.py -- FlatAdam: the optimizer of the training step.
+"""step_amd/optim.py -- FlatAdam / FlatSGD: the optimizers of the training step.
 
 The reference builds `optim.Adam(params, lr=args.det_lr)` (train.py:126) over the single-tensor parameter groups of
 utils/solver.py:12-93 (each with its own lr / weight_decay) and calls `optimizer.step()` once per iteration
@@ -11,6 +11,10 @@ utils/solver.py:12-93 (each with its own lr / weight_decay) and calls `optimizer
 * the gradient arena is one contiguous buffer, so the data-parallel exchange is a single large RCCL all-reduce
   (`step_amd.dist.allreduce_flat`, no bucket copies: xGMI rings are per-link bound, few large messages win), and the
   1/world_size of the average and the gradient clear are folded into the Adam pass (`grad_scale`, `zero_grad`).
+
+The reference's DEFAULT optimizer is `optim.SGD(params, lr=args.det_lr, momentum=args.momentum, weight_decay=args.weight_decay)`
+(train.py:123-124, config.py:51-57): FlatSGD is the same scheme on three arenas (one momentum buffer) and `step_sgd_flat`, 20 B/element.
+Both share the arena layer `_FlatOptimizer`, which is all that step_amd.dist and step_amd.workloads read.
 """
 import torch
 
@@ -29,7 +33,8 @@ class LossScaler:
         scaler.scale_loss(loss).backward()          # a device multiply: nothing here reads the scale on the host
         opt.step(scaler=scaler, zero_grad=True)     # overflow scan + unscale + skip-or-step + scale update: step_adam_flat_amp
 
-    The optimizer must be FlatAdam(capturable=True): a skipped step must not advance the step count, and only the device knows."""
+    The optimizer must be FlatAdam / FlatSGD(capturable=True): a skipped step must not advance the step count, and only the device knows
+    (for FlatSGD the count also decides which step initialises the momentum buffer)."""
 
     def __init__(self, device, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
         self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
@@ -52,17 +57,23 @@ class LossScaler:
         self.state.copy_(torch.tensor([float(sd["scale"]), float(sd["growth_tracker"]), 0.0, 0.0]))
 
 
-class FlatAdam(torch.optim.Optimizer):
-    """A torch.optim.Optimizer (the reference's schedulers subclass torch's _LRScheduler, which insists on one:
-    utils/solver.py:96,141) whose whole state lives in four flat arenas."""
+class _FlatOptimizer(torch.optim.Optimizer):
+    """The arena layer FlatAdam and FlatSGD share: parameters and gradients re-homed into `flat_param` / `flat_grad`, one zeroed arena
+    per name in `state_arenas`, the `_entries` / `numel` / `_seg_*` tables the kernels, step_amd.dist and step_amd.workloads read, the
+    host / device step count, and everything of step() around the subclass's launch (`_launch`)."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
-        # the base class normalises `params` into self.param_groups (fills lr / betas / eps / weight_decay defaults,
-        # rejects duplicates) exactly as it does for torch.optim.Adam
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
-        b, e = self.param_groups[0]["betas"], self.param_groups[0]["eps"]
-        if any(tuple(g["betas"]) != tuple(b) or g["eps"] != e for g in self.param_groups):
-            raise ValueError("FlatAdam: betas / eps must be the same for every group (one launch)")
+    def _check_groups(self):
+        """hyper-parameters that one launch cannot vary must agree across the groups"""
+
+    def _launch(self, L, grad_scale, zero_grad, scaler):
+        raise NotImplementedError
+
+    def __init__(self, params, defaults, state_arenas, capturable):
+        # the base class normalises `params` into self.param_groups (fills the defaults, rejects duplicates) exactly as it does for
+        # torch's own optimizers
+        super().__init__(params, defaults)
+        name = type(self).__name__
+        self._check_groups()
         self._entries = []                                       # (group index, parameter, offset, numel)
         off = 0
         for gi, g in enumerate(self.param_groups):
@@ -70,22 +81,22 @@ class FlatAdam(torch.optim.Optimizer):
                 if not p.requires_grad:
                     continue
                 if p.dtype != torch.float32:
-                    raise RuntimeError("FlatAdam: fp32 master parameters expected, got %s" % p.dtype)
+                    raise RuntimeError("%s: fp32 master parameters expected, got %s" % (name, p.dtype))
                 self._entries.append((gi, p, off, p.numel()))
                 off += -(-p.numel() // _ALIGN) * _ALIGN
         if not self._entries:
-            raise ValueError("FlatAdam: no trainable parameter")
+            raise ValueError("%s: no trainable parameter" % name)
         if len(self._entries) > 4096:
-            raise RuntimeError("FlatAdam: more than 4096 tensors")
+            raise RuntimeError("%s: more than 4096 tensors" % name)
         dev = self._entries[0][1].device
         if any(p.device != dev for _, p, _, _ in self._entries):
-            raise RuntimeError("FlatAdam: all parameters must live on one device (one process per GPU)")
+            raise RuntimeError("%s: all parameters must live on one device (one process per GPU)" % name)
         _lib.dptr(self._entries[0][1].data)                      # refuses non-device tensors: there is no CPU fallback
         self.device, self.numel = dev, off
         self.flat_param = torch.zeros(off, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=dev)
+        for a in state_arenas:
+            setattr(self, a, torch.zeros(off, dtype=torch.float32, device=dev))
         with torch.no_grad():
             for _, p, o, n in self._entries:
                 self.flat_param[o:o + n].copy_(p.data.reshape(-1))
@@ -99,10 +110,9 @@ class FlatAdam(torch.optim.Optimizer):
         self._seg_wd = torch.zeros(len(ends), dtype=torch.float32, device=dev)
         self._tables = None
         # capturable (as torch.optim.Adam's flag): the step counter lives on the device and step() is free of host scalars, so a
-        # whole training step can be captured in a HIP graph and replayed (step_adam_flat_dev)
+        # whole training step can be captured in a HIP graph and replayed (step_adam_flat_dev / step_sgd_flat_dev)
         self.capturable = bool(capturable)
         self._step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._bias_corr = torch.zeros(2, dtype=torch.float32, device=dev)
         self._step_host = 0
 
     @property
@@ -124,11 +134,11 @@ class FlatAdam(torch.optim.Optimizer):
 
     def _gather_stray_grads(self):
         # a caller that replaced p.grad (set_to_none, grad = tensor): fold it back into the arena.
-        # Known divergence from torch.optim.Adam (documented, not emulated): torch SKIPS a parameter whose .grad is None -- no
+        # Known divergence from torch.optim.Adam / SGD (documented, not emulated): torch SKIPS a parameter whose .grad is None -- no
         # moment decay, no step count -- while the one launch here treats it as a zero gradient at the shared step count (its
-        # moments decay and the parameter keeps moving along exp_avg).  The reference's loop never produces that case: every
-        # parameter of get_params() receives a gradient in every iteration (train.py:318-348), and zero_grad() here keeps the
-        # gradients as views of the arena instead of dropping them.
+        # moments decay and the parameter keeps moving along exp_avg / the momentum buffer).  The reference's loop never produces that
+        # case: every parameter of get_params() receives a gradient in every iteration (train.py:318-348), and zero_grad() here keeps
+        # the gradients as views of the arena instead of dropping them.
         base = self.flat_grad.data_ptr()
         for _, p, o, n in self._entries:
             g = p.grad
@@ -152,7 +162,7 @@ class FlatAdam(torch.optim.Optimizer):
         """optimizer.step() (train.py:348): one kernel launch.  grad_scale multiplies every gradient on the way in
         (1/world_size after a SUM all-reduce, 1/loss_scale); zero_grad=True clears the gradient arena in the same pass.
         scaler = a LossScaler whose scale the loss was multiplied by: the gradients are scanned for inf / nan, unscaled, and the
-        step is skipped on overflow (apex O1 / GradScaler semantics), all on the device (step_adam_flat_amp)."""
+        step is skipped on overflow (apex O1 / GradScaler semantics), all on the device (step_adam_flat_amp / step_sgd_flat_amp)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -161,41 +171,18 @@ class FlatAdam(torch.optim.Optimizer):
         wgrad_sync()                                             # weight gradients still in flight on the side stream
         self._gather_stray_grads()
         self._refresh_tables()
-        g0 = self.param_groups[0]
-        L = _lib.lib()
-        if scaler is not None:
-            if not self.capturable:
-                raise RuntimeError("FlatAdam.step(scaler=...): build the optimizer with capturable=True (a skipped step must not count, "
-                                   "and only the device knows whether it was skipped)")
-            _capi.check(L.step_adam_flat_amp(_lib.dptr(self.flat_param), _lib.dptr(self.flat_grad), _lib.dptr(self.exp_avg),
-                                             _lib.dptr(self.exp_avg_sq), self.numel, _lib.dptr(self._seg_end), _lib.dptr(self._seg_lr),
-                                             _lib.dptr(self._seg_wd), len(self._entries), float(g0["betas"][0]), float(g0["betas"][1]),
-                                             float(g0["eps"]), _lib.dptr(self._step_dev), _lib.dptr(self._bias_corr), float(grad_scale),
-                                             int(bool(zero_grad)), _lib.dptr(scaler.state), scaler.growth_factor, scaler.backoff_factor,
-                                             scaler.growth_interval, _lib.stream_ptr(self.device)), "step_adam_flat_amp")
-        elif self.capturable:
-            _capi.check(L.step_adam_flat_dev(_lib.dptr(self.flat_param), _lib.dptr(self.flat_grad), _lib.dptr(self.exp_avg),
-                                             _lib.dptr(self.exp_avg_sq), self.numel, _lib.dptr(self._seg_end), _lib.dptr(self._seg_lr),
-                                             _lib.dptr(self._seg_wd), len(self._entries), float(g0["betas"][0]), float(g0["betas"][1]),
-                                             float(g0["eps"]), _lib.dptr(self._step_dev), _lib.dptr(self._bias_corr), float(grad_scale),
-                                             int(bool(zero_grad)), _lib.stream_ptr(self.device)), "step_adam_flat_dev")
-        else:
-            self._step_host += 1
-            _capi.check(L.step_adam_flat(_lib.dptr(self.flat_param), _lib.dptr(self.flat_grad), _lib.dptr(self.exp_avg),
-                                         _lib.dptr(self.exp_avg_sq), self.numel, _lib.dptr(self._seg_end), _lib.dptr(self._seg_lr),
-                                         _lib.dptr(self._seg_wd), len(self._entries), float(g0["betas"][0]), float(g0["betas"][1]),
-                                         float(g0["eps"]), self._step_host, float(grad_scale), int(bool(zero_grad)),
-                                         _lib.stream_ptr(self.device)), "step_adam_flat")
+        if scaler is not None and not self.capturable:
+            raise RuntimeError("%s.step(scaler=...): build the optimizer with capturable=True (a skipped step must not count, "
+                               "and only the device knows whether it was skipped)" % type(self).__name__)
+        self._launch(_lib.lib(), float(grad_scale), int(bool(zero_grad)), scaler)
         # the kernel wrote through raw pointers: bump the autograd version counters (the packed-weight caches of
         # backbone.py / heads.py are keyed on them)
         torch.autograd.graph.increment_version([p for _, p, _, _ in self._entries])
         return loss
 
-    def state_dict(self):
-        """Same structure as torch.optim.Adam.state_dict() (checkpoints: train.py:382,437)."""
-        state, idx = {}, {}
-        k = 0
-        packed_groups = []
+    # -- checkpoints: torch's own structure ({"state": {index: {...}}, "param_groups": [... "params": [indices]]}) ------------------
+    def _pack_groups(self):
+        idx, k, packed_groups = {}, 0, []
         for g in self.param_groups:
             ids = []
             for p in g["params"]:
@@ -205,6 +192,56 @@ class FlatAdam(torch.optim.Optimizer):
             pg = {kk: vv for kk, vv in g.items() if kk != "params"}
             pg["params"] = ids
             packed_groups.append(pg)
+        return packed_groups, idx
+
+    def _unpack_groups(self, sd):
+        groups = sd["param_groups"]
+        if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"]) for a, b in zip(groups, self.param_groups)):
+            raise ValueError("%s.load_state_dict: parameter groups do not match" % type(self).__name__)
+        idx = {}
+        for a, b in zip(groups, self.param_groups):
+            for k, p in zip(a["params"], b["params"]):
+                idx[id(p)] = k
+            for kk, vv in a.items():
+                if kk != "params":
+                    b[kk] = vv
+        self._tables = None
+        return idx
+
+
+class FlatAdam(_FlatOptimizer):
+    """A torch.optim.Optimizer (the reference's schedulers subclass torch's _LRScheduler, which insists on one:
+    utils/solver.py:96,141) whose whole state lives in four flat arenas."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay), ("exp_avg", "exp_avg_sq"), capturable)
+        self._bias_corr = torch.zeros(2, dtype=torch.float32, device=self.device)
+
+    def _check_groups(self):
+        b, e = self.param_groups[0]["betas"], self.param_groups[0]["eps"]
+        if any(tuple(g["betas"]) != tuple(b) or g["eps"] != e for g in self.param_groups):
+            raise ValueError("FlatAdam: betas / eps must be the same for every group (one launch)")
+
+    def _launch(self, L, grad_scale, zero_grad, scaler):
+        g0 = self.param_groups[0]
+        head = (_lib.dptr(self.flat_param), _lib.dptr(self.flat_grad), _lib.dptr(self.exp_avg), _lib.dptr(self.exp_avg_sq), self.numel,
+                _lib.dptr(self._seg_end), _lib.dptr(self._seg_lr), _lib.dptr(self._seg_wd), len(self._entries), float(g0["betas"][0]),
+                float(g0["betas"][1]), float(g0["eps"]))
+        if scaler is not None:
+            _capi.check(L.step_adam_flat_amp(*head, _lib.dptr(self._step_dev), _lib.dptr(self._bias_corr), grad_scale, zero_grad,
+                                             _lib.dptr(scaler.state), scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval,
+                                             _lib.stream_ptr(self.device)), "step_adam_flat_amp")
+        elif self.capturable:
+            _capi.check(L.step_adam_flat_dev(*head, _lib.dptr(self._step_dev), _lib.dptr(self._bias_corr), grad_scale, zero_grad,
+                                             _lib.stream_ptr(self.device)), "step_adam_flat_dev")
+        else:
+            self._step_host += 1
+            _capi.check(L.step_adam_flat(*head, self._step_host, grad_scale, zero_grad, _lib.stream_ptr(self.device)), "step_adam_flat")
+
+    def state_dict(self):
+        """Same structure as torch.optim.Adam.state_dict() (checkpoints: train.py:382,437)."""
+        packed_groups, idx = self._pack_groups()
+        state = {}
         if self.step_count:
             for _, p, o, n in self._entries:
                 state[idx[id(p)]] = {"step": torch.tensor(float(self.step_count)),
@@ -214,16 +251,7 @@ class FlatAdam(torch.optim.Optimizer):
 
     def load_state_dict(self, sd):
         """optimizer.load_state_dict(checkpoint['optimizer']) (train.py:205); accepts torch.optim.Adam's own dicts."""
-        groups = sd["param_groups"]
-        if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"]) for a, b in zip(groups, self.param_groups)):
-            raise ValueError("FlatAdam.load_state_dict: parameter groups do not match")
-        idx = {}
-        for a, b in zip(groups, self.param_groups):
-            for k, p in zip(a["params"], b["params"]):
-                idx[id(p)] = k
-            for kk, vv in a.items():
-                if kk != "params":
-                    b[kk] = vv
+        idx = self._unpack_groups(sd)
         steps = set()
         with torch.no_grad():
             self.exp_avg.zero_()
@@ -239,4 +267,98 @@ class FlatAdam(torch.optim.Optimizer):
         if len(steps) != 1:
             raise ValueError("FlatAdam.load_state_dict: parameters are at different step counts %s" % sorted(steps))
         self.step_count = steps.pop()
-        self._tables = None
+
+
+class FlatSGD(_FlatOptimizer):
+    """The reference's default optimizer -- `optim.SGD(params, lr=args.det_lr, momentum=args.momentum, weight_decay=args.weight_decay)`
+    (train.py:123-124; config.py:51-57: momentum 0.9, weight decay 1e-7) -- on three flat arenas: same constructor arguments, same
+    `param_groups` / `zero_grad` / `step` / `state_dict` surface, accepted by the reference's _LRScheduler subclasses (utils/solver.py:96,141);
+    step() is ONE launch of `step_sgd_flat` (include/step_amd.h), 12 B read + 8 B written per element.  `momentum`, `dampening` and
+    `nesterov` must agree across the groups (one launch); `lr` and `weight_decay` are per group.  momentum == 0 keeps no buffer
+    (`momentum_buffer` is None), as torch keeps no state then.
+
+    torch's SGD has no step number: a parameter's "momentum_buffer" being present means "past the first step", which only decides whether
+    the buffer is initialised (buf = g) or updated.  Here `step_count` plays that role for all parameters at once, on the device when
+    capturable=True -- a step skipped by the loss scaler does not count, so the first clean step still initialises the buffer.
+    The divergence documented in `_gather_stray_grads` (a parameter whose .grad is None is treated as a zero gradient instead of
+    being skipped) applies here as it does to FlatAdam."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, capturable=False):
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: %r" % (lr,))
+        if momentum < 0.0:
+            raise ValueError("Invalid momentum value: %r" % (momentum,))
+        if weight_decay < 0.0:
+            raise ValueError("Invalid weight_decay value: %r" % (weight_decay,))
+        # (maximize / foreach / differentiable / fused: torch.optim.SGD's remaining group keys at their defaults, so that a state_dict
+        # of this class loads into torch's and the loaded optimizer can step)
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=False,
+                        foreach=None, differentiable=False, fused=None)
+        groups = list(params)
+        first = groups[0] if groups and isinstance(groups[0], dict) else {}
+        state = ("momentum_buffer",) if first.get("momentum", momentum) != 0 else ()
+        super().__init__(groups, defaults, state, capturable)
+        if not state:
+            self.momentum_buffer = None
+
+    def _check_groups(self):
+        g0 = self.param_groups[0]
+        key = lambda g: (g["momentum"], g["dampening"], bool(g["nesterov"]))
+        if any(key(g) != key(g0) for g in self.param_groups):
+            raise ValueError("FlatSGD: momentum / dampening / nesterov must be the same for every group (one launch)")
+        if g0["momentum"] < 0.0:
+            raise ValueError("Invalid momentum value: %r" % (g0["momentum"],))
+        if g0["nesterov"] and (g0["momentum"] <= 0 or g0["dampening"] != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if any(g.get("maximize") for g in self.param_groups):
+            raise ValueError("FlatSGD: maximize is not supported")
+
+    def _launch(self, L, grad_scale, zero_grad, scaler):
+        g0 = self.param_groups[0]
+        if (g0["momentum"] != 0) != (self.momentum_buffer is not None):
+            raise RuntimeError("FlatSGD: momentum changed between zero and non-zero after construction (the buffer arena is fixed)")
+        head = (_lib.dptr(self.flat_param), _lib.dptr(self.flat_grad), _lib.dptr(self.momentum_buffer), self.numel, _lib.dptr(self._seg_end),
+                _lib.dptr(self._seg_lr), _lib.dptr(self._seg_wd), len(self._entries), float(g0["momentum"]), float(g0["dampening"]),
+                int(bool(g0["nesterov"])))
+        if scaler is not None:
+            _capi.check(L.step_sgd_flat_amp(*head, _lib.dptr(self._step_dev), grad_scale, zero_grad, _lib.dptr(scaler.state),
+                                            scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval,
+                                            _lib.stream_ptr(self.device)), "step_sgd_flat_amp")
+        elif self.capturable:
+            _capi.check(L.step_sgd_flat_dev(*head, _lib.dptr(self._step_dev), grad_scale, zero_grad, _lib.stream_ptr(self.device)),
+                        "step_sgd_flat_dev")
+        else:
+            self._step_host += 1
+            _capi.check(L.step_sgd_flat(*head, self._step_host, grad_scale, zero_grad, _lib.stream_ptr(self.device)), "step_sgd_flat")
+
+    def state_dict(self):
+        """Same structure as torch.optim.SGD.state_dict() (checkpoints: train.py:382,437): state[k] = {"momentum_buffer": tensor} once a
+        step was taken with momentum != 0, nothing before (and nothing at all with momentum == 0)."""
+        packed_groups, idx = self._pack_groups()
+        state = {}
+        if self.momentum_buffer is not None and self.step_count:
+            for _, p, o, n in self._entries:
+                state[idx[id(p)]] = {"momentum_buffer": self.momentum_buffer[o:o + n].view(p.shape).clone()}
+        return {"state": state, "param_groups": packed_groups}
+
+    def load_state_dict(self, sd):
+        """optimizer.load_state_dict(checkpoint['optimizer']) (train.py:205); accepts torch.optim.SGD's own dicts.  No buffers in the
+        dict: the step count is reset to 0 (the next step initialises the buffer); buffers present: the count becomes >= 1 (it is kept
+        when it already is, torch's dicts carry no step number)."""
+        idx = self._unpack_groups(sd)
+        self._check_groups()
+        have = set()
+        with torch.no_grad():
+            if self.momentum_buffer is not None:
+                self.momentum_buffer.zero_()
+            for _, p, o, n in self._entries:
+                st = sd["state"].get(idx[id(p)])
+                buf = None if st is None else st.get("momentum_buffer")
+                have.add(buf is not None)
+                if buf is not None:
+                    if self.momentum_buffer is None:
+                        raise ValueError("FlatSGD.load_state_dict: the checkpoint holds momentum buffers, this optimizer was built with momentum == 0")
+                    self.momentum_buffer[o:o + n].copy_(buf.reshape(-1))
+        if len(have) != 1:
+            raise ValueError("FlatSGD.load_state_dict: some parameters have a momentum buffer and some do not")
+        self.step_count = max(self.step_count, 1) if have.pop() else 0

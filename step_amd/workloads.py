@@ -10,7 +10,7 @@ from . import BaseNet, ContextNet, ROINet, TwoBranchNet
 from . import dist as sdist
 from .driver import GraphedInference, inference, inference_flat, postprocess
 from .backbone import wgrad_into_grad
-from .optim import FlatAdam
+from .optim import FlatAdam, FlatSGD
 from .selection import train_select
 from .driver import _flat_tubes
 from .tube_math import generate_anchors
@@ -99,11 +99,13 @@ class C4TrainStep:
     """One optimisation step on `batch` AVA-shaped clips per rank (fp32): backbone + ContextNet + the max_iter = 3 heads on
     tubes of 3, 3 and 9 frames (NUM_CHUNKS 1, 1, 3), the three losses of train.py:318-331 summed over the steps
     (lambda_reg 5, lambda_nbr 1), ONE flat gradient all-reduce over ranks (step_amd.dist.allreduce_flat), ONE fused Adam
-    launch that also applies 1/world and clears the gradients (step_amd.optim.FlatAdam).  The reference's proposal
+    launch that also applies 1/world and clears the gradients (step_amd.optim.FlatAdam; optimizer="sgd": step_amd.optim.FlatSGD, the
+    reference's default optimizer, in its place -- same arenas, same exchange, same capture).  The reference's proposal
     selection between steps (utils/utils.py:135-423, host Python) is not part of the hot path: every step trains on the
     same `tubes_per_clip` anchor tubes, extended to the step's length."""
 
-    def __init__(self, dev, batch=1, tubes_per_clip=5, seed=123, max_iter=3, dtype=torch.float32, capturable=False, force_exchange=False):
+    def __init__(self, dev, batch=1, tubes_per_clip=5, seed=123, max_iter=3, dtype=torch.float32, capturable=False, force_exchange=False,
+                 optimizer="adam"):
         # replicas: the same weights on every rank (same init seed, then rank 0's copy is broadcast once, as DDP does);
         # `seed` only varies the rank's clips
         self.args, self.base, self.ctx, self.nets = build_nets(dev, 123, heads=max_iter)
@@ -113,7 +115,14 @@ class C4TrainStep:
         for m in self.mods:
             m.train()
         self.params = [p for m in self.mods for p in m.parameters() if p.requires_grad]
-        self.opt = FlatAdam(self.params, lr=1e-5, capturable=capturable)
+        # "adam": what the reference's scripts pick (train.py:126); "sgd": its default (train.py:123-124 with config.py:51-57's momentum
+        # and weight decay).  Everything below reads the optimizer through the arena layer the two share (step_amd.optim._FlatOptimizer)
+        if optimizer == "adam":
+            self.opt = FlatAdam(self.params, lr=1e-5, capturable=capturable)
+        elif optimizer == "sgd":
+            self.opt = FlatSGD(self.params, lr=1e-5, momentum=0.9, weight_decay=1e-7, capturable=capturable)
+        else:
+            raise ValueError("C4TrainStep: optimizer is 'adam' or 'sgd', got %r" % (optimizer,))
         self.graph = None
         self.graph_mode = None                                   # "one" | "split" after capture()
         self._g_update = None
@@ -217,7 +226,7 @@ class C4TrainStep:
         Runs `warmup` eager steps first (caches, pack tables, workspaces, the communicator); the captured step itself is recorded,
         not executed."""
         if not self.opt.capturable:
-            raise RuntimeError("C4TrainStep.capture: build the workload with capturable=True (device-side Adam step counter)")
+            raise RuntimeError("C4TrainStep.capture: build the workload with capturable=True (device-side optimizer step counter)")
         import gc
         dd = torch.distributed
         grouped = self.reducer.active
@@ -307,8 +316,10 @@ class C4SelectTrainStep(C4TrainStep):
                       backward, ONE eager flat all-reduce, graph U = re-pack + Adam -- the split form, nothing of the group is recorded).
                       Same kernels on the same buffers as step_padded(): bit-identical trajectory (tests/test_gpu_graph_step.py)."""
 
-    def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, tubes_per_clip=34, capturable=False, force_exchange=False, budget=None):
-        super().__init__(dev, batch=batch, tubes_per_clip=5, seed=seed, max_iter=3, dtype=dtype, capturable=capturable, force_exchange=force_exchange)
+    def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, tubes_per_clip=34, capturable=False, force_exchange=False, budget=None,
+                 optimizer="adam"):
+        super().__init__(dev, batch=batch, tubes_per_clip=5, seed=seed, max_iter=3, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
+                         optimizer=optimizer)
         rs = np.random.RandomState(seed)
         anchors = (generate_anchors()[:tubes_per_clip] * 400.0).astype(np.float32)
         self.init_tubes = [np.tile(anchors[:, None, :], (1, 3, 1)) for _ in range(batch)]

@@ -16,6 +16,8 @@ Every rank
   5. replays it --iters times, the learning-rate schedule written through `optimizer.param_groups` exactly as the reference's
      schedulers do (utils/solver.py:96-180: the captured Adam reads per-group lr / weight_decay from device tables that
      `step()` refreshes from the param groups),
+     --optimizer sgd trains with the reference's default optimizer instead (train.py:123-124: SGD with momentum, step_amd.FlatSGD) --
+     same arenas, same exchange, same captured step,
   6. rank 0 prints one JSON line per --log-every iterations and a final summary (loss, ms per iteration, clips/s of the whole job).
 
 Data: synthetic AVA-shaped clips [B,36,3,400,400] and fixed anchor tubes (there is no dataset in this repository; the reference's
@@ -42,6 +44,11 @@ def main():
     ap.add_argument("--tubes", type=int, default=5, help="tubes per clip and step")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"])
     ap.add_argument("--lr", type=float, default=1e-5)
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "sgd"],
+                    help="adam: what the reference's scripts pick (train.py:126); sgd: its default, optim.SGD with momentum (train.py:123-124)")
+    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd (config.py:55)")
+    ap.add_argument("--weight-decay", type=float, default=None,
+                    help="every group's weight decay (default: the optimizer's own -- 0 for adam, 1e-7 for sgd as config.py:57)")
     ap.add_argument("--warmup-iters", type=int, default=3, help="eager iterations before the capture (caches, workspaces, communicator)")
     ap.add_argument("--lr-decay-every", type=int, default=0, help="> 0: multiply every group's lr by 0.1 every that many iterations (scheduler stand-in)")
     ap.add_argument("--no-graph", action="store_true")
@@ -55,6 +62,8 @@ def main():
                     help="process-group backend (default: nccl = RCCL; gloo only to exercise the multi-rank program with ranks SHARING one GPU, "
                          "which RCCL refuses -- the exchange is then one eager flat all-reduce between two captured graphs)")
     a = ap.parse_args()
+    if a.optimizer == "sgd" and a.momentum <= 0:
+        raise SystemExit("train_step_amd.py: --momentum must be positive (the workload's momentum buffer is allocated at construction)")
     if not torch.cuda.is_available():
         raise SystemExit("train_step_amd.py needs a ROCm device (there is no CPU fallback)")
 
@@ -75,11 +84,16 @@ def main():
         import numpy as np
         random.seed(1000 + rank)                                 # (the selection draws from the reference's two host RNG streams)
         np.random.seed(1000 + rank)
-        w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=graphed)
+        w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=graphed, optimizer=a.optimizer)
     else:
-        w = workloads.C4TrainStep(dev, batch=len(mine), tubes_per_clip=a.tubes, seed=123 + rank, dtype=tdt, capturable=graphed)
+        w = workloads.C4TrainStep(dev, batch=len(mine), tubes_per_clip=a.tubes, seed=123 + rank, dtype=tdt, capturable=graphed,
+                                  optimizer=a.optimizer)
     for g in w.opt.param_groups:
         g["lr"] = a.lr
+        if a.optimizer == "sgd":
+            g["momentum"] = a.momentum
+        if a.weight_decay is not None:
+            g["weight_decay"] = a.weight_decay
     if graphed:
         w.capture(warmup=a.warmup_iters, mode=a.graph)             # (C4SelectTrainStep: its own graph forms; `mode` only matters for the fixed-tube step)
     else:
@@ -142,7 +156,8 @@ def main():
                           "ms_per_iter": round(el / max(a.iters, 1) * 1e3, 3), "clips_per_s": round(gb * a.iters / el, 3),
                           "launch": ("hipGraph replay (%s)" % w.graph_mode) if w.graph is not None else "eager",
                           "gradient_exchange": _exchange_label(w, world),
-                          "feed": a.feed, "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "adam_steps": w.opt.step_count}), flush=True)
+                          "feed": a.feed, "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
+                          **({"adam_steps": w.opt.step_count} if a.optimizer == "adam" else {})}), flush=True)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
