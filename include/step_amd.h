@@ -103,13 +103,17 @@ enum {
     STEP_OPT_CONV_NB_RULE,     /*  0 (default): conv_tap's accumulator depth minimises ROUNDS of the chip (the latency of one launch) | 1: minimises workgroups x per-workgroup time (the chip time of the launch: what counts with several batches in flight); same K order per output either way (bit-identical) */
     STEP_OPT_THROUGHPUT,       /*  0 (default): launch shapes tuned for the LATENCY of one batch | 1: for several independent batches in flight on separate streams (a serving loop) --
                                     a block's pointwise conv is launched on its own instead of riding in the 3x3x3 members' grid (the other batch fills the idle CUs; measured
-                                    C2 +1.3 % at two in flight, -2.2 % one batch at a time).  Same bits either way */
+                                    C2 +1.3 % at two in flight, -2.2 % one batch at a time); a group with a pixel-split narrow member (STEP_OPT_CONV_GROUP_NARROW)
+                                    keeps its pointwise conv in the grid.  Same bits either way */
     STEP_OPT_CONV_PERSIST,     /*  1 (default): one-channel-group conv_tap launches of more than one round of the chip run as a PERSISTENT tile loop, one workgroup per CU
                                     (the weight ring never drains, the next tile's halo is requested inside the current tile's epilogue) where the library has that
                                     form (the fused conv3d_2b -> conv3d_2c -> maxPool3d_3a call) | 0: one workgroup per tile (bit-identical) */
     STEP_OPT_CONV_PWS_WAVES,   /*  0 (default): the weight-stationary pointwise stream runs sixteen waves per workgroup where that gives every wave at most ONE 32-pixel
                                     group and eight waves do not (the 28x28 maps of 8 clips: 3136 groups), outside the throughput profile; eight otherwise | 8 | 16
                                     (bit-identical) */
+    STEP_OPT_CONV_GROUP_NARROW,/*  1 (default): the narrow 3x3x3 members of step_conv_forward_group (Cin <= 32, Cout <= 96: an Inception block's branch_2) run the
+                                    pixel-split body (512-pixel boxes, both wave groups on pixels, no zero k16 step) where the measured rule of conv_igemm.hip admits
+                                    their map | 2: wherever the form is eligible (tests / A-B) | 0: every member on the partner's instantiation (bit-identical) */
     STEP_OPT_COUNT_
 };
 STEP_API int step_set_option(int option, int value);

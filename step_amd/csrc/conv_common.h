@@ -35,6 +35,7 @@ struct ConvParams {
     // [0, s_split) read x, the rest x2 (same pixels); x2 = null everywhere else
     const void* x2; int x2_cstride, x2_coff, s_split;
     int gpersist;        // > 0: launch the PERSISTENT form with this many workgroups (each walks virtual ids id, id + gpersist, ... < gcount); 0: one workgroup per id
+    int narrow;          // grouped launches: this member runs the pixel-split body (conv_tap_narrow.h; gtd x gth x gtw is then a box of <= 512 pixels)
     int nchunks;   // ceil(Cin / 32)
     int nchunks32; // same (the packed-weight K extent is 2*nchunks32 k16 blocks)
     int vec_epi;   // 16-byte output stores are legal (channel strides/offsets % 8 == 0, pointers 16-B aligned)
@@ -199,6 +200,9 @@ __host__ __device__ constexpr int conv_gen_npix(int wv, int nb) {
     return wv == 8 ? (nb == 1 ? CONV_GEN_NPIX_SMALL : CONV_GEN_NPIX) : (nb >= 3 ? CONV_GEN_NPIX4 : CONV_GEN_NPIX4_WIDE);
 }
 
+// the pixel-split body of a grouped launch's narrow members (conv_tap_narrow.h): halo pixels reserved for a box of <= 512 pixels (90 KiB)
+constexpr int CONV_NARROW_NPIX = 1152;
+
 static inline unsigned flat_grid(long long total, int block) {
     long long g = ceil_div64(total, block);
     if (g > 16384) g = 16384;
@@ -220,6 +224,7 @@ template <> int conv_tap_ph_launch<f16_t>(const ConvPlan& pl, const ConvParams& 
 template <typename T> int conv_tap_group_launch(int twl, int NB, const ConvGroupParams& g, dim3 grid, step_stream_t stream);       // conv_tap_ph_<dtype>.hip
 template <> int conv_tap_group_launch<bf16_t>(int twl, int NB, const ConvGroupParams& g, dim3 grid, step_stream_t stream);
 template <> int conv_tap_group_launch<f16_t>(int twl, int NB, const ConvGroupParams& g, dim3 grid, step_stream_t stream);
+// (a group with a member marked p.narrow -- general boxes only -- is launched as conv_tap_group[_pw]_kernel_narrow, conv_tap_narrow.h)
 template <typename T> int conv_pw_launch(int NB, int wv, const ConvParams& p, dim3 grid, step_stream_t stream);                        // conv_pw.hip
 template <typename T> int conv_pws_launch(int nbw, const ConvParams& p, dim3 grid, step_stream_t stream);                              // conv_pw.hip (weight-stationary stream, 16-bit)
 // conv_pws_kernel: nbw channel blocks per workgroup, KC16 16-channel chunks -> blocks per pass (<= 3: registers), 64-channel steps

@@ -840,7 +840,7 @@ static int conv_fill_params(const step_conv_desc* d, const void* x, const void* 
     p.x_cstride = d->x_cstride; p.x_coff = d->x_coff; p.y_cstride = d->y_cstride; p.y_coff = d->y_coff;
     p.r_cstride = d->res_cstride; p.r_coff = d->res_coff;
     p.relu = d->relu;
-    p.tiles_h = p.tiles_w = 0; p.tiles_d = d->D; p.gtd = p.gth = p.gtw = 1; p.gmode = 0; p.gx = p.gy = 0; p.tile0 = 0; p.gbase = 0; p.gcount = 0; p.gpersist = 0;
+    p.tiles_h = p.tiles_w = 0; p.tiles_d = d->D; p.gtd = p.gth = p.gtw = 1; p.gmode = 0; p.gx = p.gy = 0; p.tile0 = 0; p.gbase = 0; p.gcount = 0; p.gpersist = 0; p.narrow = 0;
     p.x2 = nullptr; p.x2_cstride = p.x2_coff = p.s_split = 0;
     p.nchunks = ceil_div(d->Cin, CK);
     p.nchunks32 = p.nchunks;
@@ -1140,6 +1140,41 @@ static bool conv_group_plan(const step_conv_item* items, int n, step_conv_desc* 
     return true;
 }
 
+// Which members of a planned group run the pixel-split body (conv_tap_narrow.h) instead of their partner's instantiation: one input slab
+// (Cin <= 32), at most three channel blocks (whatever the partner's depth: the grouped kernel carries every narrow body), general boxes,
+// vector epilogue or not, no residual (the caller has already excluded split outputs).  Such a member gets a box
+// of <= 512 pixels of its own (pls[k] is rewritten: box, tile counts, gmode) and ONE channel group.
+// Which maps (STEP_OPT_CONV_GROUP_NARROW = 1): the form halves the member's workgroup count, so it is taken where the member still is a
+// substantial share of a round of the chip -- at least CONV_NARROW_MIN_TILES 512-pixel tiles.  C2 (8 clips): the 28x28 members of Mixed_3b /
+// 3c are 224 tiles and take it; the 14x14 members of Mixed_4b-4e would be 32 tiles, cost nothing with two batches in flight on today's path
+// (profiles/r05_skip_b2b.txt) and stay there.  Measured on MI355X, whole step, variants interleaved in one process
+// (profiles/r07_ab_conv_group_narrow.txt), one batch at a time / two in flight:
+//   C2, the rule (28x28 members only)   1.2123 -> 1.1983 ms / 1.0749 -> 1.0543 ms (noise floor of the call 0.08 % / 0.17 %)
+//   C2, every eligible member (mode 2)  1.1987 / 1.0584 ms against the rule's 1.1925 / 1.0563 ms in that call: the 14x14 members LOSE
+//     (32 boxes each; their NB = 1 partner also drops from two resident workgroups to one under the shared 117.5 KB arena)
+//   C5 (50x50 / 100x100 maps, every member past the tile count)  3.6660 -> 3.6229 ms / 3.4660 -> 3.4326 ms
+//   C3, 34 tubes (bench.py, alternating with the parent)  707.6 / 707.1 -> 713.9 / 711.5 clips/s
+constexpr long long CONV_NARROW_MIN_TILES = 128;
+static void conv_group_narrow_plan(const step_conv_item* items, int n, const step_conv_desc* canon, const ConvParams* ps, ConvPlan* pls, bool* narrow) {
+    for (int k = 0; k < n; ++k) narrow[k] = false;
+    const int mode = opt(STEP_OPT_CONV_GROUP_NARROW);
+    if (mode == 0) return;
+    for (int k = 0; k < n; ++k) {
+        const step_conv_desc& d = canon[k];
+        if (pls[k].twl != 0 || d.Cin > 32 || d.Cout > 96 || ps[k].nchunks32 != 1 || items[k].res) continue;
+        int td = 1, th = 1, tw = 1;
+        const long long tiles = best_gen_box(d.D, d.H, d.W, 3, CONV_NARROW_NPIX, &td, &th, &tw, 512);
+        if (tiles <= 0) continue;
+        if (mode == 1 && tiles * d.N < CONV_NARROW_MIN_TILES) continue;
+        ConvPlan& pl = pls[k];
+        pl.gtd = td; pl.gth = th; pl.gtw = tw;
+        pl.gmode = gen_gmode(td, th, tw, 512);
+        pl.tiles_d = ceil_div(d.D, td); pl.tiles_h = ceil_div(d.H, th); pl.tiles_w = ceil_div(d.W, tw);
+        pl.mtiles = (long long)d.N * tiles;
+        narrow[k] = true;
+    }
+}
+
 // The members of a grouped launch: the 3x3x3 items that share one conv_tap instantiation and, optionally, ONE pointwise item the
 // planner sends to conv_pw_kernel<T, 1, 4> (plain epilogue).  tap[] / pw index into items; returns false when the items do not
 // group (the caller launches them one by one).
@@ -1200,6 +1235,8 @@ int step_conv_forward_group(const step_conv_item* items, int n, step_stream_t st
         }
         int NBc = 0;
         if (ok && conv_group_plan(taps, sel.ntap, canon, ps, pls, &NBc)) {
+            bool narrow[CONV_GROUP_MAX];
+            conv_group_narrow_plan(taps, sel.ntap, canon, ps, pls, narrow);
             ConvGroupParams g;
             g.n = sel.ntap;
             // longest workgroups first (they are dispatched first): descending K depth
@@ -1215,7 +1252,8 @@ int step_conv_forward_group(const step_conv_item* items, int n, step_stream_t st
                 p.tiles_h = pl.tiles_h; p.tiles_w = pl.tiles_w; p.tiles_d = pl.tiles_d;
                 p.gtd = pl.gtd; p.gth = pl.gth; p.gtw = pl.gtw; p.gmode = pl.gmode;
                 conv_set_box_magic(p, canon[k].kh, canon[k].kw);
-                const int groups = ceil_div(p.nblk32, 2 * NBc);
+                p.narrow = narrow[k] ? 1 : 0;
+                const int groups = narrow[k] ? 1 : ceil_div(p.nblk32, 2 * NBc);
                 p.gx = (int)pl.mtiles; p.gy = groups;
                 const long long tot = (pl.mtiles * groups + 7) / 8 * 8;
                 p.gbase = (int)base; p.gcount = (int)tot;
@@ -1227,7 +1265,11 @@ int step_conv_forward_group(const step_conv_item* items, int n, step_stream_t st
             // the pointwise member rides along when the 3x3x3 members leave CUs idle (fewer one-per-CU workgroups than CUs):
             // behind a launch that fills every CU its workgroups would only queue
             bool with_pw = false;
-            if (sel.pw >= 0 && pls[0].twl == 0 && base <= opt(STEP_OPT_CONV_GROUP_PW) && opt(STEP_OPT_THROUGHPUT) == 0) {
+            // (under the throughput profile only beside a narrow member: the pixel-split form halves that member's workgroups, and the pointwise
+            // workgroups fill the CUs it frees -- C2 with two batches in flight, variants interleaved, profiles/r07_ab_conv_group_narrow.txt)
+            bool any_narrow = false;
+            for (int k = 0; k < sel.ntap; ++k) any_narrow = any_narrow || narrow[k];
+            if (sel.pw >= 0 && pls[0].twl == 0 && base <= opt(STEP_OPT_CONV_GROUP_PW) && (opt(STEP_OPT_THROUGHPUT) == 0 || any_narrow)) {
                 step_conv_desc cpw;
                 with_pw = conv_group_pw_params(items[sel.pw], canon[0].dtype, cpw, g.pw, base);
                 if (!with_pw) { g.pw = g.p[0]; g.pw.gbase = 0; g.pw.gcount = 0; }
@@ -1269,17 +1311,25 @@ int step_conv_group_kernel_name(const step_conv_item* items, int n, char* buf, i
     }
     int NBc = 0;
     if (!conv_group_plan(taps, sel.ntap, canon, ps, pls, &NBc)) return STEP_OK;
+    bool narrow[CONV_GROUP_MAX], any_narrow = false;
+    conv_group_narrow_plan(taps, sel.ntap, canon, ps, pls, narrow);
     long long base = 0;
-    for (int k = 0; k < sel.ntap; ++k) base += (pls[k].mtiles * ceil_div(ps[k].nblk32, 2 * NBc) + 7) / 8 * 8;
+    for (int k = 0; k < sel.ntap; ++k) {
+        base += (pls[k].mtiles * (narrow[k] ? 1 : ceil_div(ps[k].nblk32, 2 * NBc)) + 7) / 8 * 8;
+        any_narrow = any_narrow || narrow[k];
+    }
     bool with_pw = false;
-    if (sel.pw >= 0 && pls[0].twl == 0 && base <= opt(STEP_OPT_CONV_GROUP_PW) && opt(STEP_OPT_THROUGHPUT) == 0) {
+    if (sel.pw >= 0 && pls[0].twl == 0 && base <= opt(STEP_OPT_CONV_GROUP_PW) && (opt(STEP_OPT_THROUGHPUT) == 0 || any_narrow)) {
         step_conv_desc cpw;
         ConvParams ppw;
         with_pw = conv_group_pw_params(items[sel.pw], canon[0].dtype, cpw, ppw, base);
     }
     const char* t = canon[0].dtype == STEP_BF16 ? "step::bf16_t" : "step::f16_t";
-    snprintf(buf, (size_t)buflen, "void step::conv_tap_group%s_kernel<%s, %d, %d, 3, 3, 3, 2, 2, 8, 1>(step::ConvGroupParams)", with_pw ? "_pw" : "", t,
-             pls[0].twl, NBc);
+    if (any_narrow)
+        snprintf(buf, (size_t)buflen, "void step::conv_tap_group%s_kernel_narrow<%s, %d>(step::ConvGroupParams)", with_pw ? "_pw" : "", t, NBc);
+    else
+        snprintf(buf, (size_t)buflen, "void step::conv_tap_group%s_kernel<%s, %d, %d, 3, 3, 3, 2, 2, 8, 1>(step::ConvGroupParams)", with_pw ? "_pw" : "", t,
+                 pls[0].twl, NBc);
     return STEP_OK;
 }
 

@@ -64,8 +64,10 @@ typedef short s16x8_pool __attribute__((ext_vector_type(8)));
 //   * the next tile's halo is REQUESTED before the current tile's epilogue (index tables + global loads, raw pixels of the fused pointwise
 //     input for PRE) and lands while the epilogue's conversions, LDS passes and stores run; the fragment registers of the K loop are dead there.
 // The accumulation order of every output is unchanged: bit-identical to the one-tile-per-workgroup launch.
-template <typename T, int TWL, int NB, int KD, int KH, int KW, int TPS, int MB, int WV, int PH = 0, bool GRP = false, bool PRE = false, bool POOL = false, bool PERSIST = false>
-__device__ __forceinline__ void conv_tap_body(const ConvParams& p) {
+// EXTB > 0: the LDS comes from the caller (`arena`, EXTB bytes, 16-byte aligned) instead of a static array of this function -- a kernel that
+// carries workgroups of several bodies declares ONE arena of the largest size (conv_tap_narrow.h; same pattern as conv_pw_body's EXT).
+template <typename T, int TWL, int NB, int KD, int KH, int KW, int TPS, int MB, int WV, int PH = 0, bool GRP = false, bool PRE = false, bool POOL = false, bool PERSIST = false, int EXTB = 0>
+__device__ __forceinline__ void conv_tap_body(const ConvParams& p, unsigned char* arena = nullptr) {
     static_assert(!PERSIST || (PH == 1 && !GRP && (NTAPS_EVEN_STEPS(KD, KH, KW, TPS))), "the persistent tile loop exists for the two-phase form with an even number of steps per slab");
     static_assert(!(PERSIST && POOL) || PRE, "persistent + pooled epilogue: the pooled tile lives in halo + stash (PRE)");
     static_assert(!POOL || (TWL == 3 && WV == 8 && PH == 1 && !GRP && sizeof(T) == 2 && KD == 3), "the pooled epilogue exists for the 4-plane 8x8 tile of the two-phase 16-bit form");
@@ -138,7 +140,14 @@ __device__ __forceinline__ void conv_tap_body(const ConvParams& p) {
     // covers halo + stash only and the rings (which already hold the NEXT tile's first step) survive it
     static_assert(!POOL || PERSIST || TPXM * (NBT * 64 + 16) <= NPIX_MAX * PITCH + BBYTES, "the pooled epilogue's tile lives in the halo / weight rings, below the scale table");
     static_assert(!POOL || !PERSIST || TPXM * (NBT * 64 + 16) <= NPIX_MAX * PITCH + STASH_BYTES, "persistent form: the pooled tile lives in halo + stash");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
+    static_assert(EXTB == 0 || EXTB >= LDS_BYTES, "the caller's arena holds this body");
+    unsigned char* lds;
+    if constexpr (EXTB != 0) {
+        lds = arena;
+    } else {
+        __shared__ __attribute__((aligned(16))) unsigned char own[LDS_BYTES];
+        lds = own;
+    }
     unsigned char* const ldsA = lds;
     unsigned char* const ldsB = lds + NPIX_MAX * PITCH + (PERSIST ? STASH_BYTES + SS_BYTES : 0);
     float* const ldsS = (float*)(lds + NPIX_MAX * PITCH + (PERSIST ? STASH_BYTES : BBYTES));
