@@ -217,6 +217,20 @@ STEP_API int step_detect_compact(const uint8_t* keep, const float* const* boxes,
                                  const int32_t* tube_start, int I, int B, int NC, int kmax, float width, float height, float* out_boxes,
                                  float* out_scores, long long* out_cls, long long* out_tube, int32_t* counts, step_stream_t stream);
 
+/* The cross-class merge behind the evaluation loop (demo.py:176-198), all G = I * B groups in ONE launch, on step_detect_compact's output as it
+ * lies: boxes [G, cap, 4] normalised fp32, counts [G].  The LIST is the group's rows in list order: position p is row order[g][p], p <
+ * sel_counts[g] (the order after the top-k cut), or row p, p < counts[g], when order and sel_counts are both NULL.  Walking the list, the
+ * first position without a cluster leads cluster k = 0, 1, ...; every LATER position without a cluster whose IoU with the LEADER's box
+ * (utils/tube_utils.py:269-308 compute_box_iou: no "+1", fp32, every operation rounded separately) is > global_thresh (strict, compared in
+ * fp32) joins it.  The cluster's box is np.mean of its members' boxes: a sequential fp32 sum in list order, then one division by the count.
+ *   cluster  [G, cap] int32: cluster number of every list position (-1 at positions past the list's end)
+ *   lead_pos [G, cap] int32: list position of cluster k's leader, k < n_clusters[g] (ascending)
+ *   merged   [G, cap, 4] fp32: cluster k's box, k < n_clusters[g]          n_clusters [G] int32
+ * cap <= 65536 (more: STEP_E_UNSUPPORTED).  Rows must hold no NaN and no empty box (union > 0), which step_detect_nms guarantees. */
+STEP_API int step_detect_merge(const float* boxes, const int32_t* counts, const int32_t* order, const int32_t* sel_counts, int G, int cap,
+                               float global_thresh, int32_t* cluster, int32_t* lead_pos, float* merged, int32_t* n_clusters,
+                               step_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused convolution unit on channels-last activations:
  *     y = act( conv(x, w) * scale[c] + shift[c] (+ residual) )

@@ -255,11 +255,163 @@ __global__ __launch_bounds__(256) void detect_compact_kernel(DetectCompactParams
     if (threadIdx.x == 0) p.counts[g] = base;
 }
 
+// detect_merge_kernel -- the cross-class merge of demo.py:176-198 on the rows of detect_compact_kernel, all (iteration, clip) groups in one
+// launch: one 256-thread workgroup per group.  List position p is row order[p] of the group's segment (identity without `order`).
+//   * the "not yet flagged" state of the reference's `flag` list is a bitmap in LDS, one 64-bit word per 64 consecutive list positions;
+//   * the serial loop runs once per CLUSTER: the next leader is the first set bit past the previous one (a ballot over 64 words, ctz), then
+//     the four waves take the later words round-robin -- lane = position -- test the set bits against the LEADER's box (compute_box_iou,
+//     tube_utils.py:269-308: no "+1", every operation rounded separately, strict `>` in fp32) and clear the joiners with ONE plain 64-bit
+//     store of the wave's ballot per word (a word belongs to one wave, so no atomics).  The search of the next round only reads bits past
+//     the leader, the join only clears bits past it too, so ONE barrier per cluster (after the join) is enough;
+//   * np.mean of a cluster's boxes is a sequential fp32 sum in list order and one division by the member count, so the sums are taken
+//     one lane per cluster, the lanes of a wave walking the list together (every read is a wave-wide broadcast) and adding only their own
+//     cluster's members, in order.
+// Serial depth: n_clusters rounds (a barrier, a broadcast LDS read of the leader and at most ceil(n / 256) IoU tests per lane each) plus
+// ceil(n_clusters / 256) walks of at most n positions -- NOT n barrier rounds (worst case n_clusters == n: no two rows overlap).  Rows past DM_LDS_ROWS are not a limit, only slower: their
+// boxes and cluster numbers are read back from global memory instead of LDS.  The bitmap is sized statically: cap <= 64 * DM_WORDS rows.
+#define DM_WORDS 1024
+#define DM_LDS_ROWS 2048
+struct DmBox { float x1, y1, x2, y2; };
+
+__device__ __forceinline__ bool merge_iou_gt(const DmBox& a, const DmBox& b, float thr) {
+    const float xmin = fmaxf(a.x1, b.x1), ymin = fmaxf(a.y1, b.y1);
+    const float xmax = fminf(a.x2, b.x2), ymax = fminf(a.y2, b.y2);
+    const float iw = fmaxf(__fsub_rn(xmax, xmin), 0.f), ih = fmaxf(__fsub_rn(ymax, ymin), 0.f);
+    const float inter = (iw > 0.f && ih > 0.f) ? __fmul_rn(iw, ih) : 0.f;
+    const float a1 = __fmul_rn(__fsub_rn(a.x2, a.x1), __fsub_rn(a.y2, a.y1));
+    const float a2 = __fmul_rn(__fsub_rn(b.x2, b.x1), __fsub_rn(b.y2, b.y1));
+    return __fdiv_rn(inter, __fsub_rn(__fadd_rn(a1, a2), inter)) > thr;
+}
+
+__global__ __launch_bounds__(256) void detect_merge_kernel(const float* __restrict__ boxes, const int32_t* __restrict__ counts,
+                                                           const int32_t* __restrict__ order, const int32_t* __restrict__ sel_counts, int cap,
+                                                           float thr, int32_t* cluster, int32_t* lead_pos, float* __restrict__ merged,
+                                                           int32_t* __restrict__ n_clusters) {
+    __shared__ unsigned long long avail[DM_WORDS];             // bit (p & 63) of word (p >> 6): position p has no cluster yet
+    __shared__ __attribute__((aligned(16))) float sbox[DM_LDS_ROWS * 4];                    // the boxes of the first positions, in list order
+    __shared__ int32_t scl[DM_LDS_ROWS];                       // their cluster numbers
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* B = boxes + (size_t)g * cap * 4;
+    const int32_t* ord = order ? order + (size_t)g * cap : nullptr;
+    int32_t* cl = cluster + (size_t)g * cap;
+    int32_t* lp = lead_pos + (size_t)g * cap;
+    const int n = min(max(sel_counts ? sel_counts[g] : counts[g], 0), cap);
+    const int nwords = (n + 63) >> 6;
+
+    auto row_box = [&](int p) {                                  // list position -> box, through `order` (clamped: a bad index must not leave the segment)
+        const int r = ord ? min(max(ord[p], 0), cap - 1) : p;
+        DmBox b = {B[4 * r], B[4 * r + 1], B[4 * r + 2], B[4 * r + 3]};
+        return b;
+    };
+    auto box_at = [&](int p) {
+        if (p < DM_LDS_ROWS) { DmBox b = {sbox[4 * p], sbox[4 * p + 1], sbox[4 * p + 2], sbox[4 * p + 3]}; return b; }
+        return row_box(p);
+    };
+
+    for (int p = tid; p < min(n, DM_LDS_ROWS); p += 256) {
+        const DmBox b = row_box(p);
+        sbox[4 * p] = b.x1; sbox[4 * p + 1] = b.y1; sbox[4 * p + 2] = b.x2; sbox[4 * p + 3] = b.y2;
+    }
+    for (int w = tid; w < nwords; w += 256) avail[w] = (64 * w + 64 <= n) ? ~0ull : ((1ull << (n - 64 * w)) - 1ull);
+    for (int p = n + tid; p < cap; p += 256) cl[p] = -1;
+    __syncthreads();
+
+    int K = 0;
+    for (int from = 0; from < n;) {
+        // next leader: the first set bit at or past `from` (every wave finds the same one)
+        int L = -1;
+        for (int wb = from >> 6; wb < nwords; wb += 64) {
+            const int w = wb + lane;
+            unsigned long long word = w < nwords ? avail[w] : 0ull;
+            if (w == (from >> 6)) word &= ~0ull << (from & 63);
+            const unsigned long long m = __ballot(word != 0ull);
+            if (m) {
+                const int src = __builtin_ctzll(m);
+                const unsigned long long found = __shfl(word, src);
+                L = 64 * (wb + src) + __builtin_ctzll(found);
+                break;
+            }
+        }
+        if (L < 0) break;
+        const DmBox lb = box_at(L);
+        const int wL = L >> 6;
+        for (int w = wL + wave; w < nwords; w += 4) {
+            const unsigned long long word = avail[w];
+            const unsigned long long later = w == wL ? (((L & 63) == 63) ? 0ull : (~0ull << ((L & 63) + 1))) : ~0ull;
+            if ((word & later) == 0ull) continue;                // wave-uniform
+            const int p = 64 * w + lane;
+            bool join = ((word & later) >> lane) & 1ull;
+            if (join) join = merge_iou_gt(lb, box_at(p), thr);
+            const unsigned long long m = __ballot(join);
+            if (m) {
+                if (lane == 0) avail[w] = word & ~m;
+                if (join) {
+                    cl[p] = K;
+                    if (p < DM_LDS_ROWS) scl[p] = K;
+                }
+            }
+        }
+        if (tid == 0) {
+            cl[L] = K; lp[K] = L;
+            if (L < DM_LDS_ROWS) scl[L] = K;
+        }
+        ++K;
+        from = L + 1;
+        __syncthreads();
+    }
+    if (tid == 0) n_clusters[g] = K;
+
+    // the means: lane = cluster, 64 consecutive clusters per wave and round; the walk starts at the first of their leaders
+    for (int k0 = 64 * wave; k0 < K; k0 += 256) {
+        const int k = k0 + lane;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int cnt = 0;
+        int p = lp[k0];
+        for (const int nl = min(n, DM_LDS_ROWS); p + 8 <= nl; p += 8) {      // eight positions' LDS reads in flight, the adds still in list order
+            int c[8];
+            DmBox b[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { c[u] = scl[p + u]; b[u] = box_at(p + u); }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (c[u] == k) {
+                    s0 = __fadd_rn(s0, b[u].x1); s1 = __fadd_rn(s1, b[u].y1); s2 = __fadd_rn(s2, b[u].x2); s3 = __fadd_rn(s3, b[u].y2);
+                    ++cnt;
+                }
+        }
+        for (; p < n; ++p) {
+            const int c = p < DM_LDS_ROWS ? scl[p] : cl[p];
+            const DmBox b = box_at(p);
+            if (c == k) {
+                s0 = __fadd_rn(s0, b.x1); s1 = __fadd_rn(s1, b.y1); s2 = __fadd_rn(s2, b.x2); s3 = __fadd_rn(s3, b.y2);
+                ++cnt;
+            }
+        }
+        if (k < K) {
+            float* o = merged + ((size_t)g * cap + k) * 4;
+            const float d = (float)cnt;
+            o[0] = __fdiv_rn(s0, d); o[1] = __fdiv_rn(s1, d); o[2] = __fdiv_rn(s2, d); o[3] = __fdiv_rn(s3, d);
+        }
+    }
+}
+
 }  // namespace step
 
 using namespace step;
 
 extern "C" {
+
+int step_detect_merge(const float* boxes, const int32_t* counts, const int32_t* order, const int32_t* sel_counts, int G, int cap,
+                      float global_thresh, int32_t* cluster, int32_t* lead_pos, float* merged, int32_t* n_clusters, step_stream_t stream) {
+    if (G < 0 || cap < 0) return STEP_E_SHAPE;
+    if (G == 0 || cap == 0) return STEP_OK;
+    if (cap > 64 * DM_WORDS) return STEP_E_UNSUPPORTED;
+    if (!boxes || !counts || !cluster || !lead_pos || !merged || !n_clusters) return STEP_E_NULL;
+    if ((order == nullptr) != (sel_counts == nullptr)) return STEP_E_NULL;
+    STEP_LAUNCH((detect_merge_kernel), dim3((unsigned)G), dim3(256), stream, boxes, counts, order, sel_counts, cap, global_thresh, cluster,
+                lead_pos, merged, n_clusters);
+    return STEP_LAUNCH_CHECK();
+}
 
 int step_detect_compact(const uint8_t* keep, const float* const* boxes, const float* const* scores, const long long* score_strides,
                         const int32_t* tube_start, int I, int B, int NC, int kmax, float width, float height, float* out_boxes,

@@ -22,7 +22,8 @@ from . import ops
 from .tube_math import extrapolate_tubes, decode_coef, valid_tubes
 
 TUBE_KERNEL = True             # per-step tube bookkeeping as one HIP launch (False: the tensor-op restatement below)
-COMPACT_KERNEL = True          # postprocess: the detection rows of all iterations and clips compacted by one HIP launch (False: nonzero / gather / bincount)
+COMPACT_KERNEL = True          # postprocess: the detection rows of all iterations and clips compacted by one HIP launch (False: nonzero / gather / bincount);
+                               # postprocess_merged always compacts with the launch: step_detect_merge reads its segments
 
 
 def _flat_tubes(tubes_list, device, dtype=torch.float32):
@@ -142,6 +143,31 @@ def _clip_groups(nums, device):
 _POST_CONST = {}
 
 
+def _detect_keep(nums, NC, dev, members, conf, thr, W, H):
+    """The fused mask + valid_tubes + NMS launch (ops.detect_nms) of every iteration in `members` (one clip layout `nums`, <= 64 tubes per
+    clip) -> keep [I,B,NC,kmax], the clamped boxes and the middle-frame scores per iteration, tube_start [B] int32, [W,H,W,H]."""
+    B, kmax, I = len(nums), max(nums), len(members)
+    # per-layout constants live on the device (a host -> device copy from pageable memory per call stalls the host; the layout of a
+    # serving loop never changes)
+    ck = (nums, dev, W, H)
+    hit = _POST_CONST.get(ck)
+    if hit is None:
+        n = torch.as_tensor(nums, device=dev, dtype=torch.int32)
+        hit = _POST_CONST[ck] = (n, (torch.cumsum(n, 0) - n).to(torch.int32), torch.tensor([W, H, W, H], device=dev))
+        if len(_POST_CONST) > 64:
+            _POST_CONST.pop(next(iter(_POST_CONST)))
+    n, start, whwh = hit
+    keep = torch.empty((I, B, NC, kmax), dtype=torch.uint8, device=dev)
+    sc_all, bx_all = [], []
+    for k, (oi, h) in enumerate(members):
+        prob, loc = h["pred_prob"], h["pred_loc"]
+        scores = prob[:, int(prob.shape[1] / 2)].float()                                          # [N,NC] middle frame (test.py:159)
+        _, boxes = ops.detect_nms(scores, loc[:, int(loc.shape[1] / 2)].float(), start, n, kmax, conf, thr, 400.0, 400.0, keep[k])
+        sc_all.append(scores)                                                                     # (valid_tubes' 400 x 400 default, as the reference calls it: test.py:161,191)
+        bx_all.append(boxes)
+    return keep, bx_all, sc_all, start, whwh
+
+
 def postprocess(args, history, conf_thresh=None, nms_thresh=None, evaluate_topk=None, topk=None, iterations=None):
     """The evaluation loop of test.py:157-210 (the same code is inlined in train.py:512-573 and demo.py:123-174) as batched
     tensor operations: for EVERY refinement iteration and every clip, per class: mask the middle-frame scores with
@@ -155,8 +181,6 @@ def postprocess(args, history, conf_thresh=None, nms_thresh=None, evaluate_topk=
     Thresholds default to args.conf_thresh / nms_thresh / evaluate_topk / topk (config.py:62-65).
     Returns a list over iterations of lists over clips of dicts {boxes [m,4] fp32 normalised, scores [m], labels [m] (class
     index), tubes [m] (index of the tube inside its clip)} in the order the reference writes its CSV rows."""
-    from . import ops
-
     conf = float(getattr(args, "conf_thresh", 0.01) if conf_thresh is None else conf_thresh)
     thr = float(getattr(args, "nms_thresh", 0.4) if nms_thresh is None else nms_thresh)
     etopk = int(getattr(args, "evaluate_topk", -1) if evaluate_topk is None else evaluate_topk)
@@ -181,24 +205,7 @@ def postprocess(args, history, conf_thresh=None, nms_thresh=None, evaluate_topk=
         groups.setdefault((tuple(nums), h["pred_prob"].shape[-1], h["pred_loc"].device), []).append((oi, h))
     for (nums, NC, dev), members in groups.items():
         B, kmax, I = len(nums), max(nums), len(members)
-        # per-layout constants live on the device (a host -> device copy from pageable memory per call stalls the host; the layout of a
-        # serving loop never changes)
-        ck = (nums, dev, W, H)
-        hit = _POST_CONST.get(ck)
-        if hit is None:
-            n = torch.as_tensor(nums, device=dev, dtype=torch.int32)
-            hit = _POST_CONST[ck] = (n, (torch.cumsum(n, 0) - n).to(torch.int32), torch.tensor([W, H, W, H], device=dev))
-            if len(_POST_CONST) > 64:
-                _POST_CONST.pop(next(iter(_POST_CONST)))
-        n, start, whwh = hit
-        keep = torch.empty((I, B, NC, kmax), dtype=torch.uint8, device=dev)
-        sc_all, bx_all = [], []
-        for k, (oi, h) in enumerate(members):
-            prob, loc = h["pred_prob"], h["pred_loc"]
-            scores = prob[:, int(prob.shape[1] / 2)].float()                                          # [N,NC] middle frame (test.py:159)
-            _, boxes = ops.detect_nms(scores, loc[:, int(loc.shape[1] / 2)].float(), start, n, kmax, conf, thr, 400.0, 400.0, keep[k])
-            sc_all.append(scores)                                                                     # (valid_tubes' 400 x 400 default, as the reference calls it: test.py:161,191)
-            bx_all.append(boxes)
+        keep, bx_all, sc_all, start, whwh = _detect_keep(nums, NC, dev, members, conf, thr, W, H)
         # rows in the reference's order: iteration, clip, class ascending, kept tube ascending == row-major order of `keep`
         if COMPACT_KERNEL and I <= 8:
             # one launch (step_detect_compact: a ballot prefix per (iteration, clip) into fixed-capacity segments) and one small copy of
@@ -230,8 +237,9 @@ def postprocess(args, history, conf_thresh=None, nms_thresh=None, evaluate_topk=
     return out
 
 
-def _postprocess_general(h, nums, conf, thr, etopk, topk, W, H):
-    """One iteration with tensor operations + step_nms_batched: more than 64 tubes per clip (anchor modes 3 / 4)."""
+def _general_rows(h, nums, conf, thr, W, H):
+    """The rows of one iteration on the general path, all clips in one flat list in the reference's order: (clip, class, box, score,
+    tube) per row."""
     from .roi_layers import nms_batched
     prob, loc = h["pred_prob"], h["pred_loc"]
     dev = loc.device
@@ -253,6 +261,13 @@ def _postprocess_general(h, nums, conf, thr, etopk, topk, W, H):
     rb = gb[kb, kc, kj] / torch.tensor([W, H, W, H], device=dev)                                      # :197-198
     rs = gs[kb, kc, kj]
     rt = order[kb, kc, kj]
+    return kb, kc, rb, rs, rt
+
+
+def _postprocess_general(h, nums, conf, thr, etopk, topk, W, H):
+    """One iteration with tensor operations + step_nms_batched: more than 64 tubes per clip (anchor modes 3 / 4)."""
+    B = len(nums)
+    kb, kc, rb, rs, rt = _general_rows(h, nums, conf, thr, W, H)
     per_clip = torch.bincount(kb, minlength=B).tolist()
     clips = []
     for bx, sc, cl, tb in zip(rb.split(per_clip), rs.split(per_clip), kc.split(per_clip), rt.split(per_clip)):
@@ -273,6 +288,112 @@ def detections_csv(dets, infos, label_dict=None):
             lab = int(cl[k]) + 1 if label_dict is None else label_dict[int(cl[k])]
             lines.append("{0},{1:04},{2:.4},{3:.4},{4:.4},{5:.4},{6},{7:.4}\n".format(
                 info["video_name"], info["fid"], bx[k, 0], bx[k, 1], bx[k, 2], bx[k, 3], lab, sc[k]))
+    return lines
+
+
+def _merge_segments(seg_boxes, seg_scores, seg_cls, seg_tube, cnt, gthr, etopk, topk):
+    """The tail of postprocess_merged for G groups at once: seg_* [G,cap(,4)] fixed-capacity row segments in the reference's row order with
+    cnt [G] int32 rows each (on the device) -> one dict per group.  The top-k list order, the merge (ONE step_detect_merge launch) and the
+    cluster-major output order are batched tensor operations on the device-side counts; the ONE host copy fetches rows, selected rows
+    and clusters per group together, behind the launch."""
+    G, cap = seg_scores.shape
+    dev = seg_scores.device
+    pos = torch.arange(cap, device=dev).view(1, cap)
+    order = sel = None
+    if etopk > 0:                                                                                     # demo.py:171-174
+        # list.sort(key=score) is stable and ascending, then reversed: descending with ties in REVERSED row order == a stable descending
+        # sort of the flipped segment; rows past the count sort last
+        key = torch.where(pos < cnt.view(G, 1), seg_scores, torch.full_like(seg_scores, float("-inf")))
+        order = (cap - 1) - torch.argsort(torch.flip(key, dims=(1,)), dim=1, descending=True, stable=True)
+        sel = (cnt.clamp(max=topk) if topk >= 0 else (cnt + topk).clamp(min=0)).to(torch.int32)      # what `[:topk]` keeps
+        order32 = order.to(torch.int32)
+    cluster, lead_pos, merged, ncl = ops.detect_merge(seg_boxes, cnt, gthr, order32 if order is not None else None, sel)
+    # the reference writes cluster after cluster, members in list order (demo.py:210-217): a stable sort of the list positions by cluster
+    cl64 = cluster.long()
+    perm = torch.argsort(torch.where(cl64 >= 0, cl64, torch.full_like(cl64, cap)), dim=1, stable=True)
+    row = perm if order is None else torch.gather(order, 1, perm)
+    o_cluster = torch.gather(cl64, 1, perm)
+    o_scores, o_cls, o_tube = torch.gather(seg_scores, 1, row), torch.gather(seg_cls, 1, row), torch.gather(seg_tube, 1, row)
+    stats = torch.stack([cnt if sel is None else sel, ncl]).tolist()                                  # the one host sync
+    return [{"boxes": merged[g, :stats[1][g]], "cluster": o_cluster[g, :stats[0][g]], "labels": o_cls[g, :stats[0][g]],
+             "scores": o_scores[g, :stats[0][g]], "tubes": o_tube[g, :stats[0][g]]} for g in range(G)]
+
+
+def postprocess_merged(args, history, conf_thresh=None, nms_thresh=None, global_thresh=0.8, evaluate_topk=None, topk=None, iterations=None):
+    """postprocess() followed by the cross-class merge of demo.py:176-198, which turns a clip's per-class rows into one box per person with
+    its list of (action, score): walking the rows in list order (postprocess()'s order), the first row without a cluster leads one, and
+    every later row without a cluster whose IoU with the LEADER's box (compute_box_iou on the normalised fp32 boxes) is > global_thresh
+    joins it; the cluster's box is the mean of its members' boxes (np.mean: summed in list order).  demo.py:54-55 sets conf_thresh = 0.4
+    and global_thresh = 0.8 as locals; here conf_thresh defaults to args.conf_thresh like postprocess().
+
+    Same launches as postprocess() for the mask, NMS and row compaction; then the list order after top-k for all groups as batched tensor
+    operations, ONE step_detect_merge launch per set of iterations that share a clip layout, and ONE host synchronisation behind it (rows,
+    selected rows and clusters per group in one copy) on the <= 64 tubes path; the general path keeps the synchronisation of its nonzero.
+
+    Returns a list over iterations of lists over clips of dicts {boxes [K,4] fp32 normalised merged boxes in cluster order, cluster [m]
+    (index into boxes), labels [m], scores [m], tubes [m]}, rows in the order the reference writes them: cluster after cluster, members in
+    list order.  Where two clusters of a clip have the same merged box, the reference's dict (keyed by the box's text) keeps only the later
+    one; this returns both."""
+    conf = float(getattr(args, "conf_thresh", 0.01) if conf_thresh is None else conf_thresh)
+    thr = float(getattr(args, "nms_thresh", 0.4) if nms_thresh is None else nms_thresh)
+    etopk = int(getattr(args, "evaluate_topk", -1) if evaluate_topk is None else evaluate_topk)
+    topk = int(getattr(args, "topk", -1) if topk is None else topk)
+    gthr = float(global_thresh)
+    W, H = float(args.image_size[0]), float(args.image_size[1])
+    todo = [(it, h) for it, h in enumerate(history) if iterations is None or it in iterations]
+    out = [None] * len(todo)
+    groups = {}
+    for oi, (it, h) in enumerate(todo):
+        nums = [int(v) for v in h["tubes_nums"]]
+        if len(nums) == 0 or sum(nums) == 0:
+            e = torch.zeros(0, device=h["pred_loc"].device)
+            out[oi] = [{"boxes": e.view(0, 4), "cluster": e.long(), "labels": e.long(), "scores": e, "tubes": e.long()} for _ in nums]
+        else:
+            groups.setdefault((tuple(nums), h["pred_prob"].shape[-1], h["pred_loc"].device), []).append((oi, h))
+    for (nums, NC, dev), members in groups.items():
+        B, kmax = len(nums), max(nums)
+        cap = NC * kmax
+        if kmax <= 64:
+            for m0 in range(0, len(members), 8):                                                      # (STEP_DETECT_ITERS_MAX iterations per launch)
+                part = members[m0:m0 + 8]
+                keep, bx_all, sc_all, start, _ = _detect_keep(nums, NC, dev, part, conf, thr, W, H)
+                rb, rs, kc, kj, cnt = ops.detect_compact(keep, bx_all, sc_all, start, W, H)
+                G = len(part) * B
+                res = _merge_segments(rb.view(G, cap, 4), rs.view(G, cap), kc.view(G, cap), kj.view(G, cap), cnt, gthr, etopk, topk)
+                for k, (oi, h) in enumerate(part):
+                    out[oi] = res[k * B:(k + 1) * B]
+        else:
+            # the general path's rows come as one flat list per iteration: scatter them into the same fixed-capacity segments
+            I = len(members)
+            seg_b = torch.zeros((I * B, cap, 4), dtype=torch.float32, device=dev)
+            seg_s = torch.zeros((I * B, cap), dtype=torch.float32, device=dev)
+            seg_c = torch.zeros((I * B, cap), dtype=torch.int64, device=dev)
+            seg_t = torch.zeros((I * B, cap), dtype=torch.int64, device=dev)
+            cnts = []
+            for k, (oi, h) in enumerate(members):
+                kb, kc, rb, rs, rt = _general_rows(h, list(nums), conf, thr, W, H)
+                per = torch.bincount(kb, minlength=B)
+                at = torch.arange(kb.shape[0], device=dev) - (torch.cumsum(per, 0) - per)[kb]         # row number inside its clip
+                g = kb + k * B
+                seg_b[g, at], seg_s[g, at], seg_c[g, at], seg_t[g, at] = rb, rs, kc, rt
+                cnts.append(per)
+            res = _merge_segments(seg_b, seg_s, seg_c, seg_t, torch.cat(cnts).to(torch.int32), gthr, etopk, topk)
+            for k, (oi, h) in enumerate(members):
+                out[oi] = res[k * B:(k + 1) * B]
+    return out
+
+
+def merged_csv(dets, infos, label_dict=None):
+    """The text demo.py:210-217 writes for one batch: `dets` = one entry of postprocess_merged()'s result, infos = per clip {'video_name',
+    'fid'}; per cluster, one line per member with the MERGED box; label_dict maps class index -> label id (identity + 1 when None)."""
+    lines = []
+    for d, info in zip(dets, infos):
+        bx, k_, sc, cl = d["boxes"].cpu().numpy(), d["cluster"].cpu().numpy(), d["scores"].cpu().numpy(), d["labels"].cpu().numpy()
+        for k in range(len(sc)):
+            lab = int(cl[k]) + 1 if label_dict is None else label_dict[int(cl[k])]
+            b = bx[k_[k]]
+            lines.append("{0},{1:04},{2:.4},{3:.4},{4:.4},{5:.4},{6},{7:.4}\n".format(
+                info["video_name"], info["fid"], b[0], b[1], b[2], b[3], lab, sc[k]))
     return lines
 
 

@@ -1059,6 +1059,30 @@ def detect_compact(keep, boxes, scores, tube_start, width, height):
     return ob, os_, oc, ot, counts
 
 
+def detect_merge(boxes, counts, global_thresh, order=None, sel_counts=None):
+    """step_detect_merge (demo.py:176-198): boxes [G,cap,4] fp32 normalised (step_detect_compact's segments), counts [G] int32, optionally
+    the list order [G,cap] int32 with sel_counts [G] int32 (both or neither) -> (cluster [G,cap] int32: cluster number of every list
+    position, -1 past the list's end; lead_pos [G,cap] int32: list position of cluster k's leader; merged [G,cap,4] fp32: cluster k's
+    mean box; n_clusters [G] int32), the last three valid for k < n_clusters[g]."""
+    L = _lib.lib()
+    if (order is None) != (sel_counts is None):
+        raise ValueError("detect_merge: order and sel_counts go together")
+    G, cap = boxes.shape[0], boxes.shape[1]
+    dev = boxes.device
+    i32 = lambda t: None if t is None else (t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous())
+    if boxes.dtype != torch.float32 or not boxes.is_contiguous():
+        boxes = boxes.float().contiguous()
+    counts, order, sel_counts = i32(counts), i32(order), i32(sel_counts)
+    cluster = torch.empty((G, cap), dtype=torch.int32, device=dev)
+    lead_pos = torch.empty((G, cap), dtype=torch.int32, device=dev)
+    merged = torch.empty((G, cap, 4), dtype=torch.float32, device=dev)
+    n_clusters = torch.empty((G,), dtype=torch.int32, device=dev) if G * cap else torch.zeros((G,), dtype=torch.int32, device=dev)
+    _capi.check(L.step_detect_merge(_lib.dptr(boxes), _lib.dptr(counts), _lib.dptr(order), _lib.dptr(sel_counts), G, cap, float(global_thresh),
+                                    _lib.dptr(cluster), _lib.dptr(lead_pos), _lib.dptr(merged), _lib.dptr(n_clusters), _lib.stream_ptr(dev)),
+                "step_detect_merge")
+    return cluster, lead_pos, merged, n_clusters
+
+
 def select_prepare(prob, loc, first, last, clip_of, gt_mid, gt_count, width, height):
     """step_select_prepare: prob [N,T,NC], loc [N,T,4], first / last [N,Tw,4] | None, clip_of [N] int32, gt_mid [B,Gmax,4], gt_count [B]
     int32 (one device) -> (mean_prob [N,NC], vloc [N,T,4], vfirst, vlast ([N,Tw,4] | None), iou [N,Gmax]), fp32 on that device."""
