@@ -231,6 +231,42 @@ STEP_API int step_detect_merge(const float* boxes, const int32_t* counts, const 
                                float global_thresh, int32_t* cluster, int32_t* lead_pos, float* merged, int32_t* n_clusters,
                                step_stream_t stream);
 
+/* ---- frame-mAP evaluation: what utils/eval_utils.py:12-23 ava_evaluation computes (external/ActivityNet/Evaluation, the
+ * PascalDetectionEvaluator at IoU 0.5 behind test.py:225, train.py:580, train_cls.py:551).  All float64, every operation rounded on its own.
+ *
+ * step_round_sig4: out[i] = float("{:.4}".format(in[i])) for n fp32 values, bit for bit: the four-significant-digit text of test.py:213
+ * parsed back, without the text.  0 -> 0.  |v| outside [1e-9, 1e4), inf and NaN (none occurs in normalised boxes and scores) give NaN and
+ * set *status (device int32) to 1; the call never clears the word: the caller zeroes it, reads it and raises. */
+STEP_API int step_round_sig4(const float* in, long long n, double* out, int32_t* status, step_stream_t stream);
+
+/* step_eval_match: true / false positive of every detection row, all NI images in ONE launch (ava/per_image_evaluation.py).
+ *   det_boxes [R,4] f64 (x1,y1,x2,y2), det_cls [R] int32, det_start [NI+1] int64: image k owns rows det_start[k] .. det_start[k+1], ALREADY
+ *   in labelling order -- descending score, among equal scores the LATER row of the input first (a stable ascending sort, reversed) -- so a
+ *   row's position inside its image is its rank;
+ *   gt_boxes [M,4] f64, gt_cls [M] int32, gt_start [NI+1] int64, input order kept (the "first maximum" below is taken in it); boxes of
+ *   positive area (then no union is 0); gt_max = the largest number of ground-truth rows of one image (the caller holds the ground truth on
+ *   the host), <= 1024, more: STEP_E_UNSUPPORTED.  The limit also holds on the device: should gt_start give an image more than 1024 rows
+ *   although gt_max said otherwise, that image is not matched against a truncated list -- all its rows get label 255 and match -2;
+ *   label [R] uint8: 2 = removed, not (y1 < y2 and x1 < x2); else the row looks only at the FIRST ground-truth box of its class with the
+ *   largest IoU (inter / (area1 + area2 - inter), no "+1"): 1 = that IoU >= thresh and no row of lower rank claimed the box, 0 otherwise
+ *   (no fall-back to a second-best box; no box of the class: 0);
+ *   match [R] int32: index of that box inside the image's ground-truth rows, -1 without one or for a removed row.
+ * A class id matches only equal ids, so rows of a class outside the label map can be passed with class -1. */
+STEP_API int step_eval_match(const double* det_boxes, const int32_t* det_cls, const long long* det_start, const double* gt_boxes,
+                             const int32_t* gt_cls, const long long* gt_start, int NI, long long R, long long M, int gt_max, double thresh,
+                             uint8_t* label, int32_t* match, step_stream_t stream);
+
+/* step_eval_ap: per class precision, recall and average precision (ava/metrics.py:22-119), all NC classes in ONE launch.
+ *   cls_start [NC+1] int64: class c owns positions cls_start[c] .. cls_start[c+1] of label [R] uint8 (0 false / 1 true positive), its rows
+ *   of all images in descending score order; num_gt [NC] int64: its ground-truth rows;
+ *   precision, recall [R] f64: ctp / (i + 1) and ctp / num_gt at position i of the class (ctp = true positives up to and including i);
+ *   ap [NC] f64: the sum over the true positives of (recall[i] - recall before it) * max(precision[i..]); NaN where num_gt == 0 (precision
+ *   and recall too), 0 for an empty list.  The sum has a fixed order (thread t of 256 adds positions t, t + 256, ... from the last to the
+ *   first, then a binary tree over the 256 partial sums, stride 128 .. 1): bit-reproducible from run to run; against a sum in another
+ *   order it differs by at most K * 2^-53 for K true positives. */
+STEP_API int step_eval_ap(const long long* cls_start, const uint8_t* label, const long long* num_gt, int NC, long long R, double* precision,
+                          double* recall, double* ap, step_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused convolution unit on channels-last activations:
  *     y = act( conv(x, w) * scale[c] + shift[c] (+ residual) )

@@ -5,6 +5,8 @@ from .backbone import BaseNet, I3D, I3D_head, build_base_i3d, weights_init  # no
 from .heads import ContextNet, ROINet, TwoBranchNet  # noqa: F401
 from . import dist  # noqa: F401
 from .optim import FlatAdam, FlatSGD, LossScaler  # noqa: F401
+from . import evaluate  # noqa: F401
+from .evaluate import FrameMAP, ava_evaluation  # noqa: F401
 
-__all__ = ["BaseNet", "ROINet", "TwoBranchNet", "ContextNet", "I3D", "I3D_head"]
+__all__ = ["BaseNet", "ROINet", "TwoBranchNet", "ContextNet", "I3D", "I3D_head", "FrameMAP", "ava_evaluation"]
 __version__ = "0.1.0"

@@ -5,7 +5,7 @@ import ctypes as C
 F32, BF16, F16 = 0, 1, 2
 NCHW, NHWC = 0, 1
 ROI_BWD_GATHER, ROI_BWD_ATOMIC = 0, 1
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 vp, fp, ip, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # raw device addresses
 i, f, ll, sz = C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -58,6 +58,9 @@ SIGNATURES = {
     "step_nms_batched_f64": (i, [fp, fp, ip, i, i, f, u8p, vp, vp]),
     "step_detect_compact": (i, [u8p, vp, vp, vp, ip, i, i, i, i, f, f, fp, fp, vp, vp, ip, vp]),
     "step_detect_merge": (i, [fp, ip, ip, ip, i, i, f, ip, ip, fp, ip, vp]),
+    "step_round_sig4": (i, [fp, ll, fp, ip, vp]),
+    "step_eval_match": (i, [fp, ip, vp, fp, ip, vp, i, ll, ll, i, C.c_double, u8p, ip, vp]),
+    "step_eval_ap": (i, [vp, u8p, vp, i, ll, fp, fp, fp, vp]),
     "step_detect_nms": (i, [fp, ll, i, fp, ll, ip, ip, i, i, f, f, f, f, u8p, fp, vp]),
     "step_conv_packed_elems": (sz, [i, i, i, i, i]),
     "step_conv_pack_weight": (i, [fp, i, i, i, i, i, i, ip, vp, vp]),

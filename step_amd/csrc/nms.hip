@@ -13,6 +13,9 @@
 // Arithmetic: "+1" areas, IoU = inter / (area_i + area_j - inter) with every operation rounded
 // separately (__f*_rn: no FMA contraction), suppress when IoU >= threshold (nms_cpu.cpp:84 -- the
 // CUDA op uses '>', nms.cu:84; parity target is the CPU op), ties in score broken by lower index.
+//
+// Behind it in this file: the rows of the evaluation loop (detect_compact), their cross-class merge (detect_merge) and the frame-mAP
+// evaluation of those rows (round_sig4, eval_match, eval_ap: external/ActivityNet/Evaluation restated in float64).
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -395,11 +398,220 @@ __global__ __launch_bounds__(256) void detect_merge_kernel(const float* __restri
     }
 }
 
+// ---- frame-mAP evaluation (external/ActivityNet/Evaluation: PascalDetectionEvaluator behind utils/eval_utils.py:12-23) ------------------
+// Everything here is float64, every operation rounded on its own (fp contraction is off in this file; the divisions are IEEE).
+
+// round_sig4_kernel -- out[i] = float("{:.4}".format(in[i])): the fp32 value rounded to FOUR SIGNIFICANT decimal digits and parsed back,
+// which is what the text of test.py:213 does to every box coordinate and score before the evaluator sees it.  |v| is exact in fp64; p is
+// the smallest exponent with |v| * 10^p >= 1000 (the products are exact for p <= 12: a 24-bit mantissa times 5^p < 2^28 fits 53 bits, so
+// the decade is found by exact comparisons, no log10); n = rint(|v| * 10^p) is the half-to-even rounding of the exact binary value that
+// Python's formatting does; n / 10^p is ONE correctly rounded division of two exact doubles = the correctly rounded parse of the decimal.
+// 0 -> 0 (sign kept).  |v| outside [1e-9, 1e4), inf, NaN: out = NaN and *status = 1 (a plain vector store of the same value from every
+// such lane; the caller clears the word and raises when it finds it set).
+__device__ const double k_pow10[13] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12};
+
+__global__ __launch_bounds__(256) void round_sig4_kernel(const float* __restrict__ in, long long n, double* __restrict__ out,
+                                                         int32_t* __restrict__ status) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double v = (double)in[i];
+    const double a = fabs(v);
+    if (a == 0.0) { out[i] = v; return; }
+    double r = __builtin_nan("");
+    if (a < 1e4) {                                             // (false for NaN and inf as well)
+        int p = 0;
+        double prod = a;
+        while (prod < 1000.0 && p < 12) { ++p; prod = a * k_pow10[p]; }
+        if (prod >= 1000.0) {
+            double m = rint(prod);                            // 1000 .. 10000, half to even
+            if (m == 10000.0) { m = 1000.0; --p; }
+            r = p < 0 ? 10000.0 : m / k_pow10[p];
+            if (v < 0.0) r = -r;
+        }
+    }
+    out[i] = r;
+    if (r != r) *status = 1;
+}
+
+// eval_match_kernel -- the per-image labelling (ava/per_image_evaluation.py:53-122, 388-487, 535-567), one 256-thread workgroup per IMAGE.
+// The image's ground-truth rows (box, class, one claim word) sit in LDS; lanes = detection rows, in chunks of 256; a row's position in its
+// image is its rank in labelling order (the caller sorted).  Pass 1: a lane walks the ground-truth rows of its class in order and keeps the
+// FIRST maximum of the IoU (np.argmax; ava/np_box_ops.py:25-78) -- strict `>` -- and, where that IoU >= thresh, does
+// atomicMin(&claim[gt], rank) in LDS.  One barrier.  Pass 2: true positive <=> the row's IoU passed and it holds the claim.  The reference's
+// serial "walk in score order, first come first served" is exactly "lowest rank among the claimants", so there is no loop over detections.
+// A row whose argmax box is taken does NOT fall back to its second-best box (neither does the reference).
+// An image with more ground-truth rows than LDS holds (the host refuses them by gt_max; this is for a gt_max that understated gt_start):
+// label 255 and match -2 on all its rows, uniformly for the workgroup, before any barrier.
+#define EM_GT_MAX 1024
+__global__ __launch_bounds__(256) void eval_match_kernel(const double* __restrict__ det_boxes, const int32_t* __restrict__ det_cls,
+                                                         const long long* __restrict__ det_start, const double* __restrict__ gt_boxes,
+                                                         const int32_t* __restrict__ gt_cls, const long long* __restrict__ gt_start,
+                                                         double thresh, uint8_t* __restrict__ label, int32_t* __restrict__ match) {
+    __shared__ double gbox[EM_GT_MAX * 4];
+    __shared__ int32_t gcls[EM_GT_MAX];
+    __shared__ int claim[EM_GT_MAX];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const long long d0 = det_start[k], g0 = gt_start[k];
+    const long long nd = det_start[k + 1] - d0;
+    const long long mg = gt_start[k + 1] - g0;
+    if (mg > EM_GT_MAX) {                                      // the caller's gt_max was wrong: no truncated match, the image's rows say so
+        for (long long r = tid; r < nd; r += 256) { label[d0 + r] = 255; match[d0 + r] = -2; }
+        return;
+    }
+    const int m = (int)(mg < 0 ? 0 : mg);
+    for (int j = tid; j < m; j += 256) {
+        const double* b = gt_boxes + (g0 + j) * 4;
+        gbox[4 * j] = b[0]; gbox[4 * j + 1] = b[1]; gbox[4 * j + 2] = b[2]; gbox[4 * j + 3] = b[3];
+        gcls[j] = gt_cls[g0 + j];
+        claim[j] = 0x7fffffff;
+    }
+    __syncthreads();
+    for (long long r = tid; r < nd; r += 256) {
+        const double* b = det_boxes + (d0 + r) * 4;
+        const double x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
+        const int c = det_cls[d0 + r];
+        if (!(y1 < y2 && x1 < x2)) {                           // per_image_evaluation.py:558-559 (a NaN coordinate fails it too)
+            label[d0 + r] = 2; match[d0 + r] = -1;
+            continue;
+        }
+        const double area1 = (y2 - y1) * (x2 - x1);
+        int best = -1;
+        double best_iou = -1.0;
+        for (int j = 0; j < m; ++j) {
+            if (gcls[j] != c) continue;
+            const double gx1 = gbox[4 * j], gy1 = gbox[4 * j + 1], gx2 = gbox[4 * j + 2], gy2 = gbox[4 * j + 3];
+            const double ih = fmax(0.0, fmin(y2, gy2) - fmax(y1, gy1));
+            const double iw = fmax(0.0, fmin(x2, gx2) - fmax(x1, gx1));
+            const double inter = ih * iw;
+            const double area2 = (gy2 - gy1) * (gx2 - gx1);
+            const double iou = inter / ((area1 + area2) - inter);
+            if (iou > best_iou) { best_iou = iou; best = j; }
+        }
+        const bool ok = best >= 0 && best_iou >= thresh;
+        if (ok) atomicMin(&claim[best], (int)r);
+        match[d0 + r] = best;
+        label[d0 + r] = ok ? 1 : 0;                            // (provisional: read back by this same lane behind the barrier)
+    }
+    __syncthreads();
+    for (long long r = tid; r < nd; r += 256)
+        if (label[d0 + r] == 1) label[d0 + r] = claim[match[d0 + r]] == (int)r ? 1 : 0;
+}
+
+// eval_ap_kernel -- precision, recall and average precision of one class (ava/metrics.py:22-119) on its score-descending list of labels
+// (0 false / 1 true positive), one 256-thread workgroup per CLASS, the list in chunks of 256:
+//   forward : ctp(i) = true positives among positions 0..i (ballot prefix in the chunk + a carried count); precision = ctp / (i + 1),
+//             recall = ctp / num_gt, two rounded divisions of exact integers, as the reference's;
+//   backward: chunks from the last to the first; ctp again (the carried count runs down), the precision made non-increasing from the right
+//             as a suffix maximum in the chunk (shuffles in the wave, four wave maxima in LDS) + a carried maximum of the later chunks;
+//             at a true positive the term (recall[i] - recall of ctp - 1) * envelope[i] -- recall changes exactly at the true positives.
+// ORDER OF THE SUM (fixed, no float atomics, bit-reproducible from run to run): thread t adds its own terms -- positions t, t + 256, ... --
+// starting from 0.0 in DESCENDING position order; the 256 partial sums are then added by a binary tree in LDS: stride 128, 64, ... 1,
+// s[t] = s[t] + s[t + stride].  num_gt == 0: AP, precision and recall are NaN.  An empty list with ground truth: AP 0.
+__global__ __launch_bounds__(256) void eval_ap_kernel(const long long* __restrict__ cls_start, const uint8_t* __restrict__ label,
+                                                      const long long* __restrict__ num_gt, double* __restrict__ precision,
+                                                      double* __restrict__ recall, double* __restrict__ ap) {
+    __shared__ int wsum[4];
+    __shared__ double wmax[4];
+    __shared__ double part[256];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long s0 = cls_start[c];
+    const long long n = cls_start[c + 1] - s0;
+    const long long ng = num_gt[c];
+    if (ng <= 0) {
+        const double nan = __builtin_nan("");
+        for (long long i = tid; i < n; i += 256) { precision[s0 + i] = nan; recall[s0 + i] = nan; }
+        if (tid == 0) ap[c] = nan;
+        return;
+    }
+    const double dng = (double)ng;
+    const long long chunks = (n + 255) / 256;
+    long long carry = 0;
+    for (long long ch = 0; ch < chunks; ++ch) {
+        const long long i = ch * 256 + tid;
+        const bool tp = i < n && label[s0 + i] == 1;
+        const unsigned long long mk = __ballot(tp);
+        if (lane == 0) wsum[wave] = __builtin_popcountll(mk);
+        __syncthreads();
+        long long ctp = carry + __builtin_popcountll(mk & ((2ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) ctp += wsum[w];
+        if (i < n) {
+            precision[s0 + i] = (double)ctp / (double)(i + 1);
+            recall[s0 + i] = (double)ctp / dng;
+        }
+        carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    double env_later = 0.0, sum = 0.0;                         // (the reference appends a precision of 0 behind the list)
+    for (long long ch = chunks - 1; ch >= 0; --ch) {
+        const long long i = ch * 256 + tid;
+        const bool tp = i < n && label[s0 + i] == 1;
+        const unsigned long long mk = __ballot(tp);
+        if (lane == 0) wsum[wave] = __builtin_popcountll(mk);
+        __syncthreads();
+        const long long base = carry - (wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+        long long ctp = base + __builtin_popcountll(mk & ((2ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) ctp += wsum[w];
+        double e = i < n ? (double)ctp / (double)(i + 1) : 0.0;
+        for (int d = 1; d < 64; d <<= 1) {                     // suffix maximum inside the wave
+            const double o = __shfl_down(e, d);
+            if (lane + d < 64) e = fmax(e, o);
+        }
+        if (lane == 0) wmax[wave] = e;
+        __syncthreads();
+        double env = fmax(e, env_later);
+        for (int w = wave + 1; w < 4; ++w) env = fmax(env, wmax[w]);
+        if (tp) sum = sum + ((double)ctp / dng - (double)(ctp - 1) / dng) * env;
+        env_later = fmax(env_later, fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3])));
+        carry = base;
+        __syncthreads();
+    }
+    part[tid] = sum;
+    __syncthreads();
+    for (int st = 128; st >= 1; st >>= 1) {
+        if (tid < st) part[tid] = part[tid] + part[tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) ap[c] = part[0];
+}
+
 }  // namespace step
 
 using namespace step;
 
 extern "C" {
+
+int step_round_sig4(const float* in, long long n, double* out, int32_t* status, step_stream_t stream) {
+    if (n < 0 || n > 0x7fffffffLL * 256) return STEP_E_SHAPE;
+    if (n == 0) return STEP_OK;
+    if (!in || !out || !status) return STEP_E_NULL;
+    STEP_LAUNCH((round_sig4_kernel), dim3((unsigned)((n + 255) / 256)), dim3(256), stream, in, n, out, status);
+    return STEP_LAUNCH_CHECK();
+}
+
+int step_eval_match(const double* det_boxes, const int32_t* det_cls, const long long* det_start, const double* gt_boxes,
+                    const int32_t* gt_cls, const long long* gt_start, int NI, long long R, long long M, int gt_max, double thresh,
+                    uint8_t* label, int32_t* match, step_stream_t stream) {
+    if (NI < 0 || R < 0 || M < 0 || gt_max < 0 || gt_max > M) return STEP_E_SHAPE;
+    if (gt_max > EM_GT_MAX) return STEP_E_UNSUPPORTED;
+    if (NI == 0) return STEP_OK;
+    if (!det_start || !gt_start) return STEP_E_NULL;
+    if (R > 0 && (!det_boxes || !det_cls || !label || !match)) return STEP_E_NULL;
+    if (M > 0 && (!gt_boxes || !gt_cls)) return STEP_E_NULL;
+    if (R == 0) return STEP_OK;
+    STEP_LAUNCH((eval_match_kernel), dim3((unsigned)NI), dim3(256), stream, det_boxes, det_cls, det_start, gt_boxes, gt_cls, gt_start, thresh,
+                label, match);
+    return STEP_LAUNCH_CHECK();
+}
+
+int step_eval_ap(const long long* cls_start, const uint8_t* label, const long long* num_gt, int NC, long long R, double* precision,
+                 double* recall, double* ap, step_stream_t stream) {
+    if (NC < 0 || R < 0) return STEP_E_SHAPE;
+    if (NC == 0) return STEP_OK;
+    if (!cls_start || !num_gt || !ap) return STEP_E_NULL;
+    if (R > 0 && (!label || !precision || !recall)) return STEP_E_NULL;
+    STEP_LAUNCH((eval_ap_kernel), dim3((unsigned)NC), dim3(256), stream, cls_start, label, num_gt, precision, recall, ap);
+    return STEP_LAUNCH_CHECK();
+}
 
 int step_detect_merge(const float* boxes, const int32_t* counts, const int32_t* order, const int32_t* sel_counts, int G, int cap,
                       float global_thresh, int32_t* cluster, int32_t* lead_pos, float* merged, int32_t* n_clusters, step_stream_t stream) {

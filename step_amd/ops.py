@@ -1083,6 +1083,62 @@ def detect_merge(boxes, counts, global_thresh, order=None, sel_counts=None):
     return cluster, lead_pos, merged, n_clusters
 
 
+def round_sig4(x, status):
+    """step_round_sig4: x fp32 (any shape) -> float64 tensor of that shape with float("{:.4}".format(v)) of every value, bit for bit (the
+    four-significant-digit text of test.py:213 parsed back).  status: an int32 tensor of one element on x's device that the launch sets to
+    1 where a value is outside [1e-9, 1e4) in magnitude, inf or NaN (its result is NaN); the caller clears and reads it."""
+    L = _lib.lib()
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.float().contiguous()
+    if status.dtype != torch.int32 or status.numel() != 1 or status.device != x.device:
+        raise ValueError("round_sig4: status must be one int32 on the input's device")
+    out = torch.empty(x.shape, dtype=torch.float64, device=x.device)
+    _capi.check(L.step_round_sig4(_lib.dptr(x), x.numel(), _lib.dptr(out), _lib.dptr(status), _lib.stream_ptr(x.device)), "step_round_sig4")
+    return out
+
+
+def _typed(t, dtype):
+    return t if (t.dtype == dtype and t.is_contiguous()) else t.to(dtype).contiguous()
+
+
+def eval_match(det_boxes, det_cls, det_start, gt_boxes, gt_cls, gt_start, gt_max, thresh):
+    """step_eval_match: det_boxes [R,4] f64 (x1,y1,x2,y2), det_cls [R] int32, det_start [NI+1] int64 (image k = rows det_start[k] ..
+    det_start[k+1], in labelling order), gt_boxes [M,4] f64, gt_cls [M] int32, gt_start [NI+1] int64, gt_max = the largest number of
+    ground-truth rows of one image (host int) -> (label [R] uint8: 0 false positive, 1 true positive, 2 removed as invalid box; match [R]
+    int32: the box the row's argmax chose, as an index inside its image's ground-truth rows, or -1)."""
+    L = _lib.lib()
+    dev = det_boxes.device
+    det_boxes, gt_boxes = _typed(det_boxes, torch.float64), _typed(gt_boxes, torch.float64)
+    det_cls, gt_cls = _typed(det_cls, torch.int32), _typed(gt_cls, torch.int32)
+    det_start, gt_start = _typed(det_start, torch.int64), _typed(gt_start, torch.int64)
+    NI, R, M = det_start.numel() - 1, det_cls.numel(), gt_cls.numel()
+    if gt_start.numel() != NI + 1 or NI < 0:
+        raise ValueError("eval_match: det_start and gt_start must both hold NI + 1 offsets")
+    label = torch.empty((R,), dtype=torch.uint8, device=dev)
+    match = torch.empty((R,), dtype=torch.int32, device=dev)
+    _capi.check(L.step_eval_match(_lib.dptr(det_boxes), _lib.dptr(det_cls), _lib.dptr(det_start), _lib.dptr(gt_boxes), _lib.dptr(gt_cls),
+                                  _lib.dptr(gt_start), NI, R, M, int(gt_max), float(thresh), _lib.dptr(label), _lib.dptr(match),
+                                  _lib.stream_ptr(dev)), "step_eval_match")
+    return label, match
+
+
+def eval_ap(cls_start, label, num_gt):
+    """step_eval_ap: cls_start [NC+1] int64 (class c = positions cls_start[c] .. cls_start[c+1] of label, descending score), label [R] uint8
+    (0 / 1), num_gt [NC] int64 -> (precision [R], recall [R], ap [NC]) float64; AP is NaN where num_gt == 0 and 0 for an empty list."""
+    L = _lib.lib()
+    dev = cls_start.device
+    cls_start, num_gt, label = _typed(cls_start, torch.int64), _typed(num_gt, torch.int64), _typed(label, torch.uint8)
+    NC, R = num_gt.numel(), label.numel()
+    if cls_start.numel() != NC + 1:
+        raise ValueError("eval_ap: cls_start must hold NC + 1 offsets")
+    precision = torch.empty((R,), dtype=torch.float64, device=dev)
+    recall = torch.empty((R,), dtype=torch.float64, device=dev)
+    ap = torch.empty((NC,), dtype=torch.float64, device=dev)
+    _capi.check(L.step_eval_ap(_lib.dptr(cls_start), _lib.dptr(label), _lib.dptr(num_gt), NC, R, _lib.dptr(precision), _lib.dptr(recall),
+                               _lib.dptr(ap), _lib.stream_ptr(dev)), "step_eval_ap")
+    return precision, recall, ap
+
+
 def select_prepare(prob, loc, first, last, clip_of, gt_mid, gt_count, width, height):
     """step_select_prepare: prob [N,T,NC], loc [N,T,4], first / last [N,Tw,4] | None, clip_of [N] int32, gt_mid [B,Gmax,4], gt_count [B]
     int32 (one device) -> (mean_prob [N,NC], vloc [N,T,4], vfirst, vlast ([N,Tw,4] | None), iou [N,Gmax]), fp32 on that device."""
