@@ -600,6 +600,40 @@ STEP_API int step_transpose_cs(const void* src, int src_dtype, void* dst, int ds
 STEP_API int step_clip_from_u8(const unsigned char* frames, int N, int T, int H, int W, int scale, const float* mean3,
                                const float* std3, int dtype, void* clip, step_stream_t stream);
 
+/* Clip augmentation: the training loader's transform (data/augmentations.py:540-586 TubeAugmentation; :601-615 BaseTransform)
+ * applied on the device to the decoder's uint8 BGR frames, one launch for a batch whose clips may differ in frame size.  Every random
+ * decision of that pipeline depends on frame shape and tubes only, so the host draws them (step_amd/augment.py, in the reference's RNG
+ * order) into a PLAN BLOCK in device memory (16-byte aligned), addressed in 4-byte words from its start:
+ *   words [0, 16 N)     step_aug_clip[N]
+ *   rect_off ...        step_aug_rect[n_rects] of clip n (RandomErase; rectangles in the cropped, mirrored frame; later ones win)
+ *   patch_off ...       float32 [y2-y1][x2-x1][3] noise of one rectangle, already in the range ConvertFromInts(scale) produces
+ * Per output pixel, in the reference's float32 arithmetic and order (no contraction): cv2.resize's bilinear taps from the cropped size
+ * (cw, ch) to (Wo, Ho) (equal sizes copy); each tap un-mirrored, replaced by the patch value inside an erase rectangle, else read at
+ * crop origin + tap and put through PhotometricDistort's point operations (brightness, contrast, BGR->HSV, saturation, hue, HSV->BGR,
+ * channel permutation; OpenCV's float32 HSV formulas) and ConvertFromInts(scale); then (v - mean[c]) / std[c], the optional
+ * (2,1,0) channel swap of data/ava.py:335 (rgb != 0), rounding to `dtype`, and the store into clip [N,T,3,Ho,Wo].
+ * mean3 / std3 are HOST pointers to 3 floats (NULL = 0 / 1).  The library cannot read the block on the host: the CALLER guarantees
+ * that every crop lies inside its source frame, every rectangle inside its crop and every offset inside the block. */
+#define STEP_AUG_MIRROR         1       /* flags */
+#define STEP_AUG_PHOTOMETRIC    2       /* PhotometricDistort is in the pipeline (else the four below are ignored) */
+#define STEP_AUG_BRIGHTNESS     4
+#define STEP_AUG_CONTRAST       8
+#define STEP_AUG_CONTRAST_FIRST 16      /* contrast before the HSV round trip (else after it) */
+#define STEP_AUG_SATURATION     32
+#define STEP_AUG_HUE            64
+typedef struct step_aug_clip {          /* 16 words */
+    unsigned long long src;             /* device address of this clip's uint8 frames [T,Hs,Ws,3] (BGR) */
+    int Hs, Ws;
+    int cx, cy, cw, ch;                 /* crop rectangle: origin and size */
+    int flags;
+    int perm;                           /* RandomLightingNoise: out[c] = in[(perm >> 2c) & 3]; identity = 0x24 */
+    float brightness, contrast, saturation, hue;
+    int n_rects, rect_off;
+} step_aug_clip;
+typedef struct step_aug_rect { int x1, y1, x2, y2, patch_off, reserved; } step_aug_rect;
+STEP_API int step_clip_augment_u8(const void* plan_block, int N, int T, int Ho, int Wo, int scale, const float* mean3,
+                                  const float* std3, int rgb, int dtype, void* clip, step_stream_t stream);
+
 /* Fused multi-tensor Adam over flat fp32 arenas: replaces optimizer.step() of torch.optim.Adam(params, lr=args.det_lr)
  * (train.py:126,348) over the single-tensor parameter groups of utils/solver.py:12-93 (per-group lr / weight_decay; the
  * schedulers of solver.py:96-180 rewrite group['lr'] between steps).  param / grad / exp_avg / exp_avg_sq: n fp32 elements

@@ -7,6 +7,9 @@ from . import dist  # noqa: F401
 from .optim import FlatAdam, FlatSGD, LossScaler  # noqa: F401
 from . import evaluate  # noqa: F401
 from .evaluate import FrameMAP, ava_evaluation  # noqa: F401
+from . import augment  # noqa: F401
+from .augment import BaseTransform, TubeAugmentation  # noqa: F401
 
-__all__ = ["BaseNet", "ROINet", "TwoBranchNet", "ContextNet", "I3D", "I3D_head", "FrameMAP", "ava_evaluation"]
+__all__ = ["BaseNet", "ROINet", "TwoBranchNet", "ContextNet", "I3D", "I3D_head", "FrameMAP", "ava_evaluation",
+           "TubeAugmentation", "BaseTransform"]
 __version__ = "0.1.0"

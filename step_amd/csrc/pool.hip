@@ -759,6 +759,210 @@ __global__ __launch_bounds__(256) void clip_from_u8_vec_kernel(const unsigned ch
     }
 }
 
+// Clip augmentation (include/step_amd.h: step_clip_augment_u8): the loader's transform -- PhotometricDistort, RandomSampleCrop,
+// RandomMirror, RandomErase, Resize, SubtractMeans, DivideStds (data/augmentations.py:172-305,457-483,540-586) -- as ONE gather from
+// the uint8 BGR source frames.  The host drew every decision into the plan (step_amd/augment.py); what is left is per pixel.
+// Every float32 step is one of aug_add / aug_sub / aug_mul / aug_div below and every function sits under `fp contract(off)`, so the
+// result is the reference's numpy / OpenCV arithmetic bit for bit (kernel cases against tests/golden/augment_golden.npz).
+#define AUG_RUN 8                                      // output columns per thread: one 16-byte store per plane for the 16-bit types
+
+// One float32 operation, rounded on its own.  (The toolchain's __fmul_rn / __fadd_rn are plain operators defined in a header that is
+// compiled with contraction allowed, so after inlining a product still fuses with the sum it feeds -- the hue and the bilinear blend
+// are such pairs; operators written under `fp contract(off)` carry no such permission, here and on the host interpreter alike.)
+__device__ __forceinline__ float aug_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float aug_sub(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+__device__ __forceinline__ float aug_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float aug_div(float a, float b) {
+#pragma clang fp contract(off)
+    return a / b;
+}
+
+// PhotometricDistort's point operations on one source pixel (b, g, r as float32), then ConvertFromInts(scale).
+__device__ __forceinline__ void aug_point(const unsigned char* __restrict__ p, const step_aug_clip& pc, int scale, float o[3]) {
+#pragma clang fp contract(off)
+    float b = (float)p[0], g = (float)p[1], r = (float)p[2];
+    const int fl = pc.flags;
+    if (fl & STEP_AUG_PHOTOMETRIC) {                                                     // (uniform over the workgroup)
+        if (fl & STEP_AUG_BRIGHTNESS) { b = aug_add(b, pc.brightness); g = aug_add(g, pc.brightness); r = aug_add(r, pc.brightness); }
+        const bool con = (fl & STEP_AUG_CONTRAST) != 0, first = (fl & STEP_AUG_CONTRAST_FIRST) != 0;
+        if (con && first) { b = aug_mul(b, pc.contrast); g = aug_mul(g, pc.contrast); r = aug_mul(r, pc.contrast); }
+        // BGR -> HSV (OpenCV's float32 form, h in degrees)
+        float v = fmaxf(fmaxf(r, g), b);
+        const float vmin = fminf(fminf(r, g), b);
+        const float diff = aug_sub(v, vmin);
+        float s = aug_div(diff, aug_add(fabsf(v), 1.1920928955078125e-7f));
+        const float d = (float)(60.0 / (double)aug_add(diff, 1.1920928955078125e-7f));
+        float h;
+        if (v == r) h = aug_mul(aug_sub(g, b), d);
+        else if (v == g) h = aug_add(aug_mul(aug_sub(b, r), d), 120.f);
+        else h = aug_add(aug_mul(aug_sub(r, g), d), 240.f);
+        if (h < 0.f) h = aug_add(h, 360.f);
+        if (fl & STEP_AUG_SATURATION) s = aug_mul(s, pc.saturation);
+        if (fl & STEP_AUG_HUE) {
+            h = aug_add(h, pc.hue);
+            if (h > 360.f) h = aug_sub(h, 360.f);
+            if (h < 0.f) h = aug_add(h, 360.f);
+        }
+        // HSV -> BGR
+        if (s == 0.f) {
+            b = g = r = v;
+        } else {
+            h = aug_mul(h, 6.f / 360.f);
+            if (h < 0.f) h = aug_add(h, 6.f);                       // (|h| <= 6.4 here: one step wraps it into [0, 6))
+            else if (h >= 6.f) h = aug_sub(h, 6.f);
+            int sector = (int)floorf(h);
+            h = aug_sub(h, (float)sector);
+            if ((unsigned)sector >= 6u) { sector = 0; h = 0.f; }
+            const float t1 = aug_mul(v, aug_sub(1.f, s));
+            const float t2 = aug_mul(v, aug_sub(1.f, aug_mul(s, h)));
+            const float t3 = aug_mul(v, aug_sub(1.f, aug_mul(s, aug_sub(1.f, h))));
+            switch (sector) {                                         // (b, g, r) = tab[{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}], tab = {v, t1, t2, t3}
+                case 0: b = t1; g = t3; r = v; break;
+                case 1: b = t1; g = v; r = t2; break;
+                case 2: b = t3; g = v; r = t1; break;
+                case 3: b = v; g = t2; r = t1; break;
+                case 4: b = v; g = t1; r = t3; break;
+                default: b = t2; g = t1; r = v; break;
+            }
+        }
+        if (con && !first) { b = aug_mul(b, pc.contrast); g = aug_mul(g, pc.contrast); r = aug_mul(r, pc.contrast); }
+        const float i0 = b, i1 = g, i2 = r;                           // RandomLightingNoise: out[c] = in[perm[c]] (selects, no indexed array)
+        const int p0 = pc.perm & 3, p1 = (pc.perm >> 2) & 3, p2 = (pc.perm >> 4) & 3;
+        b = p0 == 0 ? i0 : (p0 == 1 ? i1 : i2);
+        g = p1 == 0 ? i0 : (p1 == 1 ? i1 : i2);
+        r = p2 == 0 ? i0 : (p2 == 1 ? i1 : i2);
+        if (scale == 2) {                                             // np.clip(images, 0, 255): a no-op on the uint8 values of the other path
+            b = fminf(fmaxf(b, 0.f), 255.f); g = fminf(fmaxf(g, 0.f), 255.f); r = fminf(fmaxf(r, 0.f), 255.f);
+        }
+    }
+    o[0] = b; o[1] = g; o[2] = r;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (scale == 1) o[c] = aug_div(o[c], 255.f);
+        else if (scale == 2) o[c] = aug_sub(aug_div(aug_mul(o[c], 2.f), 255.f), 1.f);
+    }
+}
+
+// One tap of the resize, at (x, y) of the cropped, mirrored, erased frame the reference hands to cv2.resize.
+__device__ __forceinline__ void aug_tap(const unsigned char* __restrict__ frame, const step_aug_clip& pc, const step_aug_rect* __restrict__ rects,
+                                        const float* __restrict__ words, int x, int y, int scale, float o[3]) {
+    for (int k = pc.n_rects - 1; k >= 0; --k) {                        // later rectangles overwrite earlier ones
+        const step_aug_rect rc = rects[k];
+        if (x >= rc.x1 && x < rc.x2 && y >= rc.y1 && y < rc.y2) {
+            const float* q = words + rc.patch_off + ((size_t)(y - rc.y1) * (rc.x2 - rc.x1) + (x - rc.x1)) * 3;
+            o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+            return;
+        }
+    }
+    const int sx = pc.cx + ((pc.flags & STEP_AUG_MIRROR) ? pc.cw - 1 - x : x);
+    aug_point(frame + ((size_t)(pc.cy + y) * pc.Ws + sx) * 3, pc, scale, o);
+}
+
+// cv2.resize's bilinear source coordinate for float32 images: first tap and the weight of the second one.
+__device__ __forceinline__ void aug_coord(int d, int src, double ratio, int& s0, float& f) {
+#pragma clang fp contract(off)
+    f = (float)(((double)d + 0.5) * ratio - 0.5);
+    s0 = (int)floorf(f);
+    f = aug_sub(f, (float)s0);
+    if (s0 < 0) { s0 = 0; f = 0.f; }
+    if (s0 >= src - 1) { s0 = src - 1; f = 0.f; }
+}
+
+// grid (ceil(T * Ho * ceil(Wo / 8) / 256), N): a workgroup belongs to ONE clip, so the plan entry is uniform (scalar loads, uniform branches);
+// a thread makes AUG_RUN consecutive columns of one output row for the three planes (y weights once per thread).
+template <typename T>
+__global__ __launch_bounds__(256) void clip_augment_u8_kernel(const unsigned char* __restrict__ block, T* __restrict__ dst, int Tn, int Ho, int Wo,
+                                                              int scale, int rgb, float m0, float m1, float m2, float s0, float s1, float s2,
+                                                              int vec_ok) {
+#pragma clang fp contract(off)
+    const int n = blockIdx.y;
+    const step_aug_clip pc = ((const step_aug_clip*)block)[n];
+    const int runs = (Wo + AUG_RUN - 1) / AUG_RUN;
+    const long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= (long long)Tn * Ho * runs) return;
+    const int run = (int)(item % runs);
+    const int dy = (int)((item / runs) % Ho);
+    const int t = (int)(item / ((long long)runs * Ho));
+    const unsigned char* frame = (const unsigned char*)(uintptr_t)pc.src + (size_t)t * pc.Hs * pc.Ws * 3;
+    const step_aug_rect* rects = (const step_aug_rect*)(block + 4 * (size_t)pc.rect_off);
+    const float* words = (const float*)block;
+    const bool same = pc.cw == Wo && pc.ch == Ho;
+    const double rx = (double)pc.cw / Wo, ry = (double)pc.ch / Ho;
+    int sy = dy; float fy = 0.f;
+    if (!same) aug_coord(dy, pc.ch, ry, sy, fy);
+    const int sy1 = min(sy + 1, pc.ch - 1);
+    const float gy = aug_sub(1.f, fy);
+    const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+    float o[3][AUG_RUN];
+#pragma unroll
+    for (int j = 0; j < AUG_RUN; ++j) {
+        const int dx = run * AUG_RUN + j;
+        float v[3] = {0.f, 0.f, 0.f};
+        if (dx < Wo) {
+            if (same) {
+                aug_tap(frame, pc, rects, words, dx, dy, scale, v);
+            } else {
+                int sx; float fx;
+                aug_coord(dx, pc.cw, rx, sx, fx);
+                const int sx1 = min(sx + 1, pc.cw - 1);
+                const float gx = aug_sub(1.f, fx);
+                float a[3], b[3], c[3], d[3];
+                aug_tap(frame, pc, rects, words, sx, sy, scale, a);
+                aug_tap(frame, pc, rects, words, sx1, sy, scale, b);
+                aug_tap(frame, pc, rects, words, sx, sy1, scale, c);
+                aug_tap(frame, pc, rects, words, sx1, sy1, scale, d);
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {                        // horizontal pass on the two rows, then the vertical one
+                    const float r0 = aug_add(aug_mul(a[ch], gx), aug_mul(b[ch], fx));
+                    const float r1 = aug_add(aug_mul(c[ch], gx), aug_mul(d[ch], fx));
+                    v[ch] = aug_add(aug_mul(r0, gy), aug_mul(r1, fy));
+                }
+            }
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) o[ch][j] = aug_div(aug_sub(v[ch], mean[ch]), stdv[ch]);
+    }
+    const size_t HW = (size_t)Ho * Wo;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        T* d = dst + (((size_t)n * Tn + t) * 3 + (rgb ? 2 - ch : ch)) * HW + (size_t)dy * Wo + run * AUG_RUN;
+        if (vec_ok) {                                                   // Wo % 8 == 0 and a 16-byte aligned clip: whole runs, 16-byte stores
+            if constexpr (sizeof(T) == 2) {
+                u32x4 ov;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    ov[q] = (unsigned)elem<T>::bits16(o[ch][2 * q]) | ((unsigned)elem<T>::bits16(o[ch][2 * q + 1]) << 16);
+                *(u32x4*)d = ov;
+            } else {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    u32x4 ov;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        unsigned u;
+                        __builtin_memcpy(&u, &o[ch][4 * q + e], 4);
+                        ov[e] = u;
+                    }
+                    ((u32x4*)d)[q] = ov;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < AUG_RUN; ++j)
+                if (run * AUG_RUN + j < Wo) d[j] = elem<T>::from_f32(o[ch][j]);
+        }
+    }
+}
+
 template <typename T>
 __global__ void avgpool_hw_kernel(const T* __restrict__ x, T* __restrict__ y, int ND, int H, int W, int C, int kh,
                                   int kw, long long total) {
@@ -1063,6 +1267,29 @@ int step_clip_from_u8(const unsigned char* frames, int N, int T, int H, int W, i
         case STEP_BF16: STEP_LAUNCH((clip_from_u8_kernel<bf16_t>), grid, dim3(256), stream, frames, (bf16_t*)clip, H * W, fr, scale, m0, m1, m2, s0, s1, s2, total); break;
         case STEP_F16: STEP_LAUNCH((clip_from_u8_kernel<f16_t>), grid, dim3(256), stream, frames, (f16_t*)clip, H * W, fr, scale, m0, m1, m2, s0, s1, s2, total); break;
         default: return STEP_E_DTYPE;
+    }
+    return STEP_LAUNCH_CHECK();
+}
+
+int step_clip_augment_u8(const void* plan_block, int N, int T, int Ho, int Wo, int scale, const float* mean3, const float* std3, int rgb,
+                         int dtype, void* clip, step_stream_t stream) {
+    if (N < 0 || N > 65535 || T <= 0 || Ho <= 0 || Wo <= 0 || scale < 0 || scale > 2) return STEP_E_SHAPE;
+    if (dtype != STEP_F32 && dtype != STEP_BF16 && dtype != STEP_F16) return STEP_E_DTYPE;
+    if (N == 0) return STEP_OK;
+    if (!plan_block || !clip) return STEP_E_NULL;
+    if ((size_t)plan_block & 15) return STEP_E_ALIGN;
+    const float m0 = mean3 ? mean3[0] : 0.f, m1 = mean3 ? mean3[1] : 0.f, m2 = mean3 ? mean3[2] : 0.f;   // host pointers (3 floats)
+    const float s0 = std3 ? std3[0] : 1.f, s1 = std3 ? std3[1] : 1.f, s2 = std3 ? std3[2] : 1.f;
+    const long long items = (long long)T * Ho * ((Wo + AUG_RUN - 1) / AUG_RUN);
+    const long long gx = (items + 255) / 256;
+    if (gx > 0x7fffffffLL) return STEP_E_SHAPE;
+    const dim3 grid((unsigned)gx, (unsigned)N);
+    const int vec_ok = (Wo % AUG_RUN == 0 && ((size_t)clip & 15) == 0) ? 1 : 0;
+    const unsigned char* blk = (const unsigned char*)plan_block;
+    switch (dtype) {
+        case STEP_F32: STEP_LAUNCH((clip_augment_u8_kernel<float>), grid, dim3(256), stream, blk, (float*)clip, T, Ho, Wo, scale, rgb ? 1 : 0, m0, m1, m2, s0, s1, s2, vec_ok); break;
+        case STEP_BF16: STEP_LAUNCH((clip_augment_u8_kernel<bf16_t>), grid, dim3(256), stream, blk, (bf16_t*)clip, T, Ho, Wo, scale, rgb ? 1 : 0, m0, m1, m2, s0, s1, s2, vec_ok); break;
+        default: STEP_LAUNCH((clip_augment_u8_kernel<f16_t>), grid, dim3(256), stream, blk, (f16_t*)clip, T, Ho, Wo, scale, rgb ? 1 : 0, m0, m1, m2, s0, s1, s2, vec_ok); break;
     }
     return STEP_LAUNCH_CHECK();
 }

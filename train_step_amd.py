@@ -23,7 +23,10 @@ Every rank
 Data: synthetic AVA-shaped clips [B,36,3,400,400] and fixed anchor tubes (there is no dataset in this repository; the reference's
 loader, data/ava.py, hands over the same shapes).  --feed u8 keeps the clips as uint8 frames in pinned host memory and moves them
 host -> device every iteration on a copy stream (`step_clip_from_u8` writes the captured step's input): the transfer of iteration
-k + 1 runs under the replay of iteration k.
+k + 1 runs under the replay of iteration k.  --feed u8 --augment keeps the frames at the SOURCE size (--src-size, default 256x340) and runs the
+reference's training transform on the device instead (`step_amd.TubeAugmentation`: a host plan per clip over synthetic tubes, drawn in
+the reference's RNG order, then one `step_clip_augment_u8` launch -- photometric distortion, crop, mirror, erase, resize to the
+network's resolution -- writes the captured step's input where `step_clip_from_u8` does without the flag).
 """
 import argparse
 import json
@@ -57,6 +60,10 @@ def main():
                     help="the reference's whole iteration (train.py:257-348): no-grad inference + train_select between the steps (workloads.C4SelectTrainStep, "
                          "captured as graphs around the host's selection)")
     ap.add_argument("--feed", default="none", choices=["none", "u8"])
+    ap.add_argument("--augment", action="store_true",
+                    help="--feed u8 only: uint8 frames at --src-size, the reference's TubeAugmentation (all four switches on, scripts/train_step.sh:55-58) "
+                         "applied on the device by step_clip_augment_u8")
+    ap.add_argument("--src-size", default="256x340", help="--augment: HxW of the decoded source frames")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
                     help="process-group backend (default: nccl = RCCL; gloo only to exercise the multi-rank program with ranks SHARING one GPU, "
@@ -64,6 +71,8 @@ def main():
     a = ap.parse_args()
     if a.optimizer == "sgd" and a.momentum <= 0:
         raise SystemExit("train_step_amd.py: --momentum must be positive (the workload's momentum buffer is allocated at construction)")
+    if a.augment and a.feed != "u8":
+        raise SystemExit("train_step_amd.py: --augment needs --feed u8 (the augmentation reads the uint8 frames)")
     if not torch.cuda.is_available():
         raise SystemExit("train_step_amd.py needs a ROCm device (there is no CPU fallback)")
 
@@ -104,8 +113,17 @@ def main():
     if a.feed == "u8":
         N, T, _, H, W = w.x.shape
         g_ = torch.Generator().manual_seed(999 + rank)
-        host = [torch.randint(0, 256, (N, T, H, W, 3), dtype=torch.uint8, generator=g_).pin_memory() for _ in range(2)]
-        stage = [torch.empty((N, T, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+        Hs, Ws = (int(v) for v in a.src_size.lower().split("x")) if a.augment else (H, W)
+        host = [torch.randint(0, 256, (N, T, Hs, Ws, 3), dtype=torch.uint8, generator=g_).pin_memory() for _ in range(2)]
+        stage = [torch.empty((N, T, Hs, Ws, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+        if a.augment:
+            import numpy as np
+            from step_amd import TubeAugmentation
+            np.random.seed(2000 + rank)                           # (the plans draw from numpy's global stream, as the reference's transform does)
+            aug = TubeAugmentation((W, H), do_flip=True, do_crop=True, do_photometric=True, do_erase=True, scale=2)
+            centre = np.random.uniform(0.35, 0.65, (N, 2, 1, 2))
+            half = np.random.uniform(0.1, 0.25, (N, 2, 1, 2))
+            gt_tubes = np.tile(np.concatenate([centre - half, centre + half], 3), (1, 1, T, 1)).astype(np.float32)   # two synthetic tubes per clip
         # a stream of its own at DEFAULT priority.  (Round 5 gave it high priority, as bench.py's forward-only fed loop does; beside the captured
         # TRAINING step -- whose graph forks onto side streams -- a high-priority stream that spends its time waiting on the main stream made
         # the whole iteration 3x slower: 40.3 against 13.6 ms, tools/feed_train_probe.py, profiles/r06_feed_train_probe.txt)
@@ -120,7 +138,11 @@ def main():
 
         def feed(k):
             main_stream.wait_event(copied[k % 2])
-            ops.clip_from_u8(stage[k % 2], scale=2, out=w.x)     # the captured step's static input
+            if a.augment:                                        # what a dataset worker does per clip (host, no pixels) + one launch for the batch
+                plans = [aug.plan((T, Hs, Ws), gt_tubes[n])[0] for n in range(N)]
+                aug.apply(stage[k % 2], plans, out=w.x)
+            else:
+                ops.clip_from_u8(stage[k % 2], scale=2, out=w.x)     # the captured step's static input
             copy_stream.wait_stream(main_stream)                 # (the next copy into the OTHER buffer may start at once; this one is re-used at k + 2)
             prefetch(k + 1)
         prefetch(0)
@@ -156,7 +178,7 @@ def main():
                           "ms_per_iter": round(el / max(a.iters, 1) * 1e3, 3), "clips_per_s": round(gb * a.iters / el, 3),
                           "launch": ("hipGraph replay (%s)" % w.graph_mode) if w.graph is not None else "eager",
                           "gradient_exchange": _exchange_label(w, world),
-                          "feed": a.feed, "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
+                          "feed": a.feed + ("+augment" if a.augment else ""), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
                           **({"adam_steps": w.opt.step_count} if a.optimizer == "adam" else {})}), flush=True)
     if world > 1:
         torch.distributed.barrier()
