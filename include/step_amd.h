@@ -52,7 +52,8 @@ enum {
     STEP_E_ALIGN = -5
 };
 
-/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change. */
+/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (40: step_dropout_forward /
+ * step_dropout_backward / step_rng_words). */
 STEP_API const char* step_version(void);
 STEP_API int step_abi_version(void);
 
@@ -717,6 +718,36 @@ STEP_API int step_head_outputs_backward(int dtype, const void* logits, int logit
                                         int T, int NC, const float* tubes, const float* targets, const float* g_loss_cls,
                                         const float* g_loss_loc, const float* g_loss_nbr, void* g_logits, void* g_reg,
                                         step_stream_t stream);
+
+/* Dropout of the heads (models/two_branch.py:244-263; torch.nn.Dropout in the reference) with a counter-based generator whose state
+ * lives on the device, so that successive calls AND successive replays of a captured graph draw new masks with no host involvement.
+ *
+ * The stream.  rng_state = two unsigned long long on the device, {seed, offset}.  Philox4x32-10 as in Random123 (round multipliers
+ * 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85; the 32x32 -> 64 products split into high and low words):
+ *     key     = (seed_lo, seed_hi)
+ *     counter = (blk_lo, blk_hi, offset_lo, offset_hi),   blk = e >> 2 for the flat index e of an element of the logical contiguous tensor
+ *     element e draws word (e & 3) of its block.
+ * Keep rule.  thr = (uint64)floor(p * 2^32), taken in double; element e is KEPT iff (uint64)word >= thr (p = 0 keeps everything, p = 1
+ * nothing).  kept: y = round_to_dtype(float(x) * scale), scale = (float)(1.0 / (1.0 - p)) (0 when p == 1); dropped: y = +0.0 by selection,
+ * not by multiplication -- a dropped NaN or inf becomes 0.
+ * Mask.  ceil(n / 32) uint32 words, bit (e & 31) of word (e >> 5) set = kept; the unused high bits of the last word are 0.  n / 8 bytes
+ * instead of torch's n-element mask; the backward pass reads it back instead of regenerating the stream (it then needs neither the
+ * state nor the offset of the forward call, and a later fusion into the following GEMM's operand load can consume the same words).
+ *
+ * step_dropout_forward  reads {seed, offset} on the device, writes y [n] (`dtype`; y == x is allowed) and mask; a one-thread kernel
+ *                       behind the pass on the same stream then increments offset by 1 (also for n == 0: the call counts).
+ * step_dropout_backward gx = bit ? round_to_dtype(float(gy) * scale) : +0 from the stored mask only (gx == gy is allowed); it does not
+ *                       touch the generator, so re-seeding between forward and backward is harmless.
+ * step_rng_words        diagnostic: the raw stream -- the four words of blocks first_blk .. first_blk + n_blk - 1 at the state's seed
+ *                       and offset into out [4 * n_blk]; does not advance the state.
+ * Calls on ONE state must be stream-ordered (same stream, or ordered by events): the offset is read by the pass and bumped behind it.
+ * x / y / gy / gx aligned to their element size (16-byte aligned tensors take the vector path), 0 <= p <= 1, n < 2^44. */
+STEP_API int step_dropout_forward(int dtype, const void* x, void* y, uint32_t* mask, long long n, double p,
+                                  unsigned long long* rng_state, step_stream_t stream);
+STEP_API int step_dropout_backward(int dtype, const void* gy, void* gx, const uint32_t* mask, long long n, double p,
+                                   step_stream_t stream);
+STEP_API int step_rng_words(const unsigned long long* rng_state, unsigned long long first_blk, long long n_blk, uint32_t* out,
+                            step_stream_t stream);
 
 /* Batch-statistics BatchNorm3d (+ ReLU) of a conv unit: the TRAINING-mode BatchNorm of --freeze_stats False (models/networks.py:85-99
  * leaves the layers in train mode; models/i3dpt.py:95-110, models/two_branch.py:160,372).  Eval-mode BN is folded into the conv

@@ -2,7 +2,9 @@
 ROIAlign / ROIPool / NMS.  Drop-in for the reference's `models` package and
 `external.maskrcnn_benchmark.roi_layers` package."""
 from .backbone import BaseNet, I3D, I3D_head, build_base_i3d, weights_init  # noqa: F401
-from .heads import ContextNet, ROINet, TwoBranchNet  # noqa: F401
+from .heads import ContextNet, Dropout, ROINet, TwoBranchNet  # noqa: F401
+from . import rng  # noqa: F401
+from .rng import DeviceRNG, manual_seed  # noqa: F401
 from . import dist  # noqa: F401
 from .optim import FlatAdam, FlatSGD, LossScaler  # noqa: F401
 from . import evaluate  # noqa: F401
@@ -11,5 +13,5 @@ from . import augment  # noqa: F401
 from .augment import BaseTransform, TubeAugmentation  # noqa: F401
 
 __all__ = ["BaseNet", "ROINet", "TwoBranchNet", "ContextNet", "I3D", "I3D_head", "FrameMAP", "ava_evaluation",
-           "TubeAugmentation", "BaseTransform"]
+           "TubeAugmentation", "BaseTransform", "Dropout", "DeviceRNG", "manual_seed"]
 __version__ = "0.1.0"

@@ -5,7 +5,7 @@ import ctypes as C
 F32, BF16, F16 = 0, 1, 2
 NCHW, NHWC = 0, 1
 ROI_BWD_GATHER, ROI_BWD_ATOMIC = 0, 1
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 vp, fp, ip, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # raw device addresses
 i, f, ll, sz = C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -119,6 +119,9 @@ SIGNATURES = {
     "step_bn_train_backward": (i, [i, vp, i, vp, i, i, vp, i, ll, i, i, fp, fp, fp, vp, fp, fp, vp, sz, vp]),
     "step_head_outputs": (i, [i, vp, i, vp, i, i, i, i, i, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]),
     "step_head_outputs_backward": (i, [i, vp, i, vp, i, i, i, i, i, fp, fp, fp, fp, fp, vp, vp, vp]),
+    "step_dropout_forward": (i, [i, vp, vp, vp, ll, C.c_double, vp, vp]),
+    "step_dropout_backward": (i, [i, vp, vp, vp, ll, C.c_double, vp]),
+    "step_rng_words": (i, [vp, C.c_ulonglong, ll, vp, vp]),
     "step_tube_update": (i, [fp, i, i, fp, fp, fp, i, i, i, ip, i, f, f, fp, fp, fp, fp, vp]),
     "step_select_prepare": (i, [fp, fp, fp, fp, i, i, i, i, ip, fp, ip, i, f, f, fp, fp, fp, fp, fp, vp]),
     "step_adam_flat": (i, [fp, fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, C.c_double, i, f, i, vp]),

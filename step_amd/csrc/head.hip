@@ -11,6 +11,7 @@
 // fixed-order reductions (bit-reproducible).  The reference's `if mask.sum():` host branches are taken on the device: an all-zero
 // mask gives exactly zero losses and zero gradients (heads.py SYNC_FREE_LOSSES documents the one visible difference in shape).
 #include "common.h"
+#include <cmath>
 
 namespace step {
 
@@ -182,6 +183,136 @@ __global__ __launch_bounds__(256) void head_outputs_bwd_kernel(HeadParams p) {
     }
 }
 
+// ---- dropout (models/two_branch.py:244-263: three call sites per head) ---------------------------------------------------------------
+// A counter-based stream, so that a mask is a pure function of (seed, offset, element index): Philox4x32-10 (Random123), key = the
+// seed's two halves, counter = (blk_lo, blk_hi, offset_lo, offset_hi) with blk = e >> 2, element e takes word e & 3 of its block.
+// {seed, offset} live on the device; a one-thread kernel behind the pass bumps the offset, so a replayed graph draws a fresh mask on
+// every replay (the pattern of step_sgd_flat_dev's counter).  include/step_amd.h has the definition in full.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+template <typename T> union vec16 { u32x4 q; T e[elem<T>::VEC]; };
+
+// round_to_dtype(float(x) * scale), scale > 0.  For fp16 the compiler folds the widening, the multiply and the narrowing into one
+// v_fma_mixlo_f16 with a +0 addend, and (-0) * scale + (+0) is +0: a kept -0 would lose its sign (seen on the MI355X; the interpreter
+// build multiplies and converts separately).  The product is symmetric in the sign of x, so fp16 scales |x| and puts the sign bit back.
+template <typename T> __device__ __forceinline__ T drop_scale(T x, float scale) { return elem<T>::from_f32(elem<T>::to_f32(x) * scale); }
+template <> __device__ __forceinline__ f16_t drop_scale<f16_t>(f16_t x, float scale) {
+    f16_t r;
+    r.v = (unsigned short)(f32_to_f16_bits(fabsf(f16_bits_to_f32(x.v)) * scale) | (x.v & 0x8000u));
+    return r;
+}
+
+constexpr int DROP_PER_LANE = 32;                        // elements per thread = one mask word's worth
+constexpr int DROP_PER_WAVE = 64 * DROP_PER_LANE;
+constexpr int DROP_PER_BLOCK = 4 * DROP_PER_WAVE;
+
+// One wave covers 2048 consecutive elements in 32 / VEC load instructions of 16 bytes per lane, lanes contiguous within each
+// instruction.  A mask word (32 elements) therefore spans NL = 32 / VEC neighbouring lanes of ONE instruction: every lane collects its
+// VEC keep bits per instruction into `mine` (field j = instruction j), and a shuffle transpose inside each group of NL lanes hands lane q of
+// the group the whole word of instruction q -- 64 words per wave, one store per lane, no atomics.  Elements past n keep bit 0 and are
+// neither read nor written (partial vectors and misaligned tensors go element by element).
+template <typename T>
+__global__ __launch_bounds__(256) void dropout_fwd_kernel(const T* x, T* y, uint32_t* mask, long long n, unsigned long long thr, float scale,
+                                                          const unsigned long long* rng, int vec_ok) {
+    constexpr int V = elem<T>::VEC, NL = DROP_PER_LANE / V;
+    const int lane = threadIdx.x & 63;
+    const long long wbase = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * DROP_PER_WAVE;
+    if (wbase >= n) return;                                                  // (whole waves only: the shuffles below stay convergent)
+    const unsigned long long seed = rng[0], off = rng[1];
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), o0 = (unsigned)off, o1 = (unsigned)(off >> 32);
+    unsigned mine = 0;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+        const long long e0 = wbase + (long long)j * (64 * V) + lane * V;
+        if (e0 >= n) continue;
+        const bool full = vec_ok && e0 + V <= n;
+        vec16<T> v, o;
+        if (full) {
+            v.q = *(const u32x4*)(x + e0);
+        } else {
+            for (int i = 0; i < V; ++i) v.e[i] = e0 + i < n ? x[e0 + i] : elem<T>::from_f32(0.f);
+        }
+        unsigned bits = 0;
+#pragma unroll
+        for (int b = 0; b < V / 4; ++b) {
+            const unsigned long long blk = (unsigned long long)(e0 >> 2) + b;
+            unsigned w[4];
+            philox4x32_10((unsigned)blk, (unsigned)(blk >> 32), o0, o1, k0, k1, w);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const bool keep = (unsigned long long)w[i] >= thr && e0 + 4 * b + i < n;
+                o.e[4 * b + i] = keep ? drop_scale<T>(v.e[4 * b + i], scale) : elem<T>::from_f32(0.f);         // dropped: +0 by selection
+                bits |= (keep ? 1u : 0u) << (4 * b + i);
+            }
+        }
+        if (full) {
+            *(u32x4*)(y + e0) = o.q;
+        } else {
+            for (int i = 0; i < V; ++i) if (e0 + i < n) y[e0 + i] = o.e[i];
+        }
+        mine |= bits << (V * j);
+    }
+    const int grp = lane / NL, q = lane % NL;
+    unsigned word = 0;
+#pragma unroll
+    for (int k = 0; k < NL; ++k) {
+        const unsigned t = __shfl(mine, grp * NL + k);
+        word |= ((t >> (V * q)) & ((1u << V) - 1u)) << (V * k);
+    }
+    const long long wi = (wbase >> 5) + q * (64 / NL) + grp;               // instruction q covers 64 * V elements = 64 / NL words
+    if (wi < (n + 31) >> 5) mask[wi] = word;
+}
+
+// gx = bit ? round(float(gy) * scale) : +0 from the stored mask; the same element-to-lane map as the forward pass
+template <typename T>
+__global__ __launch_bounds__(256) void dropout_bwd_kernel(const T* gy, T* gx, const uint32_t* mask, long long n, float scale, int vec_ok) {
+    constexpr int V = elem<T>::VEC, NL = DROP_PER_LANE / V;
+    const int lane = threadIdx.x & 63;
+    const long long wbase = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * DROP_PER_WAVE;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+        const long long e0 = wbase + (long long)j * (64 * V) + lane * V;
+        if (e0 >= n) continue;
+        const bool full = vec_ok && e0 + V <= n;
+        const unsigned bits = mask[e0 >> 5] >> (unsigned)(e0 & 31);
+        vec16<T> v, o;
+        if (full) {
+            v.q = *(const u32x4*)(gy + e0);
+        } else {
+            for (int i = 0; i < V; ++i) v.e[i] = e0 + i < n ? gy[e0 + i] : elem<T>::from_f32(0.f);
+        }
+#pragma unroll
+        for (int i = 0; i < V; ++i) o.e[i] = ((bits >> i) & 1u) ? drop_scale<T>(v.e[i], scale) : elem<T>::from_f32(0.f);
+        if (full) {
+            *(u32x4*)(gx + e0) = o.q;
+        } else {
+            for (int i = 0; i < V; ++i) if (e0 + i < n) gx[e0 + i] = o.e[i];
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void rng_advance_kernel(unsigned long long* rng) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) rng[1] += 1ull;
+}
+
+__global__ __launch_bounds__(256) void rng_words_kernel(const unsigned long long* rng, unsigned long long first_blk, long long n_blk, uint32_t* out) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_blk) return;
+    const unsigned long long seed = rng[0], off = rng[1], blk = first_blk + (unsigned long long)t;
+    unsigned w[4];
+    philox4x32_10((unsigned)blk, (unsigned)(blk >> 32), (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
+    for (int i = 0; i < 4; ++i) out[4 * t + i] = w[i];
+}
+
 }  // namespace step
 
 using namespace step;
@@ -236,6 +367,66 @@ int step_head_outputs_backward(int dtype, const void* logits, int logits_stride,
         case STEP_BF16: STEP_LAUNCH((head_outputs_bwd_kernel<bf16_t>), dim3(1), dim3(256), stream, p); break;
         default: STEP_LAUNCH((head_outputs_bwd_kernel<f16_t>), dim3(1), dim3(256), stream, p); break;
     }
+    return STEP_LAUNCH_CHECK();
+}
+
+// keep threshold and scale of a drop probability: keep iff (uint64)word >= floor(p * 2^32), scale = 1 / (1 - p) taken in double
+static int dropout_consts(int dtype, long long n, double p, unsigned long long& thr, float& scale, long long& blocks) {
+    if (dtype != STEP_F32 && dtype != STEP_BF16 && dtype != STEP_F16) return STEP_E_DTYPE;
+    if (n < 0 || !(p >= 0.0 && p <= 1.0)) return STEP_E_SHAPE;
+    blocks = (n + DROP_PER_BLOCK - 1) / DROP_PER_BLOCK;
+    if (blocks > 0x7fffffffLL) return STEP_E_UNSUPPORTED;
+    thr = (unsigned long long)std::floor(p * 4294967296.0);
+    scale = p == 1.0 ? 0.f : (float)(1.0 / (1.0 - p));
+    return STEP_OK;
+}
+
+int step_dropout_forward(int dtype, const void* x, void* y, uint32_t* mask, long long n, double p, unsigned long long* rng_state,
+                         step_stream_t stream) {
+    unsigned long long thr; float scale; long long blocks;
+    const int rc = dropout_consts(dtype, n, p, thr, scale, blocks);
+    if (rc) return rc;
+    if (!rng_state || (n > 0 && (!x || !y || !mask))) return STEP_E_NULL;
+    const int es = dtype == STEP_F32 ? 4 : 2;
+    if ((((uintptr_t)x) | ((uintptr_t)y)) & (es - 1) || ((uintptr_t)mask & 3) || ((uintptr_t)rng_state & 7)) return STEP_E_ALIGN;
+    const int vec_ok = ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
+    if (n > 0) {
+        const dim3 grid((unsigned)blocks);
+        switch (dtype) {
+            case STEP_F32: STEP_LAUNCH((dropout_fwd_kernel<float>), grid, dim3(256), stream, (const float*)x, (float*)y, mask, n, thr, scale, (const unsigned long long*)rng_state, vec_ok); break;
+            case STEP_BF16: STEP_LAUNCH((dropout_fwd_kernel<bf16_t>), grid, dim3(256), stream, (const bf16_t*)x, (bf16_t*)y, mask, n, thr, scale, (const unsigned long long*)rng_state, vec_ok); break;
+            default: STEP_LAUNCH((dropout_fwd_kernel<f16_t>), grid, dim3(256), stream, (const f16_t*)x, (f16_t*)y, mask, n, thr, scale, (const unsigned long long*)rng_state, vec_ok); break;
+        }
+    }
+    STEP_LAUNCH(rng_advance_kernel, dim3(1), dim3(64), stream, rng_state);     // (also for n == 0: the call counts)
+    return STEP_LAUNCH_CHECK();
+}
+
+int step_dropout_backward(int dtype, const void* gy, void* gx, const uint32_t* mask, long long n, double p, step_stream_t stream) {
+    unsigned long long thr; float scale; long long blocks;
+    const int rc = dropout_consts(dtype, n, p, thr, scale, blocks);
+    if (rc) return rc;
+    if (n == 0) return STEP_OK;
+    if (!gy || !gx || !mask) return STEP_E_NULL;
+    const int es = dtype == STEP_F32 ? 4 : 2;
+    if ((((uintptr_t)gy) | ((uintptr_t)gx)) & (es - 1) || ((uintptr_t)mask & 3)) return STEP_E_ALIGN;
+    const int vec_ok = ((((uintptr_t)gy) | ((uintptr_t)gx)) & 15) == 0;
+    const dim3 grid((unsigned)blocks);
+    switch (dtype) {
+        case STEP_F32: STEP_LAUNCH((dropout_bwd_kernel<float>), grid, dim3(256), stream, (const float*)gy, (float*)gx, mask, n, scale, vec_ok); break;
+        case STEP_BF16: STEP_LAUNCH((dropout_bwd_kernel<bf16_t>), grid, dim3(256), stream, (const bf16_t*)gy, (bf16_t*)gx, mask, n, scale, vec_ok); break;
+        default: STEP_LAUNCH((dropout_bwd_kernel<f16_t>), grid, dim3(256), stream, (const f16_t*)gy, (f16_t*)gx, mask, n, scale, vec_ok); break;
+    }
+    return STEP_LAUNCH_CHECK();
+}
+
+int step_rng_words(const unsigned long long* rng_state, unsigned long long first_blk, long long n_blk, uint32_t* out, step_stream_t stream) {
+    if (n_blk < 0) return STEP_E_SHAPE;
+    if (n_blk == 0) return STEP_OK;
+    if (!rng_state || !out) return STEP_E_NULL;
+    const long long blocks = (n_blk + 255) / 256;
+    if (blocks > 0x7fffffffLL) return STEP_E_UNSUPPORTED;
+    STEP_LAUNCH(rng_words_kernel, dim3((unsigned)blocks), dim3(256), stream, rng_state, first_blk, n_blk, out);
     return STEP_LAUNCH_CHECK();
 }
 

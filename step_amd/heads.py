@@ -51,6 +51,41 @@ class _HeadOutputsFn(torch.autograd.Function):
         return g_logits, g_reg, None, None, None, None, None, None
 
 
+DEVICE_DROPOUT = os.environ.get("STEP_TORCH_DROPOUT", "0") != "1"   # TwoBranchNet.dropout: step_amd.Dropout (the HIP kernel, device-side generator); False / STEP_TORCH_DROPOUT=1: torch.nn.Dropout
+
+
+class _DropoutFn(torch.autograd.Function):
+    """step_dropout_forward / step_dropout_backward: one launch each, only the bit mask (n / 8 bytes) is kept for backward."""
+
+    @staticmethod
+    def forward(ctx, x, p, inplace):
+        xd = x.detach()
+        y, mask = ops.dropout(xd, p, out=xd if inplace else None)
+        ctx.save_for_backward(mask)
+        ctx.p = p
+        if inplace:
+            ctx.mark_dirty(x)
+            return x
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        mask, = ctx.saved_tensors
+        return ops.dropout_backward(gy, mask, ctx.p), None, None
+
+
+class Dropout(nn.Dropout):
+    """torch.nn.Dropout on the HIP kernel: same constructor and `p` (a subclass, so `isinstance(m, nn.Dropout)` still finds it), no
+    parameters or buffers.  The mask comes from the device's counter-based generator (step_amd.rng.default, seeded by
+    step_amd.manual_seed), so the module replays inside a captured graph with a fresh mask per replay.  Identity -- no launch, the
+    generator untouched -- in eval mode and at p == 0."""
+
+    def forward(self, x):
+        if not self.training or self.p == 0:
+            return x
+        return _DropoutFn.apply(x, float(self.p), bool(self.inplace))
+
+
 class ROINet(nn.Module):
     """ROI pool | align over tubes: frames are flattened into the batch axis and each tube box is a
     2-D ROI on its own frame (models/networks.py:35-47)."""
@@ -253,7 +288,7 @@ class TwoBranchNet(nn.Module):
         if self.freeze_affine:
             freeze_bn_affine(self.i3d_conv)
         self.downsample = nn.Conv3d(1024, self.fc_dim, kernel_size=1, stride=1, bias=True)
-        self.dropout = nn.Dropout(self.dropout_prob)
+        self.dropout = Dropout(self.dropout_prob) if DEVICE_DROPOUT else nn.Dropout(self.dropout_prob)
         self.global_cls = nn.Conv3d(flat + (0 if self.no_context else 1024), self.num_classes, (1, 1, 1), bias=True)
         self._u_down = ConvUnit(self, lambda m: m.downsample.weight, (1, 1, 1), bias_fn=lambda m: m.downsample.bias)
         perm = _nhwc_flatten_perm(self.fc_dim, P2)

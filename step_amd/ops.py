@@ -1223,6 +1223,36 @@ def head_outputs_backward(logits, reg, N, Tl, T, NC, tubes, targets, g_cls, g_lo
     return g_logits.reshape(logits.shape), (None if g_reg is None else g_reg.reshape(reg.shape))
 
 
+def dropout(x, p, rng=None, out=None):
+    """step_dropout_forward -> (y, mask): y shaped like x, mask int32[ceil(n / 32)] with bit e & 31 of word e >> 5 set where element e of
+    the contiguous tensor was kept.  rng: a step_amd.rng.DeviceRNG (default: the device's); its offset advances by one on the device.
+    out = x writes in place."""
+    from . import rng as _rng
+    L = _lib.lib()
+    if not x.is_contiguous():
+        if out is x:
+            raise RuntimeError("step_amd: in-place dropout wants a contiguous tensor")
+        x = x.contiguous()
+    g = rng if rng is not None else _rng.default(x.device)
+    n = x.numel()
+    y = out if out is not None else torch.empty_like(x)
+    mask = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=x.device)
+    _capi.check(L.step_dropout_forward(_dt(x), _lib.dptr(x), _lib.dptr(y), _lib.dptr(mask), n, float(p), _lib.dptr(g.state),
+                                       _lib.stream_ptr(x.device)), "step_dropout_forward")
+    return y, mask
+
+
+def dropout_backward(gy, mask, p):
+    """step_dropout_backward: gx = kept ? gy * 1 / (1 - p) : 0 from the mask of the forward call."""
+    L = _lib.lib()
+    if not gy.is_contiguous():
+        gy = gy.contiguous()
+    gx = torch.empty_like(gy)
+    _capi.check(L.step_dropout_backward(_dt(gy), _lib.dptr(gy), _lib.dptr(gx), _lib.dptr(mask), gy.numel(), float(p),
+                                        _lib.stream_ptr(gy.device)), "step_dropout_backward")
+    return gx
+
+
 def tube_update(flat, local_loc, first_loc, last_loc, clip_of, first_off, last_off, extend, width, height):
     """One refinement step's tube bookkeeping (step_tube_update): returns (pred_loc, pred_first, pred_last, next_flat)."""
     L = _lib.lib()

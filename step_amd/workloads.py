@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from . import BaseNet, ContextNet, ROINet, TwoBranchNet
+from . import rng as srng
 from . import dist as sdist
 from .driver import GraphedInference, inference, inference_flat, postprocess
 from .backbone import wgrad_into_grad
@@ -28,8 +29,8 @@ def step_cfg(**kw):
     return NS(**base)
 
 
-def build_nets(dev, seed=123, heads=3):
-    args = step_cfg()
+def build_nets(dev, seed=123, heads=3, **cfg):
+    args = step_cfg(**cfg)                                        # (overrides of the recipe: dropout=0.3 is scripts/train_step.sh:41)
     torch.manual_seed(seed)                                       # config.py:38 man_seed
     base = BaseNet(args).to(dev).eval()
     ctx = ContextNet(args).to(dev).eval()
@@ -105,10 +106,14 @@ class C4TrainStep:
     same `tubes_per_clip` anchor tubes, extended to the step's length."""
 
     def __init__(self, dev, batch=1, tubes_per_clip=5, seed=123, max_iter=3, dtype=torch.float32, capturable=False, force_exchange=False,
-                 optimizer="adam"):
+                 optimizer="adam", dropout=0.0, rng_seed=0):
         # replicas: the same weights on every rank (same init seed, then rank 0's copy is broadcast once, as DDP does);
         # `seed` only varies the rank's clips
-        self.args, self.base, self.ctx, self.nets = build_nets(dev, 123, heads=max_iter)
+        self.args, self.base, self.ctx, self.nets = build_nets(dev, 123, heads=max_iter, dropout=dropout)
+        # dropout > 0 (the reference's recipe: 0.3): the heads' three dropout sites draw from the device-side generator (step_amd.Dropout), whose
+        # offset advances inside the captured step; the state exists before any capture and is written from the host only here
+        srng.manual_seed(rng_seed)
+        self.rng = srng.default(dev)
         self.heads = [self.nets["det_net%d" % i] for i in range(max_iter)]
         self.mods = [self.base, self.ctx] + self.heads
         sdist.broadcast_parameters(self.mods)
@@ -317,9 +322,9 @@ class C4SelectTrainStep(C4TrainStep):
                       Same kernels on the same buffers as step_padded(): bit-identical trajectory (tests/test_gpu_graph_step.py)."""
 
     def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, tubes_per_clip=34, capturable=False, force_exchange=False, budget=None,
-                 optimizer="adam"):
+                 optimizer="adam", dropout=0.0, rng_seed=0):
         super().__init__(dev, batch=batch, tubes_per_clip=5, seed=seed, max_iter=3, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
-                         optimizer=optimizer)
+                         optimizer=optimizer, dropout=dropout, rng_seed=rng_seed)
         rs = np.random.RandomState(seed)
         anchors = (generate_anchors()[:tubes_per_clip] * 400.0).astype(np.float32)
         self.init_tubes = [np.tile(anchors[:, None, :], (1, 3, 1)) for _ in range(batch)]

@@ -18,6 +18,8 @@ Every rank
      `step()` refreshes from the param groups),
      --optimizer sgd trains with the reference's default optimizer instead (train.py:123-124: SGD with momentum, step_amd.FlatSGD) --
      same arenas, same exchange, same captured step,
+     --dropout P trains with the heads' dropout (the reference's recipe: 0.3) on the device-side generator: the captured step draws new masks
+     on every replay (`step_amd.Dropout`, `step_amd.rng`); --rng-seed S seeds it, rank r with S + r,
   6. rank 0 prints one JSON line per --log-every iterations and a final summary (loss, ms per iteration, clips/s of the whole job).
 
 Data: synthetic AVA-shaped clips [B,36,3,400,400] and fixed anchor tubes (there is no dataset in this repository; the reference's
@@ -52,6 +54,10 @@ def main():
     ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd (config.py:55)")
     ap.add_argument("--weight-decay", type=float, default=None,
                     help="every group's weight decay (default: the optimizer's own -- 0 for adam, 1e-7 for sgd as config.py:57)")
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="drop probability of the heads' three dropout sites (the reference's recipe: 0.3, scripts/train_step.sh:41); masks come from "
+                         "the device-side generator (step_amd.Dropout), fresh on every replay of the captured step")
+    ap.add_argument("--rng-seed", type=int, default=0, help="seed S of the dropout generator; rank r seeds S + r, so data-parallel ranks draw different masks")
     ap.add_argument("--warmup-iters", type=int, default=3, help="eager iterations before the capture (caches, workspaces, communicator)")
     ap.add_argument("--lr-decay-every", type=int, default=0, help="> 0: multiply every group's lr by 0.1 every that many iterations (scheduler stand-in)")
     ap.add_argument("--no-graph", action="store_true")
@@ -93,10 +99,11 @@ def main():
         import numpy as np
         random.seed(1000 + rank)                                 # (the selection draws from the reference's two host RNG streams)
         np.random.seed(1000 + rank)
-        w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=graphed, optimizer=a.optimizer)
+        w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=graphed, optimizer=a.optimizer,
+                                        dropout=a.dropout, rng_seed=a.rng_seed + rank)
     else:
         w = workloads.C4TrainStep(dev, batch=len(mine), tubes_per_clip=a.tubes, seed=123 + rank, dtype=tdt, capturable=graphed,
-                                  optimizer=a.optimizer)
+                                  optimizer=a.optimizer, dropout=a.dropout, rng_seed=a.rng_seed + rank)
     for g in w.opt.param_groups:
         g["lr"] = a.lr
         if a.optimizer == "sgd":
@@ -179,6 +186,7 @@ def main():
                           "launch": ("hipGraph replay (%s)" % w.graph_mode) if w.graph is not None else "eager",
                           "gradient_exchange": _exchange_label(w, world),
                           "feed": a.feed + ("+augment" if a.augment else ""), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
+                          "dropout": a.dropout, "rng_offset": w.rng.offset(),
                           **({"adam_steps": w.opt.step_count} if a.optimizer == "adam" else {})}), flush=True)
     if world > 1:
         torch.distributed.barrier()
