@@ -52,8 +52,7 @@ enum {
     STEP_E_ALIGN = -5
 };
 
-/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (40: step_dropout_forward /
- * step_dropout_backward / step_rng_words). */
+/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (41: step_select_train). */
 STEP_API const char* step_version(void);
 STEP_API int step_abi_version(void);
 
@@ -806,6 +805,68 @@ STEP_API int step_select_prepare(const float* prob, const float* loc, const floa
                                  int NC, const int32_t* clip_of, const float* gt_mid, const int32_t* gt_count, int Gmax,
                                  float width, float height, float* mean_prob, float* vloc, float* vfirst, float* vlast,
                                  float* iou, step_stream_t stream);
+
+/* Training sample selection, the whole rule on the device: what train_select / select_proposals (utils/utils.py:135-423) do for ONE
+ * training step and all clips after the per-tube arithmetic -- candidate ranking, the greedy and the drawn positives, the drawn
+ * negatives, target assembly, padding to static shapes -- with the draws taken from the device-side generator of step_dropout_forward.
+ * Nothing on the path synchronises with the host, so the training iteration can be captured as one graph; the host path
+ * (step_amd/selection.py train_select) stays the one that reproduces the reference's draws.
+ *
+ * Launches: one workgroup per clip; behind it on the same stream a one-thread kernel that sums counts into inv and increments the
+ * generator's offset by 1 (also when B == 0: the call counts).
+ *
+ * Inputs (dense fp32 unless noted).  cand [N,Tc,4]; cand_first / cand_last [N,Tw,4] (both NULL unless the tubes grow at this step);
+ * score [N,NC] the frame-averaged class scores (NULL at step 1); iou [N,Gmax] as step_select_prepare writes it (NULL: the kernel takes
+ * the box IoU of cand's frame Tc / 2, unclamped, with gt's box at `mid`, in step_select_prepare's fp32 operation order -- step 1, whose
+ * candidates are the initial tubes); clip_start [B+1] int32, clip b owns tubes clip_start[b] .. clip_start[b+1]-1, at most Amax of them
+ * (Amax: the caller's bound on the tubes of one clip; further tubes are ignored); gt [B,Gmax,F,4+NC] (box, class labels per frame),
+ * gt_count [B] int32; pad_tubes [B,Tout,4]; rng_state {seed, offset}.  mid / before / after: frame indices into F (before = after = -1:
+ * no neighbour targets); sampling 0 uniform, 1 random, 2 softmax.  Scores and IoUs are taken to be finite.
+ * Outputs (static shapes, Tout = Tc, or Tc + 2 Tw when growing with rows cat(first, cand, last)):
+ *   sel [B*budget,Tout,5]   column 0 = b * Tout + t, columns 1-4 the box        tgt [B*budget,3,6+NC]  rows before | centre | after:
+ *   mask [B*budget]         1 for a real row, 0 for a padded slot                                      [x1,y1,x2,y2, cls flag, reg flag, labels]
+ *   inv [1]                 1 / (max(real rows of all clips, 1) * NC)           counts [B,2] int32     positives, negatives
+ *   Clip b's real rows are its positives, then its negatives; unused slots get pad_tubes[b], all-zero targets and mask 0.
+ *
+ * The rule, per clip (A tubes, G = gt_count[b] ground truths; G = 0 or A = 0 selects nothing).
+ * Candidates, in order.  score == NULL: all tubes in index order, candidate score = max_g iou[g,a].  Otherwise keep = topk > 0 ?
+ *   2 * (topk / NC) : A; tube a QUALIFIES in class c when fewer than keep tubes a' have s[a',c] > s[a,c] || (s[a',c] == s[a,c] && a' < a);
+ *   best(a) = max of s[a,c] over the classes a qualifies in; the candidates are the tubes with a qualifying class, ordered by best
+ *   descending, equal values by lower index first, truncated to topk when topk > 0; candidate score = best.  (The reference's order,
+ *   utils.py:179-214, whenever no two compared scores are equal.)  From here on an index is a POSITION in this list, and iou[g,k] is the
+ *   table's entry for the tube at position k.
+ * First positives.  G rounds: the ground truth g with the largest remaining row maximum max_k iou[g,k] (first on ties) takes the untaken
+ *   candidate with the largest iou[g,k], equal values by the HIGHER position (a stable ascending sort read backwards); that candidate is
+ *   taken, (g, k) is appended and row g counts as -1 from then on; with every candidate taken the round takes nothing.  More than
+ *   max_pos_num collected: shuffle as random.shuffle does -- for i = len-1 down to 1: j = floor(u * (i+1)), swap entries i and j, draw
+ *   (phase 0, k = i) -- and keep the first max_pos_num (the others stay taken).
+ * More positives.  above = the untaken candidates, ascending, with iou[g,k] > cls_thresh for some g.  Non-empty and pos shorter than
+ *   max_pos_num: min(len(above), max_pos_num - len(pos)) draws without replacement, draw d (phase 1, k = d): j = floor(u * remaining), the
+ *   j-th remaining element in ascending order; it is appended with its owner, the first arg-max_g iou[g,k].  All of above is then taken.
+ * Negatives.  rest = the untaken candidates, ascending; weights in double from the fp32 candidate score: uniform score + 1e-6, random 1,
+ *   softmax exp(score).  min(len(pos) * neg_ratio, len(rest)) sequential draws without replacement, draw d (phase 2, k = d): total = the
+ *   sum of the remaining weights in ascending order, t = u * total, take the first remaining element whose running sum exceeds t, or the
+ *   last remaining one if none does; owner = first arg-max_g iou[g,k].
+ * Targets (utils.py:259-335).  Centre row: positives get the owner's box and labels at `mid` and both flags; negatives get box, labels
+ *   and the regression flag only if iou[owner,k] >= reg_thresh.  Neighbour rows (before >= 0), positives only: the owner's box and labels
+ *   at `before` / `after`, regression flag set iff ((x1 + y1) + x2) + y2 > 0; zeros for negatives.
+ * Draws.  {seed, offset} are read on the device.  Draw (b, phase, k) is Philox block (b << 20) | (phase << 16) | k at that offset (key and
+ *   counter as for step_dropout_forward); u = ((w0 << 21) | (w1 >> 11)) * 2^-53 from its words 0 and 1; every floor(u * n) is clamped to
+ *   n - 1.  A selection is a pure function of (seed, offset, inputs), and every launch owns its offset, so the stream is shared with the
+ *   dropout passes without collisions.  The draws are NOT the reference's (random / numpy.random on the host).
+ *
+ * Cost.  The limits (1024 tubes per clip, 64 ground truths) are what the LDS tables hold, not a size the kernel is fast at: the per-class
+ * ranks count, for each tube and class, the tubes ahead of it -- O(A^2 * NC) reads of `score` per clip by one workgroup, about 6e7 at
+ * A = 1024, NC = 60 (milliseconds), against ~7e4 at the training recipe's 34 tubes.  The kernel is sized for tens of tubes per clip.
+ *
+ * Errors: budget < max_pos_num * (1 + neg_ratio) -> STEP_E_SHAPE (with the bound the selection can never overflow its slots: pos <=
+ * max_pos_num, neg <= pos * neg_ratio); topk > 0 && topk < NC -> STEP_E_SHAPE; Amax > 1024 or Gmax > 64 -> STEP_E_UNSUPPORTED. */
+STEP_API int step_select_train(const float* cand, const float* cand_first, const float* cand_last, const float* score, const float* iou,
+                               int N, int Tc, int Tw, int NC, const int32_t* clip_start, int B, int Amax, const float* gt,
+                               const int32_t* gt_count, int Gmax, int F, const float* pad_tubes, unsigned long long* rng_state, int mid,
+                               int before, int after, int topk, float cls_thresh, float reg_thresh, int max_pos_num, int neg_ratio,
+                               int sampling, int budget, float* sel, float* tgt, float* mask, float* inv, int32_t* counts,
+                               step_stream_t stream);
 
 #ifdef __cplusplus
 }

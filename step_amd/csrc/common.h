@@ -219,6 +219,19 @@ __device__ inline void lane32_swap(unsigned& x, unsigned& y) {
 }
 #endif
 
+// ---- Philox4x32-10 (Random123): the counter-based stream of step_dropout_forward (head.hip) and step_select_train (tube.hip);
+// include/step_amd.h has the stream's definition
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // ---- launch helper -------------------------------------------------------------------------
 #ifdef STEP_EMUL
 #define STEP_LAUNCH(kernel, grid, block, stream, ...) \

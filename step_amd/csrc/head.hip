@@ -187,18 +187,8 @@ __global__ __launch_bounds__(256) void head_outputs_bwd_kernel(HeadParams p) {
 // A counter-based stream, so that a mask is a pure function of (seed, offset, element index): Philox4x32-10 (Random123), key = the
 // seed's two halves, counter = (blk_lo, blk_hi, offset_lo, offset_hi) with blk = e >> 2, element e takes word e & 3 of its block.
 // {seed, offset} live on the device; a one-thread kernel behind the pass bumps the offset, so a replayed graph draws a fresh mask on
-// every replay (the pattern of step_sgd_flat_dev's counter).  include/step_amd.h has the definition in full.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// every replay (the pattern of step_sgd_flat_dev's counter).  include/step_amd.h has the definition in full; philox4x32_10 itself is in
+// common.h (step_select_train in tube.hip draws from the same stream).
 template <typename T> union vec16 { u32x4 q; T e[elem<T>::VEC]; };
 
 // round_to_dtype(float(x) * scale), scale > 0.  For fp16 the compiler folds the widening, the multiply and the narrowing into one

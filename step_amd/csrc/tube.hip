@@ -118,6 +118,292 @@ __global__ void select_prepare_kernel(SelectParams p) {
     }
 }
 
+
+// ---- training sample selection, the whole rule on the device (step_select_train; include/step_amd.h has the contract) -----------------
+// What train_select / select_proposals (utils/utils.py:135-423) do after the per-tube arithmetic, for one training step: one workgroup
+// per clip.  The rankings, the per-candidate reductions over the ground truths, the greedy picks' scans and the output rows are spread
+// over the workgroup; the shuffle and the sequential draws without replacement run on thread 0 out of LDS.  The draws come from the
+// dropout generator's stream ({seed, offset} on the device), so a replayed graph selects anew on every replay.
+constexpr int SEL_MAX_TUBES = 1024;                       // tubes per clip (LDS tables below)
+constexpr int SEL_MAX_GT = 64;
+
+struct SelTrainParams {
+    const float* cand; const float* cfirst; const float* clast; const float* score; const float* iou; const int32_t* clip_start;
+    const float* gt; const int32_t* gt_count; const float* pad; const unsigned long long* rng;
+    float* sel; float* tgt; float* mask; int32_t* counts;
+    int N, B, Tc, Tw, NC, Gmax, F, Amax, mid, before, after, topk, max_pos, neg_ratio, sampling, budget;
+    float cls_thresh, reg_thresh;
+};
+
+// iou[g][tube n]: the table handed in, or (step 1) the box IoU of the tube's middle frame with ground truth g at `mid`, the arithmetic of
+// select_prepare_kernel without the clamp
+__device__ __forceinline__ float sel_iou(const SelTrainParams& p, int b, int g, int n) {
+    if (p.iou) return p.iou[(size_t)n * p.Gmax + g];
+    const float* a = p.cand + ((size_t)n * p.Tc + p.Tc / 2) * 4;
+    const float* q = p.gt + (((size_t)b * p.Gmax + g) * p.F + p.mid) * (4 + p.NC);
+    const bool live = (((q[0] + q[1]) + q[2]) + q[3]) != 0.0f && (((a[0] + a[1]) + a[2]) + a[3]) != 0.0f;
+    if (!live) return 0.0f;
+    const float iw = fmaxf(fminf(q[2], a[2]) - fmaxf(q[0], a[0]), 0.0f);
+    const float ih = fmaxf(fminf(q[3], a[3]) - fmaxf(q[1], a[1]), 0.0f);
+    const float inter = (iw > 0.0f && ih > 0.0f) ? iw * ih : 0.0f;
+    const float uni = (q[2] - q[0]) * (q[3] - q[1]) + (a[2] - a[0]) * (a[3] - a[1]) - inter;
+    return inter / uni;
+}
+
+// draw (b, phase, k): u in [0, 1) with 53 bits from words 0 and 1 of block (b << 20 | phase << 16 | k) at the state's offset
+__device__ __forceinline__ double sel_draw(unsigned long long seed, unsigned long long off, int b, int phase, int k) {
+    const unsigned long long blk = ((unsigned long long)b << 20) | ((unsigned long long)phase << 16) | (unsigned long long)k;
+    unsigned w[4];
+    philox4x32_10((unsigned)blk, (unsigned)(blk >> 32), (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
+    return (double)(((unsigned long long)w[0] << 21) | ((unsigned long long)w[1] >> 11)) * (1.0 / 9007199254740992.0);
+}
+
+__device__ __forceinline__ int sel_floor(double u, int n) {               // floor(u * n), clamped to n - 1
+    const int j = (int)(u * (double)n);
+    return j < n - 1 ? j : n - 1;
+}
+
+enum { SEL_TAKEN = 1, SEL_ABOVE = 2, SEL_DRAWN = 4 };
+
+__global__ __launch_bounds__(256) void select_train_kernel(SelTrainParams p) {
+    __shared__ int s_cidx[SEL_MAX_TUBES];                       // candidate position -> tube of the clip
+    __shared__ float s_cscore[SEL_MAX_TUBES];                   // candidate's score
+    __shared__ float s_cmax[SEL_MAX_TUBES];                     // max over the ground truths of iou[g][candidate] ...
+    __shared__ unsigned char s_cown[SEL_MAX_TUBES];             // ... and the first ground truth that reaches it (the owner)
+    __shared__ unsigned char s_flag[SEL_MAX_TUBES];
+    __shared__ float s_best[SEL_MAX_TUBES];                     // per tube: best qualifying class score
+    __shared__ unsigned char s_qual[SEL_MAX_TUBES];
+    __shared__ double s_w[SEL_MAX_TUBES];                       // negative-sampling weight per candidate
+    __shared__ unsigned short s_rowk[SEL_MAX_TUBES];            // selected rows: candidate position, owner
+    __shared__ unsigned char s_rowg[SEL_MAX_TUBES];
+    __shared__ float s_rowmax[SEL_MAX_GT];
+    __shared__ float s_redv[256];
+    __shared__ int s_redk[256];
+    __shared__ int s_n[4];                                      // candidates, positives, rows, the greedy loop's current ground truth
+
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const int start = p.clip_start[b];
+    int A = p.clip_start[b + 1] - start;
+    if (A > p.Amax) A = p.Amax;
+    if (start < 0 || A < 0 || (long long)start + A > p.N) A = 0;           // (a table that does not describe [0, N): select nothing)
+    int G = p.gt_count[b];
+    G = G < 0 ? 0 : G > p.Gmax ? p.Gmax : G;
+    if (A == 0) G = 0;
+    const int Tout = p.cfirst ? p.Tc + 2 * p.Tw : p.Tc;
+    const int TW = 6 + p.NC;
+
+    if (G > 0) {
+        // ---- the candidates, in order
+        if (p.score) {
+            const int keep = p.topk > 0 ? 2 * (p.topk / p.NC) : A;
+            for (int a = tid; a < A; a += nt) {
+                bool any = false;
+                float best = 0.0f;
+                for (int c = 0; c < p.NC; ++c) {
+                    const float s = p.score[(size_t)(start + a) * p.NC + c];
+                    if (any && !(s > best)) continue;                       // cannot raise best: the class need not be ranked
+                    int ahead = 0;
+                    for (int o = 0; o < A && ahead < keep; ++o) {
+                        const float so = p.score[(size_t)(start + o) * p.NC + c];
+                        ahead += (so > s || (so == s && o < a)) ? 1 : 0;
+                    }
+                    if (ahead < keep) { best = s; any = true; }
+                }
+                s_qual[a] = any ? 1 : 0;
+                s_best[a] = best;
+            }
+            __syncthreads();
+            for (int a = tid; a < A; a += nt) {
+                if (!s_qual[a]) continue;
+                const float s = s_best[a];
+                int rank = 0;
+                for (int o = 0; o < A; ++o) rank += (s_qual[o] && (s_best[o] > s || (s_best[o] == s && o < a))) ? 1 : 0;
+                if (p.topk <= 0 || rank < p.topk) { s_cidx[rank] = a; s_cscore[rank] = s; }
+            }
+            if (tid == 0) {
+                int nq = 0;
+                for (int a = 0; a < A; ++a) nq += s_qual[a];
+                s_n[0] = (p.topk > 0 && nq > p.topk) ? p.topk : nq;
+            }
+        } else {
+            for (int a = tid; a < A; a += nt) s_cidx[a] = a;
+            if (tid == 0) s_n[0] = A;
+        }
+        __syncthreads();
+        const int Ac = s_n[0];
+        // ---- per candidate: maximum over the ground truths, its owner, the cls_thresh flag, the sampling weight; per ground truth: row maximum
+        for (int k = tid; k < Ac; k += nt) {
+            const int n = start + s_cidx[k];
+            float m = sel_iou(p, b, 0, n);
+            int own = 0;
+            bool above = m > p.cls_thresh;
+            for (int g = 1; g < G; ++g) {
+                const float v = sel_iou(p, b, g, n);
+                if (v > m) { m = v; own = g; }
+                above = above || v > p.cls_thresh;
+            }
+            s_cmax[k] = m; s_cown[k] = (unsigned char)own; s_flag[k] = above ? SEL_ABOVE : 0;
+            if (!p.score) s_cscore[k] = m;
+            const float sc = s_cscore[k];
+            s_w[k] = p.sampling == 0 ? (double)sc + 1e-6 : p.sampling == 1 ? 1.0 : exp((double)sc);
+        }
+        for (int g = tid; g < G; g += nt) {
+            float m = sel_iou(p, b, g, start + s_cidx[0]);
+            for (int k = 1; k < Ac; ++k) m = fmaxf(m, sel_iou(p, b, g, start + s_cidx[k]));
+            s_rowmax[g] = m;
+        }
+        if (tid == 0) { s_n[1] = 0; s_n[3] = 0; }
+        __syncthreads();
+        // ---- first positives: G rounds, the ground truth with the largest remaining row maximum takes its best untaken candidate
+        if (tid == 0) {
+            int g = 0;
+            for (int h = 1; h < G; ++h) if (s_rowmax[h] > s_rowmax[g]) g = h;
+            s_n[3] = g;
+        }
+        __syncthreads();
+        for (int round = 0; round < G; ++round) {
+            const int g = s_n[3];
+            float bv = 0.0f;
+            int bk = -1;
+            for (int k = tid; k < Ac; k += nt) {
+                if (s_flag[k] & SEL_TAKEN) continue;
+                const float v = sel_iou(p, b, g, start + s_cidx[k]);
+                if (bk < 0 || v >= bv) { bv = v; bk = k; }                 // equal values: the higher candidate index
+            }
+            s_redv[tid] = bv; s_redk[tid] = bk;
+            __syncthreads();
+            if (tid == 0) {
+                for (int t = 1; t < nt; ++t) {
+                    const int k = s_redk[t];
+                    if (k >= 0 && (bk < 0 || s_redv[t] > bv || (s_redv[t] == bv && k > bk))) { bv = s_redv[t]; bk = k; }
+                }
+                if (bk >= 0) {
+                    s_flag[bk] |= SEL_TAKEN;
+                    s_rowk[s_n[1]] = (unsigned short)bk; s_rowg[s_n[1]] = (unsigned char)g;
+                    s_n[1] += 1;
+                    s_rowmax[g] = -1.0f;
+                }
+                int ng = 0;
+                for (int h = 1; h < G; ++h) if (s_rowmax[h] > s_rowmax[ng]) ng = h;
+                s_n[3] = ng;
+            }
+            __syncthreads();
+        }
+        // ---- the draws: sequential by definition
+        if (tid == 0) {
+            const unsigned long long seed = p.rng[0], off = p.rng[1];
+            int P = s_n[1];
+            if (P > p.max_pos) {                                           // random.shuffle, then the first max_pos_num
+                for (int i = P - 1; i >= 1; --i) {
+                    const int j = sel_floor(sel_draw(seed, off, b, 0, i), i + 1);
+                    const unsigned short tk = s_rowk[i]; s_rowk[i] = s_rowk[j]; s_rowk[j] = tk;
+                    const unsigned char tg = s_rowg[i]; s_rowg[i] = s_rowg[j]; s_rowg[j] = tg;
+                }
+                P = p.max_pos;
+            }
+            int nab = 0;
+            for (int k = 0; k < Ac; ++k) nab += (s_flag[k] & (SEL_ABOVE | SEL_TAKEN)) == SEL_ABOVE ? 1 : 0;
+            if (nab > 0 && P < p.max_pos) {                                // more positives: uniform, without replacement
+                const int nd = nab < p.max_pos - P ? nab : p.max_pos - P;
+                for (int d = 0; d < nd; ++d) {
+                    int j = sel_floor(sel_draw(seed, off, b, 1, d), nab - d);
+                    int k = 0;
+                    for (; k < Ac; ++k) {                                  // the j-th remaining one, ascending
+                        if ((s_flag[k] & (SEL_ABOVE | SEL_TAKEN | SEL_DRAWN)) != SEL_ABOVE) continue;
+                        if (j == 0) break;
+                        --j;
+                    }
+                    if (k >= Ac) break;                                    // (cannot happen: j < the number remaining)
+                    s_flag[k] |= SEL_DRAWN;
+                    s_rowk[P] = (unsigned short)k; s_rowg[P] = s_cown[k];
+                    ++P;
+                }
+            }
+            int nrest = 0;
+            for (int k = 0; k < Ac; ++k) {
+                if (s_flag[k] & SEL_ABOVE) s_flag[k] |= SEL_TAKEN;       // never a negative: they overlap some ground truth
+                s_flag[k] &= ~SEL_DRAWN;
+                nrest += (s_flag[k] & SEL_TAKEN) ? 0 : 1;
+            }
+            int R = P;
+            const long long want = (long long)P * p.neg_ratio;
+            const int nneg = want < nrest ? (int)want : nrest;
+            for (int d = 0; d < nneg; ++d) {                               // negatives: weighted, without replacement, sequential
+                double total = 0.0;
+                for (int k = 0; k < Ac; ++k) if (!(s_flag[k] & (SEL_TAKEN | SEL_DRAWN))) total += s_w[k];
+                const double t = sel_draw(seed, off, b, 2, d) * total;
+                double run = 0.0;
+                int pick = -1;
+                for (int k = 0; k < Ac; ++k) {
+                    if (s_flag[k] & (SEL_TAKEN | SEL_DRAWN)) continue;
+                    pick = k;
+                    run += s_w[k];
+                    if (run > t) break;
+                }
+                if (pick < 0) break;                                       // (cannot happen: nneg <= the number remaining)
+                s_flag[pick] |= SEL_DRAWN;
+                s_rowk[R] = (unsigned short)pick; s_rowg[R] = s_cown[pick];
+                ++R;
+            }
+            s_n[1] = P; s_n[2] = R;
+        }
+    } else if (tid == 0) {
+        s_n[1] = 0; s_n[2] = 0;
+    }
+    __syncthreads();
+    const int P = s_n[1], R = s_n[2];
+    if (tid == 0) { p.counts[2 * b] = P; p.counts[2 * b + 1] = R - P; }
+    // ---- the clip's `budget` output rows: real rows (positives, then negatives), then the padded slots
+    const size_t row0 = (size_t)b * p.budget;
+    for (int r = tid; r < p.budget; r += nt) p.mask[row0 + r] = r < R ? 1.0f : 0.0f;
+    for (int i = tid; i < p.budget * Tout; i += nt) {
+        const int r = i / Tout, t = i % Tout;
+        const float* src;
+        if (r < R) {
+            const size_t n = (size_t)start + s_cidx[s_rowk[r]];
+            if (!p.cfirst) src = p.cand + (n * p.Tc + t) * 4;
+            else if (t < p.Tw) src = p.cfirst + (n * p.Tw + t) * 4;
+            else if (t < p.Tw + p.Tc) src = p.cand + (n * p.Tc + (t - p.Tw)) * 4;
+            else src = p.clast + (n * p.Tw + (t - p.Tw - p.Tc)) * 4;
+        } else {
+            src = p.pad + ((size_t)b * Tout + t) * 4;
+        }
+        float* dst = p.sel + ((row0 + r) * Tout + t) * 5;
+        dst[0] = (float)(b * Tout + t);
+        dst[1] = src[0]; dst[2] = src[1]; dst[3] = src[2]; dst[4] = src[3];
+    }
+    for (int i = tid; i < p.budget * 3 * TW; i += nt) {
+        const int r = i / (3 * TW), row = (i / TW) % 3, j = i % TW;
+        float v = 0.0f;
+        if (r < R) {
+            const bool pos = r < P;
+            const int frame = row == 1 ? p.mid : row == 0 ? p.before : p.after;
+            const float* q = p.gt + (((size_t)b * p.Gmax + s_rowg[r]) * p.F + (frame < 0 ? 0 : frame)) * (4 + p.NC);
+            if (row == 1) {
+                const bool reg = pos || s_cmax[s_rowk[r]] >= p.reg_thresh;    // (a negative's owner is its arg-max ground truth)
+                if (j == 4) v = pos ? 1.0f : 0.0f;
+                else if (j == 5) v = reg ? 1.0f : 0.0f;
+                else if (reg) v = j < 4 ? q[j] : q[j - 2];
+            } else if (pos && frame >= 0) {
+                if (j == 4) v = 0.0f;
+                else if (j == 5) v = (((q[0] + q[1]) + q[2]) + q[3]) > 0.0f ? 1.0f : 0.0f;    // an all-zero box is padding: no regression target
+                else v = j < 4 ? q[j] : q[j - 2];
+            }
+        }
+        p.tgt[(row0 + r) * 3 * TW + i % (3 * TW)] = v;
+    }
+}
+
+// behind the selection: inv = 1 / (max(real rows, 1) * NC), and the call has used its offset
+__global__ __launch_bounds__(64) void select_finish_kernel(const int32_t* counts, int B, int NC, float* inv, unsigned long long* rng) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    long long rows = 0;
+    for (int b = 0; b < B; ++b) rows += (long long)counts[2 * b] + counts[2 * b + 1];
+    if (rows < 1) rows = 1;
+    inv[0] = (float)(1.0 / (double)(rows * NC));
+    rng[1] += 1ull;
+}
+
 }  // namespace step
 
 using namespace step;
@@ -134,6 +420,38 @@ extern "C" int step_select_prepare(const float* prob, const float* loc, const fl
     p.mean_prob = mean_prob; p.vloc = vloc; p.vfirst = vfirst; p.vlast = vlast; p.iou = iou;
     p.N = N; p.T = T; p.Tw = Tw; p.NC = NC; p.Gmax = Gmax; p.width = width; p.height = height;
     STEP_LAUNCH(select_prepare_kernel, dim3((unsigned)N), dim3(64), stream, p);
+    return STEP_LAUNCH_CHECK();
+}
+
+extern "C" int step_select_train(const float* cand, const float* cand_first, const float* cand_last, const float* score, const float* iou,
+                                 int N, int Tc, int Tw, int NC, const int32_t* clip_start, int B, int Amax, const float* gt,
+                                 const int32_t* gt_count, int Gmax, int F, const float* pad_tubes, unsigned long long* rng_state, int mid,
+                                 int before, int after, int topk, float cls_thresh, float reg_thresh, int max_pos_num, int neg_ratio,
+                                 int sampling, int budget, float* sel, float* tgt, float* mask, float* inv, int32_t* counts,
+                                 step_stream_t stream) {
+    if (N < 0 || B < 0 || Tc <= 0 || Tw < 0 || NC <= 0 || Gmax < 0 || F <= 0 || Amax < 0 || budget <= 0) return STEP_E_SHAPE;
+    if (mid < 0 || mid >= F || (before < 0) != (after < 0) || before >= F || after >= F) return STEP_E_SHAPE;
+    if (max_pos_num < 0 || neg_ratio < 0 || sampling < 0 || sampling > 2) return STEP_E_SHAPE;
+    if ((long long)budget < (long long)max_pos_num * (1 + (long long)neg_ratio)) return STEP_E_SHAPE;      // the slots can then never overflow
+    if (topk > 0 && topk < NC) return STEP_E_SHAPE;
+    if (Amax > SEL_MAX_TUBES || Gmax > SEL_MAX_GT) return STEP_E_UNSUPPORTED;
+    if ((long long)B * budget * (Tc + 2 * Tw > 3 * (6 + NC) ? Tc + 2 * Tw : 3 * (6 + NC)) > 0x7fffffffLL) return STEP_E_UNSUPPORTED;
+    if (!rng_state || !inv || (B > 0 && !counts)) return STEP_E_NULL;
+    if ((uintptr_t)rng_state & 7) return STEP_E_ALIGN;
+    if (B > 0) {
+        if (!clip_start || !gt_count || !pad_tubes || !sel || !tgt || !mask || (Gmax && !gt) || (N > 0 && !cand)) return STEP_E_NULL;
+        if ((cand_first != nullptr) != (cand_last != nullptr) || (cand_first && Tw <= 0)) return STEP_E_NULL;
+        SelTrainParams p;
+        p.cand = cand; p.cfirst = cand_first; p.clast = cand_last; p.score = score; p.iou = iou; p.clip_start = clip_start;
+        p.gt = gt; p.gt_count = gt_count; p.pad = pad_tubes; p.rng = rng_state;
+        p.sel = sel; p.tgt = tgt; p.mask = mask; p.counts = counts;
+        p.N = N; p.B = B; p.Tc = Tc; p.Tw = Tw; p.NC = NC; p.Gmax = Gmax; p.F = F; p.Amax = Amax; p.mid = mid; p.before = before; p.after = after;
+        p.topk = topk; p.max_pos = max_pos_num; p.neg_ratio = neg_ratio; p.sampling = sampling; p.budget = budget;
+        p.cls_thresh = cls_thresh; p.reg_thresh = reg_thresh;
+        const int threads = Amax <= 64 ? 64 : Amax <= 128 ? 128 : 256;
+        STEP_LAUNCH(select_train_kernel, dim3((unsigned)B), dim3((unsigned)threads), stream, p);
+    }
+    STEP_LAUNCH(select_finish_kernel, dim3(1), dim3(64), stream, (const int32_t*)counts, B, NC, inv, rng_state);      // (also for B == 0: the call counts)
     return STEP_LAUNCH_CHECK();
 }
 

@@ -1161,6 +1161,57 @@ def select_prepare(prob, loc, first, last, clip_of, gt_mid, gt_count, width, hei
     return mean_prob, vloc, vfirst, vlast, iou
 
 
+SAMPLING = {"uniform": 0, "random": 1, "softmax": 2}
+
+
+def select_train(cand, cand_first, cand_last, score, iou, clip_start, max_tubes, gt, gt_count, pad_tubes, rng, mid, before, after, topk,
+                 cls_thresh, reg_thresh, max_pos_num, neg_ratio, sampling, budget, out=None):
+    """step_select_train: one training step's proposal selection for all clips on the device (include/step_amd.h has the rule).
+    cand [N,Tc,4], cand_first / cand_last [N,Tw,4] | None (growing tubes), score [N,NC] | None (step 1), iou [N,Gmax] | None (the kernel
+    computes it), clip_start [B+1] int32, max_tubes = the most tubes any clip has (host integer), gt [B,Gmax,F,4+NC], gt_count [B] int32,
+    pad_tubes [B,Tout,4], rng a step_amd.rng.DeviceRNG (its offset advances by one on the device), sampling "uniform" | "random" |
+    "softmax".  -> (sel [B*budget,Tout,5], tgt [B*budget,3,6+NC], mask [B*budget,1], inv [1], counts [B,2] int32); out = such a tuple
+    writes into the caller's (static) buffers.  No host synchronisation."""
+    L = _lib.lib()
+    if sampling not in SAMPLING:
+        raise NotImplementedError(sampling)
+    dev = cand.device
+    tensors = {"cand": cand, "cand_first": cand_first, "cand_last": cand_last, "score": score, "iou": iou, "gt": gt, "pad_tubes": pad_tubes}
+    for name, t in tensors.items():
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
+            raise RuntimeError("step_amd: select_train wants %s as a contiguous float32 tensor on %s" % (name, dev))
+    for name, t in (("clip_start", clip_start), ("gt_count", gt_count)):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError("step_amd: select_train wants %s as a contiguous int32 tensor on %s" % (name, dev))
+    if (cand_first is None) != (cand_last is None):
+        raise RuntimeError("step_amd: select_train wants cand_first and cand_last together")
+    N, Tc, _ = cand.shape
+    B = clip_start.numel() - 1
+    Tw = cand_first.shape[1] if cand_first is not None else 0
+    Tout = Tc + 2 * Tw
+    if gt.dim() != 4 or gt.shape[0] != B or tuple(gt_count.shape) != (B,):
+        raise RuntimeError("step_amd: select_train wants gt [B=%d,Gmax,F,4+NC] and gt_count [B], got %s, %s" % (B, tuple(gt.shape), tuple(gt_count.shape)))
+    Gmax, F, NC = gt.shape[1], gt.shape[2], gt.shape[3] - 4
+    want = {"cand_first": (N, Tw, 4), "cand_last": (N, Tw, 4), "score": (N, NC), "iou": (N, Gmax), "pad_tubes": (B, Tout, 4)}
+    for name, shape in want.items():
+        if tensors[name] is not None and tuple(tensors[name].shape) != shape:
+            raise RuntimeError("step_amd: select_train wants %s %s, got %s" % (name, shape, tuple(tensors[name].shape)))
+    K = B * int(budget)
+    shapes = ((K, Tout, 5), (K, 3, 6 + NC), (K, 1), (1,), (B, 2))
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=torch.int32 if k == 4 else torch.float32, device=dev) for k, sh in enumerate(shapes))
+    for k, (t, sh) in enumerate(zip(out, shapes)):
+        if tuple(t.shape) != sh or t.dtype != (torch.int32 if k == 4 else torch.float32) or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError("step_amd: select_train output %d wants shape %s, got %s %s" % (k, sh, tuple(t.shape), t.dtype))
+    sel, tgt, mask, inv, counts = out
+    _capi.check(L.step_select_train(_lib.dptr(cand), _lib.dptr(cand_first), _lib.dptr(cand_last), _lib.dptr(score), _lib.dptr(iou), N, Tc, Tw, NC,
+                                    _lib.dptr(clip_start), B, int(max_tubes), _lib.dptr(gt), _lib.dptr(gt_count), Gmax, F, _lib.dptr(pad_tubes),
+                                    _lib.dptr(rng.state), int(mid), int(before), int(after), int(topk), float(cls_thresh), float(reg_thresh),
+                                    int(max_pos_num), int(neg_ratio), SAMPLING[sampling], int(budget), _lib.dptr(sel), _lib.dptr(tgt),
+                                    _lib.dptr(mask), _lib.dptr(inv), _lib.dptr(counts), _lib.stream_ptr(dev)), "step_select_train")
+    return out
+
+
 def _check_head_targets(name, dev, N, Tl, NC, tubes, targets):
     """The kernel hard-codes tubes [N,Tl,5] and targets [N,3,6+NC] (row 2 = 'last'): anything else would be read out of bounds and give
     wrong losses silently, where the torch chain it replaces (two_branch.py:294-333) would have raised."""

@@ -12,6 +12,10 @@ exactly, because they decide WHICH tubes are trained on:
   (tests/golden/selection_golden.npz was recorded from the reference).
 
 All three `temporal_mode`s ("predict": every shipped script; "extrapolate"; "mean") are supported, like step_amd/driver.py.
+
+`DeviceSelector` is the opt-in device form of the same rule (step_select_train, include/step_amd.h): no host synchronisation, static
+output shapes, draws from the device-side generator -- its own stream of draws and index-ordered ties, so it selects other tubes than
+the reference does under the reference's seeds.  `train_select` stays the default and the one that is pinned to the reference.
 """
 import random
 
@@ -263,3 +267,79 @@ def _prepare_on_device(history, targets, mid, predict, W, H):
         off += sizes[k]
         k += 1
     return res
+
+
+class DeviceSelector:
+    """train_select for a FIXED batch on the device: select(step, ...) is step_select_prepare (step > 1) + step_select_train on the
+    current stream, into static buffers -- nothing is copied to the host, nothing waits, so the calls can be recorded in a graph and the
+    draws (step_amd.rng.DeviceRNG: one offset per select()) change from replay to replay.  temporal_mode "predict" only."""
+
+    def __init__(self, args, batch, budget, device, rng):
+        import torch
+        if args.temporal_mode != "predict":
+            raise NotImplementedError("DeviceSelector: temporal_mode %r stays on the host path (selection.train_select)" % (args.temporal_mode,))
+        if args.selection_sampling not in ("uniform", "random", "softmax"):
+            raise NotImplementedError(args.selection_sampling)
+        if budget < args.max_pos_num * (1 + args.neg_ratio):
+            raise ValueError("DeviceSelector: budget %d is below max_pos_num * (1 + neg_ratio) = %d" % (budget, args.max_pos_num * (1 + args.neg_ratio)))
+        self.args, self.batch, self.budget, self.device, self.rng = args, int(batch), int(budget), torch.device(device), rng
+        K, nc = self.batch * self.budget, args.num_classes
+        self._layout = None                                      # (key, clip_of, most tubes of one clip) of the clip_start last seen
+        self._gt_mid = None                                      # (key, the ground truths' middle-frame boxes, dense)
+        self.out = {}
+        for i in range(1, args.max_iter + 1):
+            Tl = args.NUM_CHUNKS[i] * args.T
+            self.out[i] = (torch.zeros((K, Tl, 5), device=self.device), torch.zeros((K, 3, 6 + nc), device=self.device),
+                           torch.zeros((K, 1), device=self.device), torch.zeros((1,), device=self.device),
+                           torch.zeros((self.batch, 2), dtype=torch.int32, device=self.device))
+
+    @staticmethod
+    def _key(t):
+        return (t.data_ptr(), t._version, tuple(t.shape))
+
+    def _clip_layout(self, clip_start):
+        """(clip_of [N] int32, most tubes of one clip) of a clip_start table; read once per table (one small copy to the host) and again
+        whenever another tensor, or the same one written to since, is handed in -- so not inside a graph capture, where the first
+        select() of a table must not fall"""
+        import torch
+        key = self._key(clip_start)
+        if self._layout is None or self._layout[0] != key:
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("DeviceSelector: a new clip_start table cannot be read inside a graph capture (run select() once before capturing)")
+            nums = (clip_start[1:] - clip_start[:-1]).cpu().numpy().astype("int64")
+            clip_of = torch.as_tensor(np.repeat(np.arange(len(nums)), nums).astype(np.int32), device=self.device)
+            self._layout = (key, clip_of, int(nums.max()) if len(nums) else 0)
+        return self._layout[1], self._layout[2]
+
+    def _gt_mid_boxes(self, gt, mid):
+        """gt[:, :, mid, :4] as the dense tensor step_select_prepare reads; made again only when gt was replaced or written to"""
+        key = self._key(gt) + (mid,)
+        if self._gt_mid is None or self._gt_mid[0] != key:
+            self._gt_mid = (key, gt[:, :, mid, :4].contiguous())
+        return self._gt_mid[1]
+
+    def select(self, step, history, gt, gt_count, init_flat, clip_start, pad_tubes, max_tubes=None):
+        """history: the previous step's predictions (driver.inference_flat's entry; None at step 1); gt [B,Gmax,F,4+NC], gt_count [B]
+        int32, init_flat [N,T,4] the initial tubes (step 1's candidates), clip_start [B+1] int32, pad_tubes [B,Tl,4] of THIS step -- all
+        on the device.  max_tubes: the most tubes of one clip (default: read from clip_start the first time the table is seen).
+        -> (sel, tgt, mask, inv, counts), the step's static buffers."""
+        from . import ops
+        a = self.args
+        chunks, max_chunks = a.NUM_CHUNKS[step], a.NUM_CHUNKS[a.max_iter]
+        T = a.T
+        t_start = int((max_chunks - chunks) / 2) * T
+        mid = int(max_chunks / 2)
+        grow = (step - 1) in a.NUM_CHUNKS and a.NUM_CHUNKS[step] == a.NUM_CHUNKS[step - 1] + 2
+        grows_next = step < a.max_iter and a.NUM_CHUNKS[step + 1] == a.NUM_CHUNKS[step] + 2
+        before, after = (int((t_start - T) / T), int((t_start + chunks * T) / T)) if grows_next else (-1, -1)
+        clip_of, most = self._clip_layout(clip_start)
+        if step == 1:
+            cand, first, last, score, iou = init_flat, None, None, None, None
+        else:
+            score, cand, first, last, iou = ops.select_prepare(history["pred_prob"], history["pred_loc"], history["pred_first_loc"] if grow else None,
+                                                               history["pred_last_loc"] if grow else None, clip_of, self._gt_mid_boxes(gt, mid),
+                                                               gt_count, float(a.image_size[0]), float(a.image_size[1]))
+        n_max = int(max_tubes) if max_tubes is not None else most
+        return ops.select_train(cand, first, last, score, iou, clip_start, n_max, gt, gt_count, pad_tubes, self.rng, mid, before, after, a.topk,
+                                a.cls_thresh[step - 1], a.reg_thresh[step - 1], a.max_pos_num, a.neg_ratio, a.selection_sampling, self.budget,
+                                out=self.out[step])

@@ -12,7 +12,7 @@ from . import dist as sdist
 from .driver import GraphedInference, inference, inference_flat, postprocess
 from .backbone import wgrad_into_grad
 from .optim import FlatAdam, FlatSGD
-from .selection import train_select
+from .selection import DeviceSelector, train_select
 from .driver import _flat_tubes
 from .tube_math import generate_anchors
 
@@ -319,10 +319,20 @@ class C4SelectTrainStep(C4TrainStep):
                       then the draws from `random` / `numpy.random` in the reference's order) writes the selection into static device
                       buffers; graph B = ROIAlign + the three heads + losses + backward + re-pack + Adam (with a process group: B stops after
                       backward, ONE eager flat all-reduce, graph U = re-pack + Adam -- the split form, nothing of the group is recorded).
-                      Same kernels on the same buffers as step_padded(): bit-identical trajectory (tests/test_gpu_graph_step.py)."""
+                      Same kernels on the same buffers as step_padded(): bit-identical trajectory (tests/test_gpu_graph_step.py).
+
+    selection="device" (opt-in; "host" is the default and the form that reproduces the reference's draws): the padded forms select on the
+    device instead (step_amd.selection.DeviceSelector: step_select_prepare + step_select_train per step, draws from `self.rng`, one offset
+    per step) -- no copy, no host work between the first launch of the iteration and the last, so capture() records front, selection and
+    back as ONE graph ("select-one"; with a process group one graph up to the backward, the eager flat all-reduce, the update graph:
+    "select-one-split").  The ragged step() keeps the host selection -- before capture(), step() of a selection="device" workload is
+    therefore the HOST form; `selection_ran` names the selection of the last iteration, and a caller that wants the device selection
+    uncaptured calls step_padded() (train_step_amd.py --select-device --no-graph does)."""
 
     def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, tubes_per_clip=34, capturable=False, force_exchange=False, budget=None,
-                 optimizer="adam", dropout=0.0, rng_seed=0):
+                 optimizer="adam", dropout=0.0, rng_seed=0, selection="host"):
+        if selection not in ("host", "device"):
+            raise ValueError("C4SelectTrainStep: selection is 'host' or 'device', got %r" % (selection,))
         super().__init__(dev, batch=batch, tubes_per_clip=5, seed=seed, max_iter=3, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
                          optimizer=optimizer, dropout=dropout, rng_seed=rng_seed)
         rs = np.random.RandomState(seed)
@@ -337,7 +347,9 @@ class C4SelectTrainStep(C4TrainStep):
                     t[g_, c, :4] = box + rs.uniform(-5, 5, 4).astype(np.float32)
                 t[g_, :, 4 + rs.randint(0, 60, 3)] = 1
             self.gt.append(t)
-        self.selected = []
+        self.selection = selection
+        self.selection_ran = None                                # "host" | "device": the selection of the LAST iteration (step() before capture() is the ragged form: host)
+        self._selected = []
         a = self.args
         self.budget = int(budget or a.max_pos_num * (1 + a.neg_ratio))
         # static state of the padded form
@@ -351,10 +363,39 @@ class C4SelectTrainStep(C4TrainStep):
             Tl = a.NUM_CHUNKS[i] * a.T
             for dst, host, shape in ((self.s_flat, self.h_flat, (K, Tl, 5)), (self.s_tgt, self.h_tgt, (K, 3, 6 + a.num_classes)),
                                      (self.s_mask, self.h_mask, (K, 1)), (self.s_inv, self.h_inv, (1,))):
-                dst.append(torch.zeros(shape, device=dev))
-                host.append(torch.zeros(shape).pin_memory())
+                dst.append(torch.zeros(shape, device=dev) if selection == "host" else None)     # (device: the selector's own buffers, below)
+                if selection == "host":
+                    host.append(torch.zeros(shape).pin_memory())
+        if selection == "device":
+            # everything the selection reads is resident: ground truths, the initial tubes (step 1's candidates), the padded slots' box
+            self.selector = DeviceSelector(a, batch, self.budget, dev, self.rng)
+            self.d_gt = torch.from_numpy(np.stack(self.gt)).to(dev)
+            self.d_gt_count = torch.full((batch,), self.gt[0].shape[0], dtype=torch.int32, device=dev)
+            self.d_init = self.flat0[:, :, 1:].float().contiguous()
+            self.d_clip_start = torch.as_tensor(np.concatenate(([0], np.cumsum(self.nums0))).astype(np.int32), device=dev)
+            self.d_pad = []
+            for i in range(1, a.max_iter + 1):
+                Tl = a.NUM_CHUNKS[i] * a.T
+                fill = np.stack([np.tile(np.asarray(t[0], np.float32), (Tl // t.shape[1] + 1, 1))[:Tl] for t in self.init_tubes])
+                self.d_pad.append(torch.from_numpy(fill).to(dev))
+                self.s_flat[i - 1], self.s_tgt[i - 1], self.s_mask[i - 1], self.s_inv[i - 1] = self.selector.out[i][:4]
         self._gF = self._gB = self._gU = None
         self._front = None
+
+    @property
+    def selected(self):
+        """tubes selected per step and clip in the last iteration; with the device selection this reads `counts` (and synchronises)"""
+        if self._selected is None:
+            return [[int(v) for v in c.sum(axis=1)] for c in self.select_counts()]
+        return self._selected
+
+    @selected.setter
+    def selected(self, value):
+        self._selected = value
+
+    def select_counts(self):
+        """device selection: [max_iter, B, 2] (positives, negatives) of the last iteration, on the host; synchronises"""
+        return np.stack([self.selector.out[i][4].cpu().numpy() for i in range(1, self.args.max_iter + 1)])
 
     # ---- the ragged eager iteration (the reference's program, shapes follow the selection)
     def step(self):
@@ -376,6 +417,7 @@ class C4SelectTrainStep(C4TrainStep):
             t0 = int((max_chunks - chunks) / 2) * a.T
             Tl = chunks * a.T
             sel, tgt = train_select(i, history[i - 2] if i > 1 else None, self.gt, self.init_tubes, a)
+            self.selection_ran = "host"
             self.selected.append([len(s_) for s_ in sel])
             flat, nums = _flat_tubes(sel, cf.device)
             targets = torch.from_numpy(np.concatenate(tgt, axis=0)).to(cf.device)
@@ -407,9 +449,18 @@ class C4SelectTrainStep(C4TrainStep):
         return cf, cx, history
 
     def _select_part(self, history):
-        """HOST: train_select per step on the inference's outputs, padded to `budget` slots per clip, into the static device buffers"""
+        """HOST (default): train_select per step on the inference's outputs, padded to `budget` slots per clip, into the static device buffers;
+        selection="device": the same rows chosen and written by DeviceSelector, stream-ordered, with no copy either way"""
         a = self.args
+        if self.selection == "device":                          # DEVICE: two launches + their finishing kernel per step, nothing comes back
+            self._selected = None
+            self.selection_ran = "device"
+            for i in range(1, a.max_iter + 1):
+                self.selector.select(i, history[i - 2] if i > 1 else None, self.d_gt, self.d_gt_count, self.d_init, self.d_clip_start,
+                                     self.d_pad[i - 1], max_tubes=max(self.nums0))
+            return
         self.selected = []
+        self.selection_ran = "host"
         B, Bu = self.batch, self.budget
         for i in range(1, a.max_iter + 1):
             Tl = a.NUM_CHUNKS[i] * a.T
@@ -497,6 +548,23 @@ class C4SelectTrainStep(C4TrainStep):
         cur.wait_stream(s)
         torch.cuda.synchronize(dev)
         kw = {"capture_error_mode": "thread_local"} if grouped else {}
+        if self.selection == "device":
+            # nothing between the iteration's first launch and its last needs the host: front, selection and back are ONE recording
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, **kw):
+                cf, cx, hist = self._front_part()
+                self._select_part(hist)
+                self._back_part(cf, cx, update=not grouped)
+            gU = None
+            if grouped:
+                world = dd.get_world_size() if (dd.is_available() and dd.is_initialized()) else 1
+                gU = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gU, pool=g.pool(), **kw):
+                    self.opt.step(grad_scale=1.0 / world, zero_grad=True)
+            self._gF, self._gB, self._gU = g, None, gU
+            self.graph, self.graph_mode = g, ("select-one-split" if grouped else "select-one")
+            torch.autograd.graph.increment_version(self.params)
+            return self
         gF = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gF, **kw):
             self._front = self._front_part()
@@ -527,8 +595,9 @@ class C4SelectTrainStep(C4TrainStep):
     def _replay(self):
         self.opt._refresh_tables()
         self._gF.replay()
-        self._select_part(self._front[2])                        # host: reads the inference's static outputs (one small copy per step)
-        self._gB.replay()
+        if self._gB is not None:                                 # (device selection: the one graph holds all three parts)
+            self._select_part(self._front[2])                    # host: reads the inference's static outputs (one small copy per step)
+            self._gB.replay()
         if self._gU is not None:
             sdist.allreduce_flat(self.opt.flat_grad)
             self._gU.replay()

@@ -20,6 +20,8 @@ Every rank
      same arenas, same exchange, same captured step,
      --dropout P trains with the heads' dropout (the reference's recipe: 0.3) on the device-side generator: the captured step draws new masks
      on every replay (`step_amd.Dropout`, `step_amd.rng`); --rng-seed S seeds it, rank r with S + r,
+     --select-device trains on the reference's whole iteration with the proposal selection on the device, drawing from the same generator: one
+     graph per iteration instead of two around the host's selection,
   6. rank 0 prints one JSON line per --log-every iterations and a final summary (loss, ms per iteration, clips/s of the whole job).
 
 Data: synthetic AVA-shaped clips [B,36,3,400,400] and fixed anchor tubes (there is no dataset in this repository; the reference's
@@ -65,6 +67,9 @@ def main():
     ap.add_argument("--select", action="store_true",
                     help="the reference's whole iteration (train.py:257-348): no-grad inference + train_select between the steps (workloads.C4SelectTrainStep, "
                          "captured as graphs around the host's selection)")
+    ap.add_argument("--select-device", action="store_true",
+                    help="implies --select, with the selection on the device (step_select_train, draws from the generator of --rng-seed): the whole "
+                         "iteration is captured as ONE graph; the draws are not the reference's")
     ap.add_argument("--feed", default="none", choices=["none", "u8"])
     ap.add_argument("--augment", action="store_true",
                     help="--feed u8 only: uint8 frames at --src-size, the reference's TubeAugmentation (all four switches on, scripts/train_step.sh:55-58) "
@@ -75,6 +80,7 @@ def main():
                     help="process-group backend (default: nccl = RCCL; gloo only to exercise the multi-rank program with ranks SHARING one GPU, "
                          "which RCCL refuses -- the exchange is then one eager flat all-reduce between two captured graphs)")
     a = ap.parse_args()
+    a.select = a.select or a.select_device
     if a.optimizer == "sgd" and a.momentum <= 0:
         raise SystemExit("train_step_amd.py: --momentum must be positive (the workload's momentum buffer is allocated at construction)")
     if a.augment and a.feed != "u8":
@@ -100,7 +106,7 @@ def main():
         random.seed(1000 + rank)                                 # (the selection draws from the reference's two host RNG streams)
         np.random.seed(1000 + rank)
         w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=graphed, optimizer=a.optimizer,
-                                        dropout=a.dropout, rng_seed=a.rng_seed + rank)
+                                        dropout=a.dropout, rng_seed=a.rng_seed + rank, selection="device" if a.select_device else "host")
     else:
         w = workloads.C4TrainStep(dev, batch=len(mine), tubes_per_clip=a.tubes, seed=123 + rank, dtype=tdt, capturable=graphed,
                                   optimizer=a.optimizer, dropout=a.dropout, rng_seed=a.rng_seed + rank)
@@ -110,11 +116,14 @@ def main():
             g["momentum"] = a.momentum
         if a.weight_decay is not None:
             g["weight_decay"] = a.weight_decay
+    # --select-device without a capture (--no-graph, fp32): the padded eager iteration, which selects on the device -- the ragged step() always
+    # selects on the host
+    run = w.step_padded if (a.select_device and not graphed) else w.step
     if graphed:
         w.capture(warmup=a.warmup_iters, mode=a.graph)             # (C4SelectTrainStep: its own graph forms; `mode` only matters for the fixed-tube step)
     else:
         for _ in range(a.warmup_iters):
-            w.step()
+            run()
 
     feed = None
     if a.feed == "u8":
@@ -165,7 +174,7 @@ def main():
                 g["lr"] *= 0.1
         if feed is not None:
             feed(it)
-        loss = w.step()
+        loss = run()
         if rank == 0 and a.log_every and (it + 1) % a.log_every == 0:
             lv = float(loss)                                      # (one host sync per log line)
             now = time.perf_counter()
@@ -186,7 +195,7 @@ def main():
                           "launch": ("hipGraph replay (%s)" % w.graph_mode) if w.graph is not None else "eager",
                           "gradient_exchange": _exchange_label(w, world),
                           "feed": a.feed + ("+augment" if a.augment else ""), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
-                          "dropout": a.dropout, "rng_offset": w.rng.offset(),
+                          "dropout": a.dropout, "rng_offset": w.rng.offset(), **({"selection": w.selection_ran} if a.select else {}),
                           **({"adam_steps": w.opt.step_count} if a.optimizer == "adam" else {})}), flush=True)
     if world > 1:
         torch.distributed.barrier()
@@ -199,7 +208,7 @@ def _exchange_label(w, world):
         return None
     backend = torch.distributed.get_backend()
     lib = "RCCL" if backend == "nccl" else backend
-    if getattr(w, "graph_mode", None) in ("split", "select-split"):
+    if getattr(w, "graph_mode", None) in ("split", "select-split", "select-one-split"):
         return "one eager flat %s all-reduce of the gradient arena between the two graphs, %d ranks" % (lib, world)
     where = "recorded in the step's graph" if w.graph is not None else "eager, overlapped with backward"
     return "bucketed %s all-reduce, %d buckets, %s, %d ranks" % (lib, len(w.reducer.buckets), where, world)
