@@ -52,7 +52,7 @@ enum {
     STEP_E_ALIGN = -5
 };
 
-/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (41: step_select_train). */
+/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (42: step_grad_pack16 / step_grad_unpack16). */
 STEP_API const char* step_version(void);
 STEP_API int step_abi_version(void);
 
@@ -696,6 +696,27 @@ STEP_API int step_sgd_flat_amp(float* param, float* grad, float* momentum_buf, l
                                const float* seg_lr, const float* seg_wd, int n_seg, double momentum, double dampening, int nesterov,
                                long long* step_dev, float grad_scale, int zero_grad, float* amp_state, float growth_factor,
                                float backoff_factor, int growth_interval, step_stream_t stream);
+
+/* The 16-bit wire of the data-parallel gradient exchange (step_amd.dist.GradWire; what torch's DDP ships as
+ * bf16_compress_hook), with ERROR FEEDBACK: the rounding error of what a rank sent stays in an fp32 residual arena and is added to the
+ * next step's gradient before rounding, so nothing is lost locally, only delayed.  Per element i < n:
+ *     v           = fmaf(grad[i], pre_scale, residual ? residual[i] : 0)       one rounding
+ *     wire[i]     = bf16(v)                                                    round to nearest even; NaN stays NaN
+ *     residual[i] = isfinite(float(wire[i])) ? v - float(wire[i]) : 0          only when residual != NULL
+ * The subtraction is exact in fp32 (the error of a round-to-nearest-even to 8 significant bits is a multiple of v's fp32 ulp and below
+ * half a bf16 ulp), so float(wire[i]) + residual[i] == v bit for bit.  An inf / NaN on the wire -- a finite v that ROUNDS to inf, such
+ * as 3.4e38, included -- travels to every rank (the loss scaler's overflow scan sees it) and leaves a zero residual.  What the conversion
+ * does with fp32 subnormals (|v| < 2^-126) is not part of the contract.  grad is read only; residual == NULL: no feedback.  pre_scale
+ * carries the per-rank weight of a weighted average (a host scalar that is fixed per capture, as grad_scale is); 1 / world stays in the
+ * optimizer pass.
+ * step_grad_unpack16: grad[i] = float(wire[i]), exact.
+ * wire_dtype: STEP_BF16 only (STEP_F16 / STEP_F32 -> STEP_E_UNSUPPORTED); n < 0 -> STEP_E_SHAPE; n == 0 -> STEP_OK, nothing launched; a
+ * NULL grad or wire with n > 0 -> STEP_E_NULL; a refused call has written nothing.  Pointers aligned to their element size (16-byte
+ * aligned tensors take the vector path: 8 elements per lane and iteration).  14 B per element packed with a residual, 6 without, 6
+ * unpacked.  Both calls are capturable. */
+STEP_API int step_grad_pack16(int wire_dtype, const float* grad, float* residual, void* wire, long long n, float pre_scale,
+                              step_stream_t stream);
+STEP_API int step_grad_unpack16(int wire_dtype, const void* wire, float* grad, long long n, step_stream_t stream);
 
 /* The tail of TwoBranchNet.forward (models/two_branch.py:246-342) behind its last two GEMMs, as ONE launch (and one for its backward):
  * the class logits averaged over a tube's frames and their sigmoid, the box regressions (local_loc = columns 0..3 of the fused

@@ -5,7 +5,7 @@ import ctypes as C
 F32, BF16, F16 = 0, 1, 2
 NCHW, NHWC = 0, 1
 ROI_BWD_GATHER, ROI_BWD_ATOMIC = 0, 1
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 vp, fp, ip, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # raw device addresses
 i, f, ll, sz = C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -131,6 +131,8 @@ SIGNATURES = {
     "step_sgd_flat": (i, [fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, i, i, f, i, vp]),
     "step_sgd_flat_dev": (i, [fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, i, vp, f, i, vp]),
     "step_sgd_flat_amp": (i, [fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, i, vp, f, i, fp, f, f, i, vp]),
+    "step_grad_pack16": (i, [i, fp, fp, vp, ll, f, vp]),
+    "step_grad_unpack16": (i, [i, vp, fp, ll, vp]),
 }
 
 

@@ -11,6 +11,7 @@
 //   m += (g - m) * (1 - beta1)                 (Tensor.lerp_)
 //   v  = v * beta2 + (1 - beta2) * g * g
 //   p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+// Also here, beside the optimizers they feed: the bf16 wire of the data-parallel gradient exchange (grad_pack16 / grad_unpack16).
 #include "common.h"
 #include <cmath>
 #include <cstdlib>
@@ -169,6 +170,70 @@ __global__ void sgd_count_kernel(long long* step, const float* amp) {
         if (amp && amp[2] != 0.f) return;
         *step = *step + 1;
     }
+}
+
+// ---- 16-bit gradient wire with error feedback (step_grad_pack16 / step_grad_unpack16; the data-parallel exchange of step_amd.dist) ----
+// pack:   v = fma(grad, pre_scale, residual), wire = bf16(v) (round to nearest even), residual = v - float(wire) -- EXACT in fp32: |v -
+//         float(wire)| <= half a bf16 ulp of v and a multiple of v's fp32 ulp, so it fits the 24-bit significand -- or 0 where the wire
+//         value is inf / NaN (the overflow must travel, it must not stay in the residual).  14 B per element with a residual, 6 without.
+// unpack: grad = float(wire), exact.  6 B per element.
+// Pure HBM streaming like the optimizer passes: 256-thread workgroups, grid-stride, 8 elements per lane and iteration (16-byte vectors
+// of all three tensors); VEC = false walks element by element (a view that does not start on a 16-byte line).  The conversion is the
+// project's f32_to_bf16_bits, one v_cvt_pk_bf16_f32 per pair on the device.
+__device__ __forceinline__ unsigned short pack16_one(float g, float r, float s, float& r_new) {
+    const float v = fmaf(g, s, r);                         // ONE rounding, on the device and on the interpreter (-ffp-contract=off)
+    const unsigned short w = f32_to_bf16_bits(v);
+    r_new = (w & 0x7f80u) != 0x7f80u ? v - bf16_bits_to_f32(w) : 0.f;
+    return w;
+}
+
+template <bool RES, bool VEC>
+__global__ __launch_bounds__(256) void grad_pack16_kernel(const float* __restrict__ grad, float* __restrict__ residual,
+                                                          unsigned short* __restrict__ wire, long long n, float pre_scale) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)blockDim.x * gridDim.x;
+    long long done = 0;                                    // elements the vector body covers; the rest is the scalar tail
+    if (VEC) {
+        const long long nvec = n >> 3;
+        done = nvec << 3;
+        for (long long vec = gid; vec < nvec; vec += stride) {
+            const long long e = vec * 8;
+            const f32x4 g0 = *(const f32x4*)(grad + e), g1 = *(const f32x4*)(grad + e + 4);
+            f32x4 r0 = f32x4{0.f, 0.f, 0.f, 0.f}, r1 = r0;
+            if (RES) { r0 = *(const f32x4*)(residual + e); r1 = *(const f32x4*)(residual + e + 4); }
+            u16x8 w;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float a, b;
+                w[j] = pack16_one(g0[j], r0[j], pre_scale, a);
+                w[j + 4] = pack16_one(g1[j], r1[j], pre_scale, b);
+                r0[j] = a; r1[j] = b;
+            }
+            *(u16x8*)(wire + e) = w;
+            if (RES) { *(f32x4*)(residual + e) = r0; *(f32x4*)(residual + e + 4) = r1; }
+        }
+    }
+    for (long long e = done + gid; e < n; e += stride) {
+        float r = 0.f;
+        wire[e] = pack16_one(grad[e], RES ? residual[e] : 0.f, pre_scale, r);
+        if (RES) residual[e] = r;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void grad_unpack16_kernel(const unsigned short* __restrict__ wire, float* __restrict__ grad, long long n) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)blockDim.x * gridDim.x;
+    long long done = 0;
+    if (VEC) {
+        const long long nvec = n >> 3;
+        done = nvec << 3;
+        for (long long vec = gid; vec < nvec; vec += stride) {
+            const long long e = vec * 8;
+            const u16x8 w = *(const u16x8*)(wire + e);
+            *(f32x4*)(grad + e) = f32x4{bf16_bits_to_f32(w[0]), bf16_bits_to_f32(w[1]), bf16_bits_to_f32(w[2]), bf16_bits_to_f32(w[3])};
+            *(f32x4*)(grad + e + 4) = f32x4{bf16_bits_to_f32(w[4]), bf16_bits_to_f32(w[5]), bf16_bits_to_f32(w[6]), bf16_bits_to_f32(w[7])};
+        }
+    }
+    for (long long e = done + gid; e < n; e += stride) grad[e] = bf16_bits_to_f32(wire[e]);
 }
 
 // ---- activation gradient of the fused conv unit ---------------------------------------------------------------------
@@ -442,6 +507,55 @@ int step_sgd_flat_amp(float* param, float* grad, float* momentum_buf, long long 
                          zero_grad, stream, amp_state);
     if (rc) return rc;
     STEP_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), stream, amp_state, growth_factor, backoff_factor, growth_interval);
+    return STEP_LAUNCH_CHECK();
+}
+
+// every argument is checked before the first launch: a refused call has written nothing (as sgd_flat_check)
+static int grad_wire_check(int wire_dtype, const float* grad, const float* residual, const void* wire, long long n) {
+    if (wire_dtype == STEP_F16 || wire_dtype == STEP_F32) return STEP_E_UNSUPPORTED;     // one wire format: bfloat16
+    if (wire_dtype != STEP_BF16) return STEP_E_DTYPE;
+    if (n < 0) return STEP_E_SHAPE;
+    if (n == 0) return STEP_OK;
+    if (!grad || !wire) return STEP_E_NULL;
+    if ((((uintptr_t)grad) | ((uintptr_t)residual)) & 3 || ((uintptr_t)wire & 1)) return STEP_E_ALIGN;
+    return STEP_OK;
+}
+
+// 8 workgroups per CU are resident at once (32 wavefronts): one pass of the grid covers 2^22 elements of the vector body, the 44.4 M of
+// the full arena take 11 passes of the grid-stride loop
+static unsigned grad_wire_blocks(long long items) {
+    long long blocks = (items + 255) / 256;
+    if (blocks > 256LL * 8) blocks = 256LL * 8;
+#ifdef STEP_EMUL
+    if (blocks > 2) blocks = 2;                            // (host emulator: let small cases walk the grid-stride loop)
+#endif
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+int step_grad_pack16(int wire_dtype, const float* grad, float* residual, void* wire, long long n, float pre_scale, step_stream_t stream) {
+    const int rc = grad_wire_check(wire_dtype, grad, residual, wire, n);
+    if (rc || n == 0) return rc;
+    const bool vec = !((((uintptr_t)grad) | ((uintptr_t)residual) | ((uintptr_t)wire)) & 15);
+    const dim3 grid(grad_wire_blocks(vec ? (n + 7) >> 3 : n));
+    unsigned short* w = (unsigned short*)wire;
+    if (residual) {
+        if (vec) STEP_LAUNCH((grad_pack16_kernel<true, true>), grid, dim3(256), stream, grad, residual, w, n, pre_scale);
+        else STEP_LAUNCH((grad_pack16_kernel<true, false>), grid, dim3(256), stream, grad, residual, w, n, pre_scale);
+    } else {
+        if (vec) STEP_LAUNCH((grad_pack16_kernel<false, true>), grid, dim3(256), stream, grad, residual, w, n, pre_scale);
+        else STEP_LAUNCH((grad_pack16_kernel<false, false>), grid, dim3(256), stream, grad, residual, w, n, pre_scale);
+    }
+    return STEP_LAUNCH_CHECK();
+}
+
+int step_grad_unpack16(int wire_dtype, const void* wire, float* grad, long long n, step_stream_t stream) {
+    const int rc = grad_wire_check(wire_dtype, grad, nullptr, wire, n);
+    if (rc || n == 0) return rc;
+    const bool vec = !((((uintptr_t)grad) | ((uintptr_t)wire)) & 15);
+    const dim3 grid(grad_wire_blocks(vec ? (n + 7) >> 3 : n));
+    const unsigned short* w = (const unsigned short*)wire;
+    if (vec) STEP_LAUNCH((grad_unpack16_kernel<true>), grid, dim3(256), stream, w, grad, n);
+    else STEP_LAUNCH((grad_unpack16_kernel<false>), grid, dim3(256), stream, w, grad, n);
     return STEP_LAUNCH_CHECK();
 }
 

@@ -11,12 +11,17 @@ tensor on the path is per clip, BN is frozen, so:
     7 links per GPU, so a ring all-reduce is per-link bound: buckets are kept large (default 64 MiB) to
     amortise latency, and the 177.7 MB of fp32 gradients of the full model is 3 buckets.
 The same code runs over gloo on CPU (tests/test_dist_gloo.py).
+
+Optionally the exchange travels as bfloat16 with error feedback (`GradWire`): half the ring bytes, nothing lost
+locally.  The wire is fp32 unless the caller asks otherwise.
 """
 import os
 import time
 
 import torch
 import torch.distributed as dist
+
+from . import _capi, _lib
 
 
 def init(backend=None):
@@ -52,21 +57,120 @@ def broadcast_parameters(modules, src=0):
             dist.broadcast(t.data, src)
 
 
-def allreduce_flat(flat, weight=None, chunk_bytes=512 << 20):
+def _exchange_active(single_rank=False):
+    return dist.is_initialized() and (dist.get_world_size() > 1 or bool(single_rank))
+
+
+class GradWire:
+    """The gradient exchange as bfloat16 with ERROR FEEDBACK (torch's DDP ships the plain form as bf16_compress_hook).
+
+    Instead of the fp32 arena, `wire` -- a bf16 tensor of opt.numel -- is all-reduced: 2 bytes per element on the link instead of 4.
+    Each rank keeps the rounding error of what it sent in `residual` (fp32, opt.numel) and adds it to the next step's gradient before
+    rounding (step_grad_pack16, include/step_amd.h): v = g * pre_scale + r, wire = bf16(v), r = v - float(wire).  That difference is
+    exactly representable in fp32, so nothing is ever lost locally, only delayed.  An inf / NaN travels (every rank sees the overflow)
+    and leaves a zero residual.  error_feedback=False is the plain form (round, sum, widen): no residual arena.
+
+    Both arenas are allocated here, so a captured step never allocates.  The object registers itself as `opt.grad_wire`; hand it to
+    BucketedReducer(opt, wire=...) / allreduce_flat(opt.flat_grad, wire=...).  pack / unpack / wire_view work on the element range
+    [lo, hi) of the arena and launch on the current stream.
+
+    Where the exchange is INACTIVE (no process group, or one rank without single_rank) the wire does nothing -- it does not pack either,
+    so a single-process run is bit-identical to one without a wire and the residual stays zero.
+
+    Error feedback and a LossScaler exclude each other (the residual would be kept in units of a scale that changes on overflow):
+    opt.step(scaler=...) raises.  A wire without feedback works with the scaler: the inf travels and every rank skips the step.
+
+    Checkpoints: state_dict() carries dtype, the feedback flag and the residual; with the residual a resume is bit-identical, without it
+    (load_state_dict of a dict whose "residual" is None or missing) the residual restarts at zero, which only drops the delayed
+    sub-bf16 part of ONE step's gradient."""
+
+    def __init__(self, opt, dtype="bf16", error_feedback=True):
+        if dtype != "bf16":
+            raise ValueError("GradWire: the wire dtype is 'bf16', got %r" % (dtype,))
+        self.opt, self.dtype, self.error_feedback = opt, dtype, bool(error_feedback)
+        _lib.dptr(opt.flat_grad)                                 # refuses non-device arenas: there is no CPU fallback
+        self.wire = torch.zeros(opt.numel, dtype=torch.bfloat16, device=opt.device)
+        self.residual = torch.zeros(opt.numel, dtype=torch.float32, device=opt.device) if self.error_feedback else None
+        opt.grad_wire = self
+
+    def _check(self, lo, hi):
+        if not (0 <= lo <= hi <= self.opt.numel):
+            raise ValueError("GradWire: [%d, %d) is not a range of the %d-element arena" % (lo, hi, self.opt.numel))
+
+    def wire_view(self, lo, hi):
+        self._check(lo, hi)
+        return self.wire[lo:hi]
+
+    def pack(self, lo, hi, pre_scale=1.0):
+        """flat_grad[lo:hi] * pre_scale (+ residual) -> wire[lo:hi], the new rounding error -> residual[lo:hi]; the gradient is not
+        written.  pre_scale == 0 (a rank that contributes nothing to a weighted average) sends exact zeros and keeps its residual."""
+        self._check(lo, hi)
+        if float(pre_scale) == 0.0:
+            self.wire[lo:hi].zero_()
+            return
+        res = None if self.residual is None else _lib.dptr(self.residual[lo:hi])
+        _capi.check(_lib.lib().step_grad_pack16(_capi.BF16, _lib.dptr(self.opt.flat_grad[lo:hi]), res, _lib.dptr(self.wire[lo:hi]), hi - lo,
+                                                float(pre_scale), _lib.stream_ptr(self.opt.device)), "step_grad_pack16")
+
+    def unpack(self, lo, hi):
+        """wire[lo:hi] -> flat_grad[lo:hi], exact"""
+        self._check(lo, hi)
+        _capi.check(_lib.lib().step_grad_unpack16(_capi.BF16, _lib.dptr(self.wire[lo:hi]), _lib.dptr(self.opt.flat_grad[lo:hi]), hi - lo,
+                                                  _lib.stream_ptr(self.opt.device)), "step_grad_unpack16")
+
+    def state_dict(self):
+        return {"dtype": self.dtype, "error_feedback": self.error_feedback,
+                "residual": None if self.residual is None else self.residual.clone()}
+
+    def load_state_dict(self, sd):
+        if sd.get("dtype", self.dtype) != self.dtype or bool(sd.get("error_feedback", self.error_feedback)) != self.error_feedback:
+            raise ValueError("GradWire.load_state_dict: the checkpoint's wire (%r, error_feedback=%r) is not this one (%r, %r)"
+                             % (sd.get("dtype"), sd.get("error_feedback"), self.dtype, self.error_feedback))
+        if self.residual is None:
+            return
+        res = sd.get("residual")
+        with torch.no_grad():
+            if res is None:
+                self.residual.zero_()                            # harmless: the delayed part of one step's gradient is dropped
+            else:
+                if res.numel() != self.residual.numel():
+                    raise ValueError("GradWire.load_state_dict: residual of %d elements, arena of %d" % (res.numel(), self.residual.numel()))
+                self.residual.copy_(res.reshape(-1))
+
+
+def allreduce_flat(flat, weight=None, chunk_bytes=512 << 20, wire=None, single_rank=False):
     """SUM-all-reduce the contiguous gradient arena of step_amd.optim.FlatAdam in place -- one collective (a few for
     arenas beyond chunk_bytes), no bucket copies -- and return the factor that turns the sum into the average, to be
     handed to FlatAdam.step(grad_scale=...) so the division rides in the optimizer pass.
 
     weight: optional per-rank scalar as in allreduce_gradients(); the local arena is pre-multiplied by it and the
-    returned factor is 1 / sum_r(weight_r)."""
-    if not dist.is_initialized() or dist.get_world_size() == 1:
+    returned factor is 1 / sum_r(weight_r).
+
+    wire: a GradWire of the optimizer that owns `flat` (flat must BE wire.opt.flat_grad): every chunk is packed to bf16 (the weight rides
+    in the pack as pre_scale, the arena itself is not multiplied), the bf16 chunk is all-reduced and widened back into `flat`.
+    chunk_bytes then counts bytes of the wire.  Where the exchange is inactive the wire does nothing (it does not pack either).
+
+    single_rank: issue the collectives in a ONE-rank process group too (identities there), as BucketedReducer(single_rank=True)."""
+    if wire is not None and (flat is not wire.opt.flat_grad and
+                             (flat.data_ptr() != wire.opt.flat_grad.data_ptr() or flat.numel() != wire.opt.numel or flat.dtype != torch.float32)):
+        raise ValueError("allreduce_flat(wire=...): `flat` must be the gradient arena of the wire's optimizer (wire.opt.flat_grad)")
+    if not _exchange_active(single_rank):
         return 1.0
     factor = 1.0 / dist.get_world_size()
     if weight is not None:
         wsum = torch.tensor([float(weight)], device=flat.device, dtype=torch.float32)
         dist.all_reduce(wsum)
-        flat.mul_(float(weight))
+        if wire is None:
+            flat.mul_(float(weight))
         factor = 1.0 / float(wsum.item())
+    if wire is not None:
+        step = max(1, chunk_bytes // wire.wire.element_size())
+        for o in range(0, flat.numel(), step):
+            hi = min(o + step, flat.numel())
+            wire.pack(o, hi, 1.0 if weight is None else float(weight))
+            dist.all_reduce(wire.wire_view(o, hi))               # (nccl: the current stream waits for the collective)
+            wire.unpack(o, hi)
+        return factor
     step = max(1, chunk_bytes // flat.element_size())
     for o in range(0, flat.numel(), step):
         dist.all_reduce(flat[o:o + step])
@@ -96,9 +200,14 @@ class BucketedReducer:
         opt.step(grad_scale=scale, zero_grad=True)
     """
 
-    def __init__(self, opt, bucket_bytes=32 << 20, single_rank=False):
+    def __init__(self, opt, bucket_bytes=32 << 20, single_rank=False, wire=None):
         # single_rank: issue the collectives even in a ONE-rank process group (they are identities there) -- lets the whole
         # RCCL path (communicator on this device, communication stream, bucket order, stream waits) run on a one-GPU box
+        # wire: a GradWire of `opt` -- every bucket travels as bf16 (pack, all-reduce of the wire, unpack, all on the communication
+        # stream; the per-rank weight rides in the pack).  Same buckets, same issue order.  Inactive exchange: the wire does nothing.
+        if wire is not None and wire.opt is not opt:
+            raise ValueError("BucketedReducer(wire=...): the wire belongs to another optimizer")
+        self.wire = wire
         self.opt = opt
         self.flat = opt.flat_grad
         entries = opt._entries                                  # (group, param, offset, numel), ascending offsets
@@ -113,7 +222,7 @@ class BucketedReducer:
             if end - lo >= cap or k + 1 == len(entries):
                 self.buckets.append((lo, end, cnt))
                 lo, cnt = end, 0
-        self.active = dist.is_initialized() and (dist.get_world_size() > 1 or bool(single_rank))
+        self.active = _exchange_active(single_rank)
         self.cuda = self.flat.is_cuda
         self.comm = torch.cuda.Stream(self.flat.device) if self.cuda else None
         self._hooks = [p.register_post_accumulate_grad_hook(self._autograd_ready) for _, p, _, _ in entries]
@@ -209,13 +318,22 @@ class BucketedReducer:
             for s_ in self.side_streams[b]:
                 self.comm.wait_stream(s_)                        # ... and the direct weight-gradient accumulations
             with torch.cuda.stream(self.comm):
-                if self.weight is not None:
-                    seg.mul_(self.weight)
-                self.works.append(dist.all_reduce(seg, async_op=True))
+                self._exchange(seg, lo, hi)
         else:
+            self._exchange(seg, lo, hi)
+
+    def _exchange(self, seg, lo, hi):
+        # (on the communication stream)
+        if self.wire is None:
             if self.weight is not None:
                 seg.mul_(self.weight)
             self.works.append(dist.all_reduce(seg, async_op=True))
+            return
+        self.wire.pack(lo, hi, 1.0 if self.weight is None else self.weight)
+        work = dist.all_reduce(self.wire.wire_view(lo, hi), async_op=True)
+        work.wait()                                              # nccl: the communication stream waits for the collective (the host does not)
+        self.wire.unpack(lo, hi)
+        self.works.append(work)
 
     def finish(self):
         """Issue the buckets backward did not complete (same order on every rank), wait for all of them, return the

@@ -62,6 +62,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     per name in `state_arenas`, the `_entries` / `numel` / `_seg_*` tables the kernels, step_amd.dist and step_amd.workloads read, the
     host / device step count, and everything of step() around the subclass's launch (`_launch`)."""
 
+    grad_wire = None                                             # a step_amd.dist.GradWire registers itself here (on the instance)
+
     def _check_groups(self):
         """hyper-parameters that one launch cannot vary must agree across the groups"""
 
@@ -174,6 +176,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if scaler is not None and not self.capturable:
             raise RuntimeError("%s.step(scaler=...): build the optimizer with capturable=True (a skipped step must not count, "
                                "and only the device knows whether it was skipped)" % type(self).__name__)
+        if scaler is not None and self.grad_wire is not None and self.grad_wire.error_feedback:
+            raise RuntimeError("%s.step(scaler=...): the gradient wire keeps an error-feedback residual, which would be in units of a loss "
+                               "scale that changes on overflow -- use GradWire(error_feedback=False) with a LossScaler" % type(self).__name__)
         self._launch(_lib.lib(), float(grad_scale), int(bool(zero_grad)), scaler)
         # the kernel wrote through raw pointers: bump the autograd version counters (the packed-weight caches of
         # backbone.py / heads.py are keyed on them)

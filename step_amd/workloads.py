@@ -106,7 +106,7 @@ class C4TrainStep:
     same `tubes_per_clip` anchor tubes, extended to the step's length."""
 
     def __init__(self, dev, batch=1, tubes_per_clip=5, seed=123, max_iter=3, dtype=torch.float32, capturable=False, force_exchange=False,
-                 optimizer="adam", dropout=0.0, rng_seed=0):
+                 optimizer="adam", dropout=0.0, rng_seed=0, grad_wire="fp32", wire_feedback=True):
         # replicas: the same weights on every rank (same init seed, then rank 0's copy is broadcast once, as DDP does);
         # `seed` only varies the rank's clips
         self.args, self.base, self.ctx, self.nets = build_nets(dev, 123, heads=max_iter, dropout=dropout)
@@ -134,7 +134,16 @@ class C4TrainStep:
         # the gradient exchange runs bucket by bucket on a communication stream WHILE backward is still producing the
         # earlier layers' gradients (step_amd.dist.BucketedReducer); single-process runs issue nothing
         # (force_exchange: in a ONE-rank process group the collectives are issued all the same -- the multi-rank program on a one-GPU box)
-        self.reducer = sdist.BucketedReducer(self.opt, single_rank=bool(force_exchange))
+        # grad_wire="bf16": the exchange travels as bfloat16, with error feedback unless wire_feedback=False (step_amd.dist.GradWire) -- in the
+        # reducer's buckets and in the eager flat all-reduce of the split form alike.  Without an active exchange there is no wire at all.
+        if grad_wire not in ("fp32", "bf16"):
+            raise ValueError("C4TrainStep: grad_wire is 'fp32' or 'bf16', got %r" % (grad_wire,))
+        self.force_exchange = bool(force_exchange)
+        self.grad_wire = grad_wire
+        self.wire = None
+        if grad_wire == "bf16" and sdist._exchange_active(self.force_exchange):
+            self.wire = sdist.GradWire(self.opt, "bf16", error_feedback=wire_feedback)
+        self.reducer = sdist.BucketedReducer(self.opt, single_rank=self.force_exchange, wire=self.wire)
         # fp32 master weights either way; a 16-bit clip makes every activation / data gradient 16-bit (fp32 accumulate),
         # weight gradients stay fp32
         self.x = ava_clips(seed, batch).to(dev).to(dtype)
@@ -196,7 +205,7 @@ class C4TrainStep:
             self.opt._refresh_tables()                           # lr / weight_decay of param_groups -> the device tables the captured Adam reads (schedulers keep working)
             self.graph.replay()                                  # ~800 launches (+ the bucket all-reduces of a multi-rank step), one submission
             if self._g_update is not None:                       # "split" form: forward / backward replayed, the exchange eager, the update replayed
-                sdist.allreduce_flat(self.opt.flat_grad)
+                sdist.allreduce_flat(self.opt.flat_grad, wire=self.wire, single_rank=self.force_exchange)
                 self._g_update.replay()
             # the replay re-packed the weights at its start and Adam changed them at its end: any eager use of the modules between
             # replays (validation) must see its packed-weight caches as stale
@@ -330,11 +339,11 @@ class C4SelectTrainStep(C4TrainStep):
     uncaptured calls step_padded() (train_step_amd.py --select-device --no-graph does)."""
 
     def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, tubes_per_clip=34, capturable=False, force_exchange=False, budget=None,
-                 optimizer="adam", dropout=0.0, rng_seed=0, selection="host"):
+                 optimizer="adam", dropout=0.0, rng_seed=0, selection="host", grad_wire="fp32", wire_feedback=True):
         if selection not in ("host", "device"):
             raise ValueError("C4SelectTrainStep: selection is 'host' or 'device', got %r" % (selection,))
         super().__init__(dev, batch=batch, tubes_per_clip=5, seed=seed, max_iter=3, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
-                         optimizer=optimizer, dropout=dropout, rng_seed=rng_seed)
+                         optimizer=optimizer, dropout=dropout, rng_seed=rng_seed, grad_wire=grad_wire, wire_feedback=wire_feedback)
         rs = np.random.RandomState(seed)
         anchors = (generate_anchors()[:tubes_per_clip] * 400.0).astype(np.float32)
         self.init_tubes = [np.tile(anchors[:, None, :], (1, 3, 1)) for _ in range(batch)]
@@ -599,7 +608,7 @@ class C4SelectTrainStep(C4TrainStep):
             self._select_part(self._front[2])                    # host: reads the inference's static outputs (one small copy per step)
             self._gB.replay()
         if self._gU is not None:
-            sdist.allreduce_flat(self.opt.flat_grad)
+            sdist.allreduce_flat(self.opt.flat_grad, wire=self.wire, single_rank=self.force_exchange)
             self._gU.replay()
         torch.autograd.graph.increment_version(self.params)
         return self.loss

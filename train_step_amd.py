@@ -22,6 +22,7 @@ Every rank
      on every replay (`step_amd.Dropout`, `step_amd.rng`); --rng-seed S seeds it, rank r with S + r,
      --select-device trains on the reference's whole iteration with the proposal selection on the device, drawing from the same generator: one
      graph per iteration instead of two around the host's selection,
+     --grad-wire bf16 sends the gradients as bfloat16 with error feedback (`step_amd.dist.GradWire`; --no-wire-feedback: plain rounding),
   6. rank 0 prints one JSON line per --log-every iterations and a final summary (loss, ms per iteration, clips/s of the whole job).
 
 Data: synthetic AVA-shaped clips [B,36,3,400,400] and fixed anchor tubes (there is no dataset in this repository; the reference's
@@ -70,6 +71,10 @@ def main():
     ap.add_argument("--select-device", action="store_true",
                     help="implies --select, with the selection on the device (step_select_train, draws from the generator of --rng-seed): the whole "
                          "iteration is captured as ONE graph; the draws are not the reference's")
+    ap.add_argument("--grad-wire", default="fp32", choices=["fp32", "bf16"],
+                    help="what the gradient exchange puts on the link: the fp32 arena, or bfloat16 with error feedback (step_amd.dist.GradWire: half the "
+                         "bytes, the rounding error of what a rank sent is added to its next step's gradient)")
+    ap.add_argument("--no-wire-feedback", action="store_true", help="--grad-wire bf16 without the residual arena: round, sum, widen")
     ap.add_argument("--feed", default="none", choices=["none", "u8"])
     ap.add_argument("--augment", action="store_true",
                     help="--feed u8 only: uint8 frames at --src-size, the reference's TubeAugmentation (all four switches on, scripts/train_step.sh:55-58) "
@@ -106,10 +111,12 @@ def main():
         random.seed(1000 + rank)                                 # (the selection draws from the reference's two host RNG streams)
         np.random.seed(1000 + rank)
         w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=graphed, optimizer=a.optimizer,
-                                        dropout=a.dropout, rng_seed=a.rng_seed + rank, selection="device" if a.select_device else "host")
+                                        dropout=a.dropout, rng_seed=a.rng_seed + rank, selection="device" if a.select_device else "host",
+                                        grad_wire=a.grad_wire, wire_feedback=not a.no_wire_feedback)
     else:
         w = workloads.C4TrainStep(dev, batch=len(mine), tubes_per_clip=a.tubes, seed=123 + rank, dtype=tdt, capturable=graphed,
-                                  optimizer=a.optimizer, dropout=a.dropout, rng_seed=a.rng_seed + rank)
+                                  optimizer=a.optimizer, dropout=a.dropout, rng_seed=a.rng_seed + rank, grad_wire=a.grad_wire,
+                                  wire_feedback=not a.no_wire_feedback)
     for g in w.opt.param_groups:
         g["lr"] = a.lr
         if a.optimizer == "sgd":
@@ -189,11 +196,16 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=dev if torch.distributed.get_backend() == "nccl" else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         el = float(t.item())
+    # every rank prints the float64 sum of its parameter arena: replicas that apply the same exchanged gradient hold the same number
+    checksum = float(w.opt.flat_param.double().sum().item())
+    if rank != 0:
+        print(json.dumps({"rank": rank, "param_checksum": checksum}), flush=True)
     if rank == 0:
         print(json.dumps({"summary": True, "world_size": world, "global_batch": gb, "clips_per_rank": len(mine), "iters": a.iters,
                           "ms_per_iter": round(el / max(a.iters, 1) * 1e3, 3), "clips_per_s": round(gb * a.iters / el, 3),
                           "launch": ("hipGraph replay (%s)" % w.graph_mode) if w.graph is not None else "eager",
                           "gradient_exchange": _exchange_label(w, world),
+                          "grad_wire": a.grad_wire, "exchange_bytes_per_step": w.opt.numel * (2 if a.grad_wire == "bf16" else 4), "param_checksum": checksum,
                           "feed": a.feed + ("+augment" if a.augment else ""), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
                           "dropout": a.dropout, "rng_offset": w.rng.offset(), **({"selection": w.selection_ran} if a.select else {}),
                           **({"adam_steps": w.opt.step_count} if a.optimizer == "adam" else {})}), flush=True)
