@@ -5,7 +5,6 @@ below is one call into libstep_amd.so.  Activations are CHANNELS-LAST: a 5-D act
 contiguous tensor [N, D, H, W, C] (possibly a channel slice [.., c0:c1] of a wider buffer).
 """
 import ctypes
-import os
 
 import torch
 
@@ -23,48 +22,49 @@ PROFILE = None
 PROFILE_LIMIT = None
 WGRAD_WS = True        # fp32 weight gradients: partial-tile workspace + fixed-order sum instead of fp32 atomics (bit-reproducible; module switch for tests / A-B timing)
 WGRAD16_WS = True      # 16-bit weight gradients: partial-tile workspace + fixed-order sum instead of fp32 atomics (module switch for tests / A-B timing)
-class _Prof:
-    __slots__ = ("name", "flops", "bytes", "e0")
-
-    def __init__(self, name, flops, nbytes):
-        self.name, self.flops, self.bytes = name, flops, nbytes
-
-    def __enter__(self):
-        self.e0 = torch.cuda.Event(enable_timing=True)
-        self.e0.record()
-        return self
-
-    def __exit__(self, *exc):
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        PROFILE.append((self.name, self.flops, self.bytes, self.e0, e1))
-        return False
 
 
-class _NoProf:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NOPROF = _NoProf()
-
-
-def _run(launch, describe):
-    """Run one forward launch; under PROFILE record / time it (see the comment at PROFILE).  describe() -> (name, flops, bytes)."""
+def _run(launch, describe, limited=True):
+    """Run one launch; under PROFILE record / time it (see the comment at PROFILE).  describe() -> (name, flops, bytes).  Returns what
+    launch() returned (None where PROFILE_LIMIT kept it from running).  limited=False (the weight gradients): PROFILE_LIMIT does not
+    apply -- the launch always runs, between events whenever PROFILE is set."""
     if PROFILE is None:
-        launch()
-        return
+        return launch()
     name, flops, nbytes = describe()
-    if PROFILE_LIMIT is not None:
+    if limited and PROFILE_LIMIT is not None:
         PROFILE.append((name, flops, nbytes, None, None))
-        if len(PROFILE) <= PROFILE_LIMIT:
-            launch()
-        return
-    with _Prof(name, flops, nbytes):
-        launch()
+        return launch() if len(PROFILE) <= PROFILE_LIMIT else None
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    try:
+        return launch()
+    finally:
+        e1.record()
+        PROFILE.append((name, flops, nbytes, e0, e1))
+
+
+def _run_fused(launch, describe, what):
+    """_run for a fused form that the library may still refuse although the caller's own test admitted the shapes (its contract checks --
+    alignment, 32-bit offsets -- are stricter): launch() -> the library's status.  STEP_E_UNSUPPORTED / STEP_E_ALIGN: the record this
+    call appended is taken out again and the result is False (the caller returns None and its caller launches the unfused layers);
+    any other error raises."""
+    at = None if PROFILE is None else len(PROFILE)
+    rc = _run(launch, describe)
+    if rc in (-4, -5):
+        if at is not None:
+            del PROFILE[at]
+        return False
+    _capi.check(rc or 0, what)                                   # (None: PROFILE_LIMIT skipped the launch)
+    return True
+
+
+def _kernel_name(fn, *args):
+    """The kernel name one of the library's step_*_kernel_name entries writes for args ("" where it names none)."""
+    buf = ctypes.create_string_buffer(256)
+    fn(*args, buf, 256)
+    return buf.value.decode()
+
+
 _ES = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2}
 _TNAME = {torch.float32: "float", torch.bfloat16: "step::bf16_t", torch.float16: "step::f16_t"}
 
@@ -74,6 +74,21 @@ def _dt(t):
         return DT[t.dtype]
     except KeyError:
         raise RuntimeError("step_amd: unsupported dtype %s (float32 / bfloat16 / float16)" % t.dtype)
+
+
+def _typed(t, dtype):
+    """t as a contiguous tensor of dtype (itself where it is one already; None stays None)."""
+    if t is None:
+        return None
+    return t if (t.dtype == dtype and t.is_contiguous()) else t.to(dtype).contiguous()
+
+
+def _workspace(nbytes, device):
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def _float3(v):
+    return (ctypes.c_float * 3)(*[float(a) for a in v])
 
 
 def _chan_slice(t):
@@ -89,6 +104,24 @@ def _chan_slice(t):
             raise RuntimeError("step_amd: activation must be a channel slice of a dense channels-last buffer")
         exp *= t.size(i)
     return cs
+
+
+def _conv_desc(x, Cout, k, y_cs, *, cin=None, x_cs=None, relu=False, res=None, split=0, out2=None):
+    """struct step_conv_desc of a conv over the channels-last activation x [N,D,H,W,Cin] that writes Cout channels at channel stride
+    y_cs.  cin / x_cs: where the conv's input is not x as it stands (a concat, a layer evaluated on the fly); res / out2: the residual
+    and second-destination tensors, for their channel strides.  Channel slices arrive as offset pointers, so every *_coff stays 0."""
+    N, D, H, W, C = x.shape
+    return _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=C if cin is None else cin, Cout=Cout, kd=k[0], kh=k[1], kw=k[2],
+                          x_cstride=_chan_slice(x) if x_cs is None else x_cs, y_cstride=y_cs,
+                          res_cstride=0 if res is None else _chan_slice(res), relu=int(bool(relu)), split=int(split),
+                          y2_cstride=0 if out2 is None else _chan_slice(out2))
+
+
+def _conv_cost(x, Cout, k):
+    """Algorithmic (FLOPs, bytes) of a conv over x: input and output touched once, the weight once."""
+    Cin, taps = x.shape[-1], k[0] * k[1] * k[2]
+    pix = x.numel() // Cin
+    return 2.0 * pix * Cout * Cin * taps, (pix * (Cin + Cout) + Cout * Cin * taps) * _ES[x.dtype]
 
 
 def conv_packed_elems(Cout, Cin, k):
@@ -153,28 +186,17 @@ def conv_forward(x, w_packed, Cout, k, scale=None, shift=None, relu=True, res=No
     into (same N,D,H,W, Cout channels); returns out.  With split > 0 (1x1x1 only) output channels
     [0, split) go to `out` and [split, Cout) to `out2`."""
     L = _lib.lib()
-    N, D, H, W, Cin = x.shape
-    xcs = _chan_slice(x)
     if out is None:
+        N, D, H, W, _ = x.shape
         out = torch.empty((N, D, H, W, split if split else Cout), dtype=x.dtype, device=x.device)
-    ycs = _chan_slice(out)
-    d = _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=Cin, Cout=Cout, kd=k[0], kh=k[1], kw=k[2],
-                       x_cstride=xcs, x_coff=0, y_cstride=ycs, y_coff=0,
-                       res_cstride=(_chan_slice(res) if res is not None else 0), res_coff=0, relu=int(bool(relu)),
-                       split=int(split), y2_cstride=(_chan_slice(out2) if out2 is not None else 0), y2_coff=0)
-    def describe():
-        buf = ctypes.create_string_buffer(256)
-        L.step_conv_kernel_name(ctypes.byref(d), buf, 256)
-        pix = N * D * H * W
-        return (buf.value.decode(), 2.0 * pix * Cout * Cin * k[0] * k[1] * k[2],
-                (pix * (Cin + Cout) + Cout * Cin * k[0] * k[1] * k[2]) * _ES[x.dtype])
+    d = _conv_desc(x, Cout, k, _chan_slice(out), relu=relu, res=res, split=split, out2=out2)
     wsb = L.step_conv_workspace_bytes(ctypes.byref(d))            # > 0 only for the split-K Linear layers of the heads
-    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device) if wsb else None
+    ws = _workspace(wsb, x.device)
     def launch():
         _capi.check(L.step_conv_forward_ws(ctypes.byref(d), _lib.dptr(x), _lib.dptr(w_packed), _lib.dptr(scale), _lib.dptr(shift),
                                            _lib.dptr(res), _lib.dptr(out), _lib.dptr(out2), _lib.dptr(ws), wsb,
                                            _lib.stream_ptr(x.device)), "step_conv_forward_ws")
-    _run(launch, describe)
+    _run(launch, lambda: (_kernel_name(L.step_conv_kernel_name, ctypes.byref(d)),) + _conv_cost(x, Cout, k))
     return out
 
 
@@ -190,34 +212,21 @@ def conv_forward_cat(xa, xb, w_packed, Cout, scale=None, shift=None, relu=True, 
         return None
     if out is None:
         out = torch.empty((N, D, H, W, Cout), dtype=xa.dtype, device=xa.device)
-    d = _capi.ConvDesc(dtype=_dt(xa), N=N, D=D, H=H, W=W, Cin=Ca + Cb, Cout=Cout, kd=1, kh=1, kw=1, x_cstride=_chan_slice(xa), x_coff=0,
-                       y_cstride=_chan_slice(out), y_coff=0, res_cstride=(_chan_slice(res) if res is not None else 0), res_coff=0,
-                       relu=int(bool(relu)), split=0, y2_cstride=0, y2_coff=0)
-    dp = _capi.ConvDesc(dtype=_dt(xa), N=N, D=D, H=H, W=W, Cin=Ca + Cb, Cout=Cout, kd=1, kh=1, kw=1, x_cstride=Ca + Cb, x_coff=0,
-                        y_cstride=_chan_slice(out), y_coff=0, res_cstride=0, res_coff=0, relu=int(bool(relu)), split=0, y2_cstride=0, y2_coff=0)
+    k1 = (1, 1, 1)
+    d = _conv_desc(xa, Cout, k1, _chan_slice(out), cin=Ca + Cb, relu=relu, res=res)
+    dp = _conv_desc(xa, Cout, k1, _chan_slice(out), cin=Ca + Cb, x_cs=Ca + Cb, relu=relu)      # the layer over a materialised concat
     info = (ctypes.c_int * 10)()
     if L.step_conv_plan_info(ctypes.byref(dp), info, 10) != 0 or info[0] != 2:
         return None                                                      # (the streaming GEMM only: the test step_conv_forward_cat makes)
-    refused = []
-
-    def launch():
-        rc = L.step_conv_forward_cat(ctypes.byref(d), _lib.dptr(xa), int(Ca), _lib.dptr(xb), _chan_slice(xb), 0, _lib.dptr(w_packed),
-                                     _lib.dptr(scale), _lib.dptr(shift), _lib.dptr(res), _lib.dptr(out), None, _lib.stream_ptr(xa.device))
-        if rc in (-4, -5):
-            refused.append(rc)
-            return
-        _capi.check(rc, "step_conv_forward_cat")
 
     def describe():
         pix = N * D * H * W
         return ("void step::conv_pw2_kernel<%s, %d, %d>(step::ConvParams)" % (_TNAME[xa.dtype], min(info[2], 2) if info[3] == 8 else info[2], info[3]),
                 2.0 * pix * Cout * (Ca + Cb), (pix * (Ca + Cb + Cout * (2 if res is not None else 1)) + Cout * (Ca + Cb)) * _ES[xa.dtype])
-    _run(launch, describe)
-    if refused:
-        if PROFILE is not None and PROFILE and PROFILE[-1][0].startswith("void step::conv_pw2_kernel"):
-            PROFILE.pop()
-        return None
-    return out
+    ran = _run_fused(lambda: L.step_conv_forward_cat(ctypes.byref(d), _lib.dptr(xa), int(Ca), _lib.dptr(xb), _chan_slice(xb), 0, _lib.dptr(w_packed),
+                                                     _lib.dptr(scale), _lib.dptr(shift), _lib.dptr(res), _lib.dptr(out), None, _lib.stream_ptr(xa.device)),
+                     describe, "step_conv_forward_cat")
+    return out if ran else None
 
 
 POOL_CONV_FORCE_NB = 0  # pool_conv_forward: 1 | 2 force the accumulator depth of the pointwise workgroups inside the combined grid (A/B timing; 0: the library's choice)
@@ -232,9 +241,7 @@ def pool_conv_forward(x, w_packed, Cout, scale, shift, relu, out, out2=None, spl
     N, D, H, W, Cin = x.shape
     if x.dtype == torch.float32:
         return None
-    d = _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=Cin, Cout=Cout, kd=1, kh=1, kw=1, x_cstride=_chan_slice(x), x_coff=0,
-                       y_cstride=_chan_slice(out), y_coff=0, res_cstride=0, res_coff=0, relu=int(bool(relu)), split=int(split),
-                       y2_cstride=(_chan_slice(out2) if out2 is not None else 0), y2_coff=0)
+    d = _conv_desc(x, Cout, (1, 1, 1), _chan_slice(out), relu=relu, split=split, out2=out2)
     info = (ctypes.c_int * 10)()
     if L.step_conv_plan_info(ctypes.byref(d), info, 10) != 0 or info[0] != 2 or info[2] > POOL_CONV_MAX_NB:
         return None                                                      # (the test step_pool_conv_forward makes)
@@ -244,28 +251,16 @@ def pool_conv_forward(x, w_packed, Cout, scale, shift, relu, out, out2=None, spl
     if nbc <= 0:
         return None
     pooled = torch.empty((N, D, H, W, Cin), dtype=x.dtype, device=x.device)
-    refused = []
-
-    def launch():
-        with _capi.options(L, **force):
-            rc = L.step_pool_conv_forward(_dt(x), _lib.dptr(x), N, D, H, W, Cin, _chan_slice(x), 0, _lib.dptr(pooled), Cin, 0, ctypes.byref(d),
-                                          _lib.dptr(x), _lib.dptr(w_packed), _lib.dptr(scale), _lib.dptr(shift), _lib.dptr(out), _lib.dptr(out2),
-                                          _lib.stream_ptr(x.device))
-        if rc in (-4, -5):          # STEP_E_UNSUPPORTED / STEP_E_ALIGN: the library's own contract checks (alignment, 32-bit offsets, ...) are
-            refused.append(rc)      # stricter than the plan test above -- the caller then launches pool and conv one after the other
-            return
-        _capi.check(rc, "step_pool_conv_forward")
 
     def describe():
         pix = N * D * H * W
         return ("void step::pool333_pw_kernel<%s, %d>(%s const*, %s*, step::PoolParams, int, int, int, int, int, int, int, int, step::ConvParams)" % (
             _TNAME[x.dtype], nbc, _TNAME[x.dtype], _TNAME[x.dtype]), 2.0 * pix * Cout * Cin, (pix * (3 * Cin + Cout) + Cout * Cin) * _ES[x.dtype])
-    _run(launch, describe)
-    if refused:
-        if PROFILE is not None and PROFILE and PROFILE[-1][0].startswith("void step::pool333_pw_kernel"):
-            PROFILE.pop()
-        return None
-    return pooled
+    with _capi.options(L, **force):
+        ran = _run_fused(lambda: L.step_pool_conv_forward(_dt(x), _lib.dptr(x), N, D, H, W, Cin, _chan_slice(x), 0, _lib.dptr(pooled), Cin, 0, ctypes.byref(d),
+                                                          _lib.dptr(x), _lib.dptr(w_packed), _lib.dptr(scale), _lib.dptr(shift), _lib.dptr(out), _lib.dptr(out2),
+                                                          _lib.stream_ptr(x.device)), describe, "step_pool_conv_forward")
+    return pooled if ran else None
 
 
 def conv_forward_pre(x, w_packed, Cout, k, scale, shift, relu, pre, out=None):
@@ -278,34 +273,20 @@ def conv_forward_pre(x, w_packed, Cout, k, scale, shift, relu, pre, out=None):
     N, D, H, W, Cpre = x.shape
     if out is None:
         out = torch.empty((N, D, H, W, Cout), dtype=x.dtype, device=x.device)
-    d = _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=cmid, Cout=Cout, kd=k[0], kh=k[1], kw=k[2],
-                       x_cstride=_chan_slice(x), x_coff=0, y_cstride=_chan_slice(out), y_coff=0, res_cstride=0, res_coff=0,
-                       relu=int(bool(relu)), split=0, y2_cstride=0, y2_coff=0)
+    d = _conv_desc(x, Cout, k, _chan_slice(out), cin=cmid, relu=relu)
     info = (ctypes.c_int * 10)()
     if Cpre != 64 or cmid != 64 or x.dtype == torch.float32 or tuple(k) != (3, 3, 3) or L.step_conv_plan_info(ctypes.byref(d), info, 10) != 0 \
             or not (info[0] == 1 and info[4] == 1 and info[3] == 8 and info[1] in (0, 3)):
         return None                                                      # (the same test step_conv_forward_pre makes: STEP_E_UNSUPPORTED)
 
-    refused = []
-
-    def launch():
-        rc = L.step_conv_forward_pre(ctypes.byref(d), _lib.dptr(x), _lib.dptr(w_packed), _lib.dptr(scale), _lib.dptr(shift), _lib.dptr(pw),
-                                     _lib.dptr(pscale), _lib.dptr(pshift), int(Cpre), _lib.dptr(out), _lib.stream_ptr(x.device))
-        if rc in (-4, -5):          # the library's stricter contract (alignment of x / scale tables, x_coff, 32-bit offsets): fall back to two launches
-            refused.append(rc)
-            return
-        _capi.check(rc, "step_conv_forward_pre")
-
     def describe():
         pix = N * D * H * W
         return ("void step::conv_tap_pre_kernel<%s, %d, %d>(step::ConvParams)" % (_TNAME[x.dtype], info[1], info[2]),
                 2.0 * pix * (Cout * cmid * 27 + cmid * Cpre), (pix * (Cpre + Cout) + Cout * cmid * 27 + cmid * Cpre) * _ES[x.dtype])
-    _run(launch, describe)
-    if refused:
-        if PROFILE is not None and PROFILE and PROFILE[-1][0].startswith("void step::conv_tap_pre_kernel"):
-            PROFILE.pop()
-        return None
-    return out
+    ran = _run_fused(lambda: L.step_conv_forward_pre(ctypes.byref(d), _lib.dptr(x), _lib.dptr(w_packed), _lib.dptr(scale), _lib.dptr(shift), _lib.dptr(pw),
+                                                     _lib.dptr(pscale), _lib.dptr(pshift), int(Cpre), _lib.dptr(out), _lib.stream_ptr(x.device)),
+                     describe, "step_conv_forward_pre")
+    return out if ran else None
 
 
 def conv_forward_pre_pool(x, w_packed, Cout, k, scale, shift, relu, pre):
@@ -319,27 +300,15 @@ def conv_forward_pre_pool(x, w_packed, Cout, k, scale, shift, relu, pre):
     if Cpre != 64 or cmid != 64 or x.dtype == torch.float32 or tuple(k) != (3, 3, 3) or not relu:
         return None
     Hp, Wp = L.step_pool_out_size(H, 3, 2), L.step_pool_out_size(W, 3, 2)
-    d = _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=cmid, Cout=Cout, kd=3, kh=3, kw=3,
-                       x_cstride=_chan_slice(x), x_coff=0, y_cstride=Cout, y_coff=0, res_cstride=0, res_coff=0,
-                       relu=1, split=0, y2_cstride=0, y2_coff=0)
+    d = _conv_desc(x, Cout, k, Cout, cin=cmid, relu=True)
     wsb = L.step_conv_pre_pool_workspace_bytes(ctypes.byref(d))
     if not wsb:
         return None
     out = torch.empty((N, D, Hp, Wp, Cout), dtype=x.dtype, device=x.device)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+    ws = _workspace(wsb, x.device)
     info = (ctypes.c_int * 13)()
     if L.step_conv_pre_pool_plan_info(ctypes.byref(d), info, 13) != 0:     # the plan the POOLED call uses (it may re-plan a general-box layer onto 4 x 8 x 8 tiles)
         return None
-    refused = []
-
-    def launch():
-        # (the call in its two parts so that the instrumented legs time the conv launches and the seam pass separately)
-        rc = L.step_conv_forward_pre_pool_tiles(ctypes.byref(d), _lib.dptr(x), _lib.dptr(w_packed), _lib.dptr(scale), _lib.dptr(shift), _lib.dptr(pw),
-                                                _lib.dptr(pscale), _lib.dptr(pshift), int(Cpre), _lib.dptr(out), _lib.dptr(ws), wsb, _lib.stream_ptr(x.device))
-        if rc in (-4, -5):          # the library's stricter contract (alignment, 32-bit offsets): the caller falls back
-            refused.append(rc)
-            return
-        _capi.check(rc, "step_conv_forward_pre_pool_tiles")
 
     def finish():
         _capi.check(L.step_conv_pre_pool_finish(ctypes.byref(d), _lib.dptr(out), _lib.dptr(ws), wsb, _lib.stream_ptr(x.device)), "step_conv_pre_pool_finish")
@@ -354,10 +323,10 @@ def conv_forward_pre_pool(x, w_packed, Cout, k, scale, shift, relu, pre):
         pix = N * D * H * W
         return ("void step::conv_tap_pre_pool%s_kernel<%s, %d>(step::ConvParams)" % ("_persist" if info[12] else "", _TNAME[x.dtype], info[2]),
                 2.0 * pix * (Cout * cmid * 27 + cmid * Cpre), (pix * Cpre + N * D * Hp * Wp * Cout + Cout * cmid * 27 + cmid * Cpre) * _ES[x.dtype])
-    _run(launch, describe)
-    if refused:
-        if PROFILE is not None and PROFILE and PROFILE[-1][0].startswith("void step::conv_tap_pre_pool"):
-            PROFILE.pop()
+    # (the call in its two parts so that the instrumented legs time the conv launches and the seam pass separately)
+    if not _run_fused(lambda: L.step_conv_forward_pre_pool_tiles(ctypes.byref(d), _lib.dptr(x), _lib.dptr(w_packed), _lib.dptr(scale), _lib.dptr(shift),
+                                                                 _lib.dptr(pw), _lib.dptr(pscale), _lib.dptr(pshift), int(Cpre), _lib.dptr(out), _lib.dptr(ws), wsb,
+                                                                 _lib.stream_ptr(x.device)), describe, "step_conv_forward_pre_pool_tiles"):
         return None
     _run(finish, describe_finish)
     return out
@@ -369,62 +338,49 @@ def conv_forward_group(members):
     conv riding on the CUs they leave idle); otherwise they are launched one after the other.  members: (x, w_packed, Cout, k, scale, shift, relu, out) per conv, `out` a channel slice to write into.  Same results
     as conv_forward per member, bit for bit."""
     L = _lib.lib()
+    alone = lambda m: conv_forward(*m[:7], None, m[7])
+    group = [(m, _conv_desc(m[0], m[2], m[3], _chan_slice(m[7]), relu=m[6])) for m in members]
     # a member whose plan needs a caller-owned workspace (the split-K form of few-row / deep-K pointwise layers) goes through
     # conv_forward, which allocates it: inside the group call it would silently run on the tiled kernel instead -- a valid result, but
     # summed in another order than the same layer launched alone (bit-identity of the two forms is part of this function's contract)
-    solo = []
-    for m_ in members:
-        x, w_packed, Cout, k, scale, shift, relu, out = m_
-        if tuple(k) == (1, 1, 1):
-            N, D, H, W, Cin = x.shape
-            d = _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=Cin, Cout=Cout, kd=1, kh=1, kw=1, x_cstride=_chan_slice(x), x_coff=0,
-                               y_cstride=_chan_slice(out), y_coff=0, res_cstride=0, res_coff=0, relu=int(bool(relu)), split=0, y2_cstride=0, y2_coff=0)
-            if L.step_conv_workspace_bytes(ctypes.byref(d)):
-                solo.append(m_)
+    solo = [m for m, d in group if tuple(m[3]) == (1, 1, 1) and L.step_conv_workspace_bytes(ctypes.byref(d))]
     if solo:
-        members = [m_ for m_ in members if not any(m_ is s_ for s_ in solo)]
-        for (x, w_packed, Cout, k, scale, shift, relu, out) in solo:
-            conv_forward(x, w_packed, Cout, k, scale, shift, relu, None, out)
-        if not members:
+        group = [(m, d) for m, d in group if not any(m is s_ for s_ in solo)]
+        for m in solo:
+            alone(m)
+        if len(group) == 1:
+            alone(group[0][0])
+        if len(group) < 2:
             return
-        if len(members) == 1:
-            x, w_packed, Cout, k, scale, shift, relu, out = members[0]
-            conv_forward(x, w_packed, Cout, k, scale, shift, relu, None, out)
-            return
-    n = len(members)
+    members = [m for m, _ in group]
+    n = len(group)
     items = (_capi.ConvItem * n)()
-    descs, flops, nbytes = [], 0.0, 0
-    for it, (x, w_packed, Cout, k, scale, shift, relu, out) in zip(items, members):
-        N, D, H, W, Cin = x.shape
-        d = _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=Cin, Cout=Cout, kd=k[0], kh=k[1], kw=k[2],
-                           x_cstride=_chan_slice(x), x_coff=0, y_cstride=_chan_slice(out), y_coff=0, res_cstride=0, res_coff=0,
-                           relu=int(bool(relu)), split=0, y2_cstride=0, y2_coff=0)
-        descs.append(d)
+    for it, ((x, w_packed, Cout, k, scale, shift, relu, out), d) in zip(items, group):
         it.desc = ctypes.pointer(d)
         it.x, it.w_packed, it.y = x.data_ptr(), w_packed.data_ptr(), out.data_ptr()
         it.scale = None if scale is None else scale.data_ptr()
         it.shift = None if shift is None else shift.data_ptr()
         it.res = None
         _lib.dptr(x), _lib.dptr(out)                                # (refuse non-device tensors: there is no CPU fallback)
-        pix = N * D * H * W
-        flops += 2.0 * pix * Cout * Cin * k[0] * k[1] * k[2]
-        nbytes += (pix * (Cin + Cout) + Cout * Cin * k[0] * k[1] * k[2]) * _ES[x.dtype]
     stream = _lib.stream_ptr(members[0][0].device)
+    name = None
     if PROFILE is not None:
-        buf = ctypes.create_string_buffer(256)
-        L.step_conv_group_kernel_name(items, n, buf, 256)
-        if not buf.value:                                            # not merged: per-member attribution
-            for (x, w_packed, Cout, k, scale, shift, relu, out) in members:
-                conv_forward(x, w_packed, Cout, k, scale, shift, relu, None, out)
+        name = _kernel_name(L.step_conv_group_kernel_name, items, n)
+        if not name:                                                 # not merged: per-member attribution
+            for m in members:
+                alone(m)
             return
         pw = [m for m in members if tuple(m[3]) == (1, 1, 1)]
-        if pw and b"_pw_kernel" not in buf.value:                    # the pointwise member stays a launch of its own: attribute it separately
+        if pw and "_pw_kernel" not in name:                          # the pointwise member stays a launch of its own: attribute it separately
             conv_forward_group([m for m in members if tuple(m[3]) != (1, 1, 1)])
-            for (x, w_packed, Cout, k, scale, shift, relu, out) in pw:
-                conv_forward(x, w_packed, Cout, k, scale, shift, relu, None, out)
+            for m in pw:
+                alone(m)
             return
-    _run(lambda: _capi.check(L.step_conv_forward_group(items, n, stream), "step_conv_forward_group"),
-         lambda: (buf.value.decode(), flops, nbytes))
+
+    def describe():
+        costs = [_conv_cost(m[0], m[2], m[3]) for m in members]
+        return name, sum(c[0] for c in costs), sum(c[1] for c in costs)
+    _run(lambda: _capi.check(L.step_conv_forward_group(items, n, stream), "step_conv_forward_group"), describe)
 
 
 def _grad_slice(gy, vec):
@@ -439,6 +395,25 @@ def _grad_slice(gy, vec):
     return cs
 
 
+def _wgrad_setup(who, x, gy, Cout, k, into, w16):
+    """What conv_wgrad / conv_wgrad16 / conv_wgrad_partial (`who`, for the error text) share: gy in the kernel's gradient type (fp32, or
+    with w16 the 16-bit activation type as it arrives), read in place where it lies on the kernel's vector grid and densified where it
+    does not; dw = the validated `into` or a new fp32 [Cout, Cin, kd, kh, kw]; the descriptor.  -> (gy, dw, desc)"""
+    Cin = x.shape[-1]
+    if not w16 and gy.dtype != torch.float32:
+        gy = gy.float()
+    gcs = _grad_slice(gy, 8 if w16 else 4)
+    if gcs is None:
+        gy, gcs = gy.contiguous(), Cout
+    if into is not None:
+        if into.dtype != torch.float32 or not into.is_contiguous() or into.numel() != Cout * Cin * k[0] * k[1] * k[2]:
+            raise RuntimeError("step_amd: %s(into=...) wants a dense fp32 tensor of Cout*Cin*taps elements" % who)
+        dw = into
+    else:
+        dw = torch.empty((Cout, Cin) + tuple(k), dtype=torch.float32, device=x.device)
+    return gy, dw, _conv_desc(x, Cout, k, gcs)
+
+
 def conv_wgrad(x, gy, Cout, k, into=None):
     """Weight gradient of the stride-1 SAME conv: x channels-last [N,D,H,W,Cin] (any storage dtype, may be a channel
     slice), gy fp32 channels-last [N,D,H,W,Cout] (gradient w.r.t. the conv output before the affine epilogue).
@@ -446,33 +421,17 @@ def conv_wgrad(x, gy, Cout, k, into=None):
     .grad) the result is ACCUMULATED into it instead (the kernel's accumulate mode: no clear, no separate add)."""
     L = _lib.lib()
     N, D, H, W, Cin = x.shape
-    if gy.dtype != torch.float32:
-        gy = gy.float()
-    gcs = _grad_slice(gy, 4)
-    if gcs is None:
-        gy, gcs = gy.contiguous(), Cout
-    if into is not None:
-        if into.dtype != torch.float32 or not into.is_contiguous() or into.numel() != Cout * Cin * k[0] * k[1] * k[2]:
-            raise RuntimeError("step_amd: conv_wgrad(into=...) wants a dense fp32 tensor of Cout*Cin*taps elements")
-        dw = into
-    else:
-        dw = torch.empty((Cout, Cin) + tuple(k), dtype=torch.float32, device=x.device)
-    d = _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=Cin, Cout=Cout, kd=k[0], kh=k[1], kw=k[2],
-                       x_cstride=_chan_slice(x), x_coff=0, y_cstride=gcs, y_coff=0, res_cstride=0, res_coff=0, relu=0,
-                       split=0, y2_cstride=0, y2_coff=0)
-    prof = _NOPROF
-    if PROFILE is not None:
+    gy, dw, d = _wgrad_setup("conv_wgrad", x, gy, Cout, k, into, False)
+
+    def describe():
         pix = N * D * H * W
         # algorithmic: x and dy read once, dw written once (fp32); the kernel variant is chosen by Cin inside the library
-        nbuf = ctypes.create_string_buffer(256)
-        L.step_conv_wgrad_kernel_name(ctypes.byref(d), 0, nbuf, 256)
-        prof = _Prof(nbuf.value.decode(), 2.0 * pix * Cout * Cin * k[0] * k[1] * k[2],
-                     pix * (Cin * x.element_size() + Cout * 4) + 4.0 * Cout * Cin * k[0] * k[1] * k[2])
+        return (_kernel_name(L.step_conv_wgrad_kernel_name, ctypes.byref(d), 0), 2.0 * pix * Cout * Cin * k[0] * k[1] * k[2],
+                pix * (Cin * x.element_size() + Cout * 4) + 4.0 * Cout * Cin * k[0] * k[1] * k[2])
     wsb = L.step_conv_wgrad_workspace_bytes(ctypes.byref(d)) if WGRAD_WS else 0     # partial tiles + fixed-order sum: no atomics, deterministic
-    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device) if wsb else None
-    with prof:
-        _capi.check(L.step_conv_wgrad_ws(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(dw), int(into is not None),
-                                         _lib.dptr(ws), wsb, _lib.stream_ptr(x.device)), "step_conv_wgrad_ws")
+    ws = _workspace(wsb, x.device)
+    _run(lambda: _capi.check(L.step_conv_wgrad_ws(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(dw), int(into is not None),
+                                                  _lib.dptr(ws), wsb, _lib.stream_ptr(x.device)), "step_conv_wgrad_ws"), describe, limited=False)
     return dw
 
 
@@ -483,30 +442,16 @@ def conv_wgrad16(x, gy, Cout, k, into=None):
     N, D, H, W, Cin = x.shape
     if gy.dtype != x.dtype or x.dtype == torch.float32:
         raise RuntimeError("step_amd: conv_wgrad16 wants x and gy in the same 16-bit dtype")
-    gcs = _grad_slice(gy, 8)
-    if gcs is None:
-        gy, gcs = gy.contiguous(), Cout
-    if into is not None:
-        if into.dtype != torch.float32 or not into.is_contiguous() or into.numel() != Cout * Cin * k[0] * k[1] * k[2]:
-            raise RuntimeError("step_amd: conv_wgrad16(into=...) wants a dense fp32 tensor of Cout*Cin*taps elements")
-        dw = into
-    else:
-        dw = torch.empty((Cout, Cin) + tuple(k), dtype=torch.float32, device=x.device)
-    d = _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=Cin, Cout=Cout, kd=k[0], kh=k[1], kw=k[2],
-                       x_cstride=_chan_slice(x), x_coff=0, y_cstride=gcs, y_coff=0, res_cstride=0, res_coff=0, relu=0,
-                       split=0, y2_cstride=0, y2_coff=0)
-    prof = _NOPROF
-    if PROFILE is not None:
+    gy, dw, d = _wgrad_setup("conv_wgrad16", x, gy, Cout, k, into, True)
+
+    def describe():
         pix = N * D * H * W
-        nbuf = ctypes.create_string_buffer(256)
-        L.step_conv_wgrad_kernel_name(ctypes.byref(d), 1, nbuf, 256)
-        prof = _Prof(nbuf.value.decode(), 2.0 * pix * Cout * Cin * k[0] * k[1] * k[2],
-                     pix * (Cin + Cout) * x.element_size() + 4.0 * Cout * Cin * k[0] * k[1] * k[2])
+        return (_kernel_name(L.step_conv_wgrad_kernel_name, ctypes.byref(d), 1), 2.0 * pix * Cout * Cin * k[0] * k[1] * k[2],
+                pix * (Cin + Cout) * x.element_size() + 4.0 * Cout * Cin * k[0] * k[1] * k[2])
     wsb = L.step_conv_wgrad16_workspace_bytes(ctypes.byref(d)) if WGRAD16_WS else 0   # > 0: the LDS-tiled form with a two-stage sum
-    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device) if wsb else None
-    with prof:
-        _capi.check(L.step_conv_wgrad16_ws(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(dw), int(into is not None),
-                                           _lib.dptr(ws), wsb, _lib.stream_ptr(x.device)), "step_conv_wgrad16_ws")
+    ws = _workspace(wsb, x.device)
+    _run(lambda: _capi.check(L.step_conv_wgrad16_ws(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(dw), int(into is not None),
+                                                    _lib.dptr(ws), wsb, _lib.stream_ptr(x.device)), "step_conv_wgrad16_ws"), describe, limited=False)
     return dw
 
 
@@ -515,24 +460,10 @@ def conv_wgrad_partial(x, gy, Cout, k, into=None):
     writes the partial tiles and returns (dw, item, ws) -- pass the items of several layers to wgrad_reduce_group (one launch) and keep
     `ws` alive until then.  item.kind == 0: nothing is pending."""
     L = _lib.lib()
-    N, D, H, W, Cin = x.shape
     w16 = gy.dtype == x.dtype and x.dtype != torch.float32
-    if not w16 and gy.dtype != torch.float32:
-        gy = gy.float()
-    gcs = _grad_slice(gy, 8 if w16 else 4)
-    if gcs is None:
-        gy, gcs = gy.contiguous(), Cout
-    if into is not None:
-        if into.dtype != torch.float32 or not into.is_contiguous() or into.numel() != Cout * Cin * k[0] * k[1] * k[2]:
-            raise RuntimeError("step_amd: conv_wgrad_partial(into=...) wants a dense fp32 tensor of Cout*Cin*taps elements")
-        dw = into
-    else:
-        dw = torch.empty((Cout, Cin) + tuple(k), dtype=torch.float32, device=x.device)
-    d = _capi.ConvDesc(dtype=_dt(x), N=N, D=D, H=H, W=W, Cin=Cin, Cout=Cout, kd=k[0], kh=k[1], kw=k[2],
-                       x_cstride=_chan_slice(x), x_coff=0, y_cstride=gcs, y_coff=0, res_cstride=0, res_coff=0, relu=0,
-                       split=0, y2_cstride=0, y2_coff=0)
+    gy, dw, d = _wgrad_setup("conv_wgrad_partial", x, gy, Cout, k, into, w16)
     wsb = (L.step_conv_wgrad16_workspace_bytes if w16 else L.step_conv_wgrad_workspace_bytes)(ctypes.byref(d))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device) if wsb else None
+    ws = _workspace(wsb, x.device)
     item = _capi.WgradReduceItem()
     _capi.check(L.step_conv_wgrad_partial(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), int(w16), _lib.dptr(dw), int(into is not None), _lib.dptr(ws), wsb,
                                           ctypes.byref(item), _lib.stream_ptr(x.device)), "step_conv_wgrad_partial")
@@ -568,9 +499,7 @@ def act_grad(y, gy, scale, relu, want_f32=True, want_act=False):
     same = y.dtype == torch.float32
     g32 = torch.empty(y.shape, dtype=torch.float32, device=y.device) if (want_f32 or (want_act and same)) else None
     gact = torch.empty(y.shape, dtype=y.dtype, device=y.device) if (want_act and not same) else None
-    sc = None
-    if scale is not None:
-        sc = scale if (scale.dtype == torch.float32 and scale.is_contiguous()) else scale.float().contiguous()
+    sc = _typed(scale, torch.float32)
     L = _lib.lib()
     _capi.check(L.step_act_grad(_dt(y), _lib.dptr(y), ycs, DT[gy.dtype], _lib.dptr(gy), gcs, _lib.dptr(sc), M, C, int(bool(relu)),
                                 _lib.dptr(g32), _lib.dptr(gact), _lib.stream_ptr(y.device)), "step_act_grad")
@@ -586,8 +515,7 @@ def bn_train_forward(z, gamma, beta, running_mean, running_var, eps, momentum, r
     zcs = _chan_slice(z)
     if out is None:
         out = torch.empty(z.shape, dtype=z.dtype, device=z.device)
-    f32 = lambda t: None if t is None else (t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous())
-    g_, b_ = f32(gamma), f32(beta)
+    g_, b_ = _typed(gamma, torch.float32), _typed(beta, torch.float32)
     for t in (running_mean, running_var):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise RuntimeError("step_amd: BatchNorm running statistics must be contiguous fp32 tensors")
@@ -619,7 +547,7 @@ def bn_train_backward(z, y, gy, gamma, save_mean, save_invstd, relu):
     gz = torch.empty(z.shape, dtype=z.dtype, device=z.device)
     ggamma = torch.empty(C, dtype=torch.float32, device=z.device)
     gbeta = torch.empty(C, dtype=torch.float32, device=z.device)
-    g_ = None if gamma is None else (gamma if (gamma.dtype == torch.float32 and gamma.is_contiguous()) else gamma.float().contiguous())
+    g_ = _typed(gamma, torch.float32)
     wsb = L.step_bn_train_workspace_bytes(M, C)
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=z.device)
     _capi.check(L.step_bn_train_backward(_dt(z), _lib.dptr(z), _chan_slice(z), _lib.dptr(y), _chan_slice(y), DT[gy.dtype], _lib.dptr(gy), gcs, M, C,
@@ -629,20 +557,23 @@ def bn_train_backward(z, y, gy, gamma, save_mean, save_invstd, relu):
     return gz, ggamma, gbeta
 
 
+def _stem_out_size(T, H, W):
+    """Output (frames, rows, columns) of the 7x7x7 / 2 stem."""
+    return (T - 2) // 2 + 1, (H - 2) // 2 + 1, (W - 2) // 2 + 1
+
+
 def stem_forward(x, w_packed, Cout, scale, shift, out=None, relu=True):
     """x: [N,T,3,H,W] contiguous (the reference's input layout) -> channels-last [N,To,Ho,Wo,Cout]"""
     L = _lib.lib()
     N, T, C, H, W = x.shape
     if C != 3 or not x.is_contiguous():
         raise RuntimeError("step_amd: stem expects a contiguous [N,T,3,H,W] clip")
-    To, Ho, Wo = (T - 2) // 2 + 1, (H - 2) // 2 + 1, (W - 2) // 2 + 1
+    To, Ho, Wo = _stem_out_size(T, H, W)
     if out is None:
         out = torch.empty((N, To, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
     def describe():
         pix = N * To * Ho * Wo
-        buf = ctypes.create_string_buffer(256)
-        _capi.check(L.step_stem_kernel_name(_dt(x), buf, 256), "step_stem_kernel_name")
-        return buf.value.decode(), 2.0 * pix * Cout * 1029, (x.numel() + pix * Cout + Cout * 1029) * _ES[x.dtype]
+        return _kernel_name(L.step_stem_kernel_name, _dt(x)), 2.0 * pix * Cout * 1029, (x.numel() + pix * Cout + Cout * 1029) * _ES[x.dtype]
     def launch():
         _capi.check(L.step_stem_forward(_dt(x), _lib.dptr(x), N, T, H, W, _lib.dptr(w_packed), _lib.dptr(scale), _lib.dptr(shift),
                                         int(bool(relu)), Cout, _lib.dptr(out), _chan_slice(out), 0, _lib.stream_ptr(x.device)), "step_stem_forward")
@@ -661,10 +592,10 @@ def stem_pool_forward(x, w_packed, Cout, scale, shift):
     wsb = L.step_stem_pool_workspace_bytes(_dt(x), N, T, H, W, Cout)
     if not wsb:
         return None
-    To, Ho, Wo = (T - 2) // 2 + 1, (H - 2) // 2 + 1, (W - 2) // 2 + 1
+    To, Ho, Wo = _stem_out_size(T, H, W)
     Hp, Wp = L.step_pool_out_size(Ho, 3, 2), L.step_pool_out_size(Wo, 3, 2)
     out = torch.empty((N, To, Hp, Wp, Cout), dtype=x.dtype, device=x.device)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+    ws = _workspace(wsb, x.device)
 
     def describe():
         pix = N * To * Ho * Wo
@@ -700,16 +631,15 @@ def stem_pool_forward_u8(frames, dtype, w_packed, Cout, scale, shift, u8_scale=2
             or dtype not in (torch.bfloat16, torch.float16):
         return None
     N, T, H, W, _ = frames.shape
-    code = _capi.BF16 if dtype == torch.bfloat16 else _capi.F16
+    code = DT[dtype]
     wsb = L.step_stem_pool_workspace_bytes(code, N, T, H, W, Cout)
     if not wsb:
         return None
-    To, Ho, Wo = (T - 2) // 2 + 1, (H - 2) // 2 + 1, (W - 2) // 2 + 1
+    To, Ho, Wo = _stem_out_size(T, H, W)
     Hp, Wp = L.step_pool_out_size(Ho, 3, 2), L.step_pool_out_size(Wo, 3, 2)
     out = torch.empty((N, To, Hp, Wp, Cout), dtype=dtype, device=frames.device)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=frames.device)
-    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
-    sd = (ctypes.c_float * 3)(*[float(v) for v in std])
+    ws = _workspace(wsb, frames.device)
+    m, sd = _float3(mean), _float3(std)
 
     def describe():
         pix = N * To * Ho * Wo
@@ -731,7 +661,7 @@ def stem_wgrad(x, gy, Cout):
     gy = gy.float().contiguous()
     dw = torch.empty((Cout, 3, 7, 7, 7), dtype=torch.float32, device=x.device)
     wsb = L.step_stem_wgrad_workspace_bytes(N, T, H, W, Cout) if WGRAD_WS else 0
-    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device) if wsb else None
+    ws = _workspace(wsb, x.device)
     _capi.check(L.step_stem_wgrad_ws(_dt(x), _lib.dptr(x), N, T, H, W, _lib.dptr(gy), Cout, _lib.dptr(dw), 0, _lib.dptr(ws), wsb,
                                      _lib.stream_ptr(x.device)), "step_stem_wgrad_ws")
     return dw
@@ -748,16 +678,15 @@ def stem_wgrad16(x, gy, Cout):
     if not wsb:
         return None
     x, gy = x.contiguous(), gy.contiguous()
-    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+    ws = _workspace(wsb, x.device)
     dw = torch.empty((Cout, 3, 7, 7, 7), dtype=torch.float32, device=x.device)
-    prof = _NOPROF
-    if PROFILE is not None:
+
+    def describe():
         pix = gy.numel() // Cout
-        prof = _Prof("void step::stem_wgrad16_kernel<%s>(step::StemWgrad16Params)" % _TNAME[x.dtype], 2.0 * pix * Cout * 1029,
-                     (x.numel() + gy.numel()) * x.element_size())
-    with prof:
-        _capi.check(L.step_stem_wgrad16(_dt(x), _lib.dptr(x), N, T, H, W, _lib.dptr(gy), Cout, _lib.dptr(dw), 0, _lib.dptr(ws), wsb,
-                                        _lib.stream_ptr(x.device)), "step_stem_wgrad16")
+        return ("void step::stem_wgrad16_kernel<%s>(step::StemWgrad16Params)" % _TNAME[x.dtype], 2.0 * pix * Cout * 1029,
+                (x.numel() + gy.numel()) * x.element_size())
+    _run(lambda: _capi.check(L.step_stem_wgrad16(_dt(x), _lib.dptr(x), N, T, H, W, _lib.dptr(gy), Cout, _lib.dptr(dw), 0, _lib.dptr(ws), wsb,
+                                                 _lib.stream_ptr(x.device)), "step_stem_wgrad16"), describe, limited=False)
     return dw
 
 
@@ -832,11 +761,8 @@ def clip_from_u8(frames, dtype=torch.float32, scale=2, mean=(0.0, 0.0, 0.0), std
         if tuple(out.shape) != (N, T, 3, H, W) or not out.is_contiguous() or (not host and out.device != frames.device):
             raise RuntimeError("step_amd: clip_from_u8(out=...) wants a contiguous [N,T,3,H,W] tensor on the frames' device")
         dtype = out.dtype
-    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
-    sd = (ctypes.c_float * 3)(*[float(v) for v in std])
-    code = {torch.float32: _capi.F32, torch.bfloat16: _capi.BF16, torch.float16: _capi.F16}[dtype]
     src = ctypes.c_void_p(frames.data_ptr()) if host else _lib.dptr(frames)
-    _capi.check(L.step_clip_from_u8(src, N, T, H, W, int(scale), m, sd, code, _lib.dptr(out), _lib.stream_ptr(out.device)),
+    _capi.check(L.step_clip_from_u8(src, N, T, H, W, int(scale), _float3(mean), _float3(std), DT[dtype], _lib.dptr(out), _lib.stream_ptr(out.device)),
                 "step_clip_from_u8")
     return out
 
@@ -1011,7 +937,7 @@ def nms_batched(boxes, scores, counts, threshold):
     if G == 0 or kmax == 0:
         return keep
     nb = L.step_nms_scratch_bytes(G, kmax)
-    scratch = torch.empty(nb, dtype=torch.uint8, device=boxes.device) if nb else None
+    scratch = _workspace(nb, boxes.device)
     fn = L.step_nms_batched_f64 if f64 else L.step_nms_batched
     _capi.check(fn(_lib.dptr(boxes), _lib.dptr(scores), _lib.dptr(counts), G, kmax, float(threshold),
                    _lib.dptr(keep), _lib.dptr(scratch), _lib.stream_ptr(boxes.device)), "step_nms_batched")
@@ -1043,7 +969,7 @@ def detect_compact(keep, boxes, scores, tube_start, width, height):
     I, B, NC, kmax = keep.shape
     dev = keep.device
     cap = NC * kmax
-    boxes = [b if (b.dtype == torch.float32 and b.is_contiguous()) else b.float().contiguous() for b in boxes]
+    boxes = [_typed(b, torch.float32) for b in boxes]
     scores = [s_ if (s_.dtype == torch.float32 and s_.stride(1) == 1) else s_.float().contiguous() for s_ in scores]
     ob = torch.empty((I * B * cap, 4), dtype=torch.float32, device=dev)
     os_ = torch.empty((I * B * cap,), dtype=torch.float32, device=dev)
@@ -1069,10 +995,8 @@ def detect_merge(boxes, counts, global_thresh, order=None, sel_counts=None):
         raise ValueError("detect_merge: order and sel_counts go together")
     G, cap = boxes.shape[0], boxes.shape[1]
     dev = boxes.device
-    i32 = lambda t: None if t is None else (t if (t.dtype == torch.int32 and t.is_contiguous()) else t.to(torch.int32).contiguous())
-    if boxes.dtype != torch.float32 or not boxes.is_contiguous():
-        boxes = boxes.float().contiguous()
-    counts, order, sel_counts = i32(counts), i32(order), i32(sel_counts)
+    boxes = _typed(boxes, torch.float32)
+    counts, order, sel_counts = _typed(counts, torch.int32), _typed(order, torch.int32), _typed(sel_counts, torch.int32)
     cluster = torch.empty((G, cap), dtype=torch.int32, device=dev)
     lead_pos = torch.empty((G, cap), dtype=torch.int32, device=dev)
     merged = torch.empty((G, cap, 4), dtype=torch.float32, device=dev)
@@ -1088,17 +1012,12 @@ def round_sig4(x, status):
     four-significant-digit text of test.py:213 parsed back).  status: an int32 tensor of one element on x's device that the launch sets to
     1 where a value is outside [1e-9, 1e4) in magnitude, inf or NaN (its result is NaN); the caller clears and reads it."""
     L = _lib.lib()
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        x = x.float().contiguous()
+    x = _typed(x, torch.float32)
     if status.dtype != torch.int32 or status.numel() != 1 or status.device != x.device:
         raise ValueError("round_sig4: status must be one int32 on the input's device")
     out = torch.empty(x.shape, dtype=torch.float64, device=x.device)
     _capi.check(L.step_round_sig4(_lib.dptr(x), x.numel(), _lib.dptr(out), _lib.dptr(status), _lib.stream_ptr(x.device)), "step_round_sig4")
     return out
-
-
-def _typed(t, dtype):
-    return t if (t.dtype == dtype and t.is_contiguous()) else t.to(dtype).contiguous()
 
 
 def eval_match(det_boxes, det_cls, det_start, gt_boxes, gt_cls, gt_start, gt_max, thresh):

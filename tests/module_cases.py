@@ -1540,6 +1540,142 @@ def _nms_operator_api(dev, nms):
     assert e.numel() == 0 and e.dtype == torch.int64
 
 
+class _OnDevice(torch.Tensor):
+    """A host tensor that answers is_cuda with True: ops.stem_pool_forward_u8 asks that of its frames before anything else, and under the
+    interpreter patch (tests.emul.patch) host tensors stand in for device memory everywhere else already."""
+    is_cuda = property(lambda self: True)
+
+
+def ops_profile_calls(dev):
+    """One call of every instrumented wrapper of step_amd.ops, as (tag, planner options, thunk) -- the smallest shape (and the options) of
+    the matching tests/kernel_cases.py case each.  Shared by case_ops_profile_records and tools/make_ops_profile_golden.py; under
+    ops.PROFILE_LIMIT = 0 no thunk launches anything, so the tensors are uninitialised and the weights one dummy tensor."""
+    from step_amd import ops
+    bf, fh, f32 = torch.bfloat16, torch.float16, torch.float32
+    t = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    w = t((1,), f32)                                              # stands for every packed weight / scale / shift (never read)
+    k3, k1 = (3, 3, 3), (1, 1, 1)
+    pre = (w, w, w, 64)
+
+    def group(dt, sp, chans, pw=None):
+        """two 3x3x3 members on slices of one buffer (+ a pointwise member on a buffer of its own), outputs = slices of one buffer"""
+        ci0, co0, ci1, co1 = chans
+        src = t(sp + (ci0 + ci1,), dt)
+        dst = t(sp + (8 + co0 + co1 + (pw[1] if pw else 0) + 8,), dt)
+        ms = [(src[..., :ci0], w, co0, k3, w, w, True, dst[..., 8:8 + co0]),
+              (src[..., ci0:], w, co1, k3, w, w, True, dst[..., 8 + co0:8 + co0 + co1])]
+        if pw:
+            ms.append((t(sp + (pw[0],), dt), w, pw[1], k1, w, w, True, dst[..., 8 + co0 + co1:8 + co0 + co1 + pw[1]]))
+        return lambda: ops.conv_forward_group(ms)
+
+    frames = t((2, 3, 34, 36, 3), torch.uint8)
+    if dev == "cpu":
+        frames = frames.as_subclass(_OnDevice)
+    return [
+        ("conv_forward/3x3x3", {}, lambda: ops.conv_forward(t((1, 2, 8, 16, 16), bf), w, 32, k3, w, w)),
+        ("conv_forward/3x3x3_odd_f32", {}, lambda: ops.conv_forward(t((2, 3, 9, 7, 24), f32), w, 48, k3, w, w)),
+        ("conv_forward/pointwise_split", {}, lambda: ops.conv_forward(t((2, 2, 5, 7, 48), bf), w, 96, k1, w, w, out=t((2, 2, 5, 7, 64), bf)[..., 8:48],
+                                                                      out2=t((2, 2, 5, 7, 72), bf)[..., 16:72], split=40)),
+        ("conv_forward/splitk_linear", {}, lambda: ops.conv_forward(t((5, 1, 1, 1, 2056), bf), w, 12, k1, None, w, relu=False, res=t((5, 1, 1, 1, 12), bf))),
+        ("conv_forward_cat/res_slices", {}, lambda: ops.conv_forward_cat(t((1, 1, 64, 65, 136), bf)[..., 32:128], t((1, 1, 64, 65, 96), bf)[..., 8:80], w, 136, w, w,
+                                                                         res=t((1, 1, 64, 65, 136), bf))),
+        ("conv_forward_cat/whole_tiles", {}, lambda: ops.conv_forward_cat(t((1, 1, 64, 64, 64), fh), t((1, 1, 64, 64, 64), fh), w, 128, relu=False)),
+        ("pool_conv_forward/split", {}, lambda: ops.pool_conv_forward(t((8, 3, 14, 14, 136), bf), w, 104, w, w, True, t((8, 3, 14, 14, 48), bf)[..., 8:],
+                                                                      out2=t((8, 3, 14, 14, 64), bf), split=40)),
+        ("pool_conv_forward/one_destination", {}, lambda: ops.pool_conv_forward(t((8, 3, 14, 14, 128), fh), w, 96, w, w, True, t((8, 3, 14, 14, 96), fh))),
+        ("conv_forward_pre/general_box", {}, lambda: ops.conv_forward_pre(t((3, 8, 14, 14, 64), fh), w, 200, k3, w, w, True, pre)),
+        ("conv_forward_pre/tiles_4x8x8", dict(conv_slots=4, conv_nb=3, conv_waves=8), lambda: ops.conv_forward_pre(t((1, 4, 24, 24, 64), bf), w, 192, k3, w, w, True, pre)),
+        ("conv_forward_pre_pool/tiles_4x8x8", dict(conv_slots=4, conv_nb=3, conv_waves=8),
+         lambda: ops.conv_forward_pre_pool(t((1, 4, 24, 24, 64), bf), w, 192, k3, w, w, True, pre)),
+        ("conv_forward_pre_pool/persist", dict(conv_slots=8, conv_nb=3, conv_waves=8, conv_gen=0),
+         lambda: ops.conv_forward_pre_pool(t((1, 8, 24, 24, 64), bf), w, 192, k3, w, w, True, pre)),
+        ("conv_forward_group/merged", {}, group(bf, (1, 8, 14, 14), (64, 200, 64, 40))),
+        ("conv_forward_group/unmerged_f32", {}, group(f32, (1, 8, 14, 14), (64, 96, 64, 40))),
+        ("conv_forward_group/pointwise_rides", dict(conv_group_pw=256), group(bf, (3, 8, 14, 14), (64, 72, 64, 40), (128, 96))),
+        ("conv_forward_group/pointwise_behind", dict(conv_group_pw=0), group(bf, (3, 8, 14, 14), (64, 72, 64, 40), (128, 96))),
+        ("stem_forward", {}, lambda: ops.stem_forward(t((2, 5, 3, 18, 22), bf), w, 40, w, w)),
+        ("stem_pool_forward", {}, lambda: ops.stem_pool_forward(t((1, 4, 3, 72, 80), bf), w, 64, w, w)),
+        ("stem_pool_forward_u8", {}, lambda: ops.stem_pool_forward_u8(frames, fh, w, 64, w, w, 1, (0.1, -0.2, 0.3), (1.0, 0.5, 2.0))),
+        ("maxpool_tf/separable", {}, lambda: ops.maxpool_tf(t((2, 5, 9, 7, 16), bf), (1, 3, 3), (1, 2, 2))),
+        ("maxpool_tf/direct", {}, lambda: ops.maxpool_tf(t((2, 5, 9, 7, 16), f32), (2, 2, 2), (2, 2, 2))),
+    ]
+
+
+def ops_profile_records(dev):
+    """{tag: [[kernel name, algorithmic FLOPs, algorithmic bytes], ...]} of ops_profile_calls under PROFILE_LIMIT = 0 (recorded, not run)."""
+    from step_amd import _capi, _lib, ops
+    out = {}
+    for tag, opts, call in ops_profile_calls(dev):
+        ops.PROFILE, ops.PROFILE_LIMIT = [], 0
+        try:
+            with _capi.options(_lib.lib(), **opts):
+                call()
+            out[tag] = [list(r[:3]) for r in ops.PROFILE]
+            assert all(r[3] is None and r[4] is None for r in ops.PROFILE), tag
+        finally:
+            ops.PROFILE, ops.PROFILE_LIMIT = None, None
+    return out
+
+
+def case_ops_profile_records(dev, golden):
+    """The records bench.py builds its roofline from -- (kernel name, algorithmic FLOPs, algorithmic bytes) of every instrumented wrapper
+    of step_amd.ops -- equal tests/golden/ops_profile_records.json (tools/make_ops_profile_golden.py) EXACTLY.  Interpreter only: the
+    planner's choices, and with them the names, follow the device the library was built for; nothing is launched (PROFILE_LIMIT = 0)."""
+    want = json.load(open(os.path.join(GOLDEN, "ops_profile_records.json")))
+    got = ops_profile_records(dev)
+    assert list(got) == list(want), (list(got), list(want))
+    for tag in want:
+        assert len(got[tag]) >= 1, tag                             # (a wrapper that returned None recorded nothing: a wrong shape)
+        assert got[tag] == want[tag], (tag, got[tag], want[tag])
+
+
+def case_fused_forms_refused_fall_back(dev, golden):
+    """A fused form the Python pre-check admits and the LIBRARY refuses returns None and leaves no record in ops.PROFILE -- with the
+    launches recorded and executed (PROFILE_LIMIT = 1 << 30) and without instrumentation.  The refused input is the [..., 4:68] channel
+    slice of a 72-channel 16-bit buffer (it starts 8 bytes into a 16-byte vector: STEP_E_ALIGN); the [..., 8:72] slice of the same buffer
+    has the same shape and strides -- all the pre-checks look at -- and is accepted, as is the dense tensor, so it is the library that
+    says no, before any launch.  An accepted call leaves exactly its own records (one; two where a seam pass follows).
+      * conv_forward_pre, conv_forward_pre_pool: x is the slice (the 4 x 8 x 8-tile layer of the kernel cases, with their options);
+      * conv_forward_cat: the second source is the slice;
+      * pool_conv_forward: x is the slice (136-channel buffer: 128 channels).
+    All four are admitted and refused both on the interpreter and on the MI355X (the last two need a planner that streams the pointwise
+    layer at these sizes)."""
+    from step_amd import _capi, _lib, ops
+    L = _lib.lib()
+    bf = torch.bfloat16
+    g = torch.Generator().manual_seed(9)
+    rnd = lambda *shape: torch.randn(shape, generator=g).to(dev)
+    one, zero = torch.ones(128, device=dev), torch.zeros(128, device=dev)
+    pre = (ops.pack_conv_weight(rnd(64, 64, 1, 1, 1) / 8, bf), one, zero, 64)
+    w3 = ops.pack_conv_weight(rnd(64, 64, 3, 3, 3) / 40, bf)
+    wc = ops.pack_conv_weight(rnd(128, 128, 1, 1, 1) / 12, bf)
+    wq = ops.pack_conv_weight(rnd(96, 128, 1, 1, 1) / 12, bf)
+    xa = rnd(1, 1, 64, 64, 64).to(bf)
+    tiles = dict(conv_gen=0, conv_waves=8)
+    # form: (planner options, call, the wide buffer, records of an accepted call)
+    forms = {
+        "conv_forward_pre": (tiles, lambda x: ops.conv_forward_pre(x, w3, 64, (3, 3, 3), one, zero, True, pre), rnd(1, 8, 16, 8, 72).to(bf), 1),
+        "conv_forward_pre_pool": (tiles, lambda x: ops.conv_forward_pre_pool(x, w3, 64, (3, 3, 3), one, zero, True, pre), rnd(1, 8, 16, 8, 72).to(bf), 2),
+        "conv_forward_cat": ({}, lambda x: ops.conv_forward_cat(xa, x, wc, 128, one, zero), rnd(1, 1, 64, 64, 72).to(bf), 1),
+        "pool_conv_forward": ({}, lambda x: ops.pool_conv_forward(x, wq, 96, one, zero, True, torch.empty((8, 3, 14, 14, 96), dtype=bf, device=dev)),
+                              rnd(8, 3, 14, 14, 136).to(bf), 1),
+    }
+    for name, (opts, call, buf, nrec) in forms.items():
+        width = buf.shape[-1] - 8
+        for limit in (1 << 30, None):
+            got = {}
+            for tag, x in (("misaligned", buf[..., 4:4 + width]), ("aligned", buf[..., 8:]), ("dense", buf[..., 8:].contiguous())):
+                ops.PROFILE, ops.PROFILE_LIMIT = (None, None) if limit is None else ([], limit)
+                try:
+                    with _capi.options(L, **opts):
+                        y = call(x)
+                    got[tag] = (y is not None, 0 if limit is None else len(ops.PROFILE))
+                finally:
+                    ops.PROFILE, ops.PROFILE_LIMIT = None, None
+            accepted = (True, 0 if limit is None else nrec)
+            assert got == {"misaligned": (False, 0), "aligned": accepted, "dense": accepted}, (name, limit, got)
+
+
 CPU_CASES = ["case_state_dict_contract", "case_mixed_golden", "case_basenet_c1_golden", "case_context_golden",
              "case_twobranch_T3_and_losses_golden", "case_roinet_layouts", "case_training_step_matches_torch_autograd",
              "case_training_step_generic_weights",
@@ -1548,5 +1684,6 @@ CPU_CASES = ["case_state_dict_contract", "case_mixed_golden", "case_basenet_c1_g
              "case_contextnet_backward_matches_oracle_autograd", "case_basenet_batch_statistics_bn_golden", "case_postprocess_golden",
              "case_batched_repack_follows_weight_updates", "case_stem_backward_16bit",
              "case_loss_masks_without_host_branches", "case_data_parallel_replicas", "case_train_select_device_front_end", "case_nms_operator_api",
-             "case_resample_bottleneck_concat_in_one_launch"]
+             "case_resample_bottleneck_concat_in_one_launch", "case_fused_forms_refused_fall_back"]
 GPU_CASES = CPU_CASES + ["case_basenet_forward_u8", "case_conv_pool_fusion_in_basenet", "case_fp16_training_step_loss_scaling", "case_base_context_chain_backward", "case_wgrad_into_grad_matches_autograd", "case_training_iteration_with_selection", "case_training_step_16bit_storage", "case_c2_full_size_properties", "case_c5_full_size_properties", "case_basenet_c1_16bit_error", "case_twobranch_T9_golden", "case_i3d_classifier_golden", "case_inference_golden", "case_inference_modes_golden", "case_inference_golden_34", "case_e2e_c3_golden"]
+CPU_CASES = CPU_CASES + ["case_ops_profile_records"]        # interpreter only: the fixture holds the interpreter build's plans
