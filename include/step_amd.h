@@ -52,7 +52,7 @@ enum {
     STEP_E_ALIGN = -5
 };
 
-/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (42: step_grad_pack16 / step_grad_unpack16). */
+/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (43: step_clip_gather_u8). */
 STEP_API const char* step_version(void);
 STEP_API int step_abi_version(void);
 
@@ -633,6 +633,25 @@ typedef struct step_aug_clip {          /* 16 words */
 typedef struct step_aug_rect { int x1, y1, x2, y2, patch_off, reserved; } step_aug_rect;
 STEP_API int step_clip_augment_u8(const void* plan_block, int N, int T, int Ho, int Wo, int scale, const float* mean3,
                                   const float* std3, int rgb, int dtype, void* clip, step_stream_t stream);
+
+/* Indexed clip gather: the video demo's loader (data/customize.py:75-127 CustomizedDataset.read_images + BaseTransform) with the source
+ * frames RESIDENT on the device.  Every frame of a video is the middle of one clip, and neighbouring clips share almost all their source
+ * frames; so each decoded frame is uploaded once into a ring, and a batch of clips is assembled by one launch that reads its frames
+ * through an index table (step_clip_augment_u8 cannot: step_aug_clip.src addresses T contiguous frames).
+ *   ring     device memory, 16-byte aligned: n_slots uint8 BGR frames [Hs,Ws,3] at a pitch of slot_bytes (>= Hs*Ws*3, a multiple of 16;
+ *            a row of Ws*3 bytes may be odd, so a frame is read by bytes)
+ *   slot_of  DEVICE int32 [N*T]: slot_of[n*T + t] is the slot of frame t of clip n; slots may repeat and come in any order.  A value outside
+ *            [0, n_slots) is clamped in the kernel, so no table can make it read outside the ring (step_amd/video.py refuses such a table)
+ *   clip     [N,T,3,Ho,Wo] in `dtype`
+ * Per output pixel, the arithmetic of step_clip_augment_u8 under the identity plan (full-frame crop, flags 0, identity perm, no rectangles),
+ * through the same device function: cv2.resize's float32 bilinear taps from (Ws,Hs) to (Wo,Ho) (equal sizes copy), ConvertFromInts(scale),
+ * (v - mean[c]) / std[c], the optional (2,1,0) swap (rgb != 0), rounding to `dtype`.  BIT-IDENTICAL to step_clip_augment_u8 over
+ * BaseTransform plans on a contiguous stack of the same frames, for every dtype, scale and rgb.  mean3 / std3 are HOST pointers to 3
+ * floats (NULL = 0 / 1).  Errors, with nothing launched: STEP_E_SHAPE (N < 0, another size <= 0, scale outside 0..2, slot_bytes < Hs*Ws*3
+ * or no multiple of 16), STEP_E_DTYPE, STEP_E_NULL, STEP_E_ALIGN (ring); N == 0 is no error. */
+STEP_API int step_clip_gather_u8(const unsigned char* ring, long long slot_bytes, int n_slots, int Hs, int Ws,
+                                 const int* slot_of /* device, [N*T] */, int N, int T, int Ho, int Wo, int scale,
+                                 const float* mean3, const float* std3, int rgb, int dtype, void* clip, step_stream_t stream);
 
 /* Fused multi-tensor Adam over flat fp32 arenas: replaces optimizer.step() of torch.optim.Adam(params, lr=args.det_lr)
  * (train.py:126,348) over the single-tensor parameter groups of utils/solver.py:12-93 (per-group lr / weight_decay; the

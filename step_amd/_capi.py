@@ -5,7 +5,7 @@ import ctypes as C
 F32, BF16, F16 = 0, 1, 2
 NCHW, NHWC = 0, 1
 ROI_BWD_GATHER, ROI_BWD_ATOMIC = 0, 1
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 vp, fp, ip, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # raw device addresses
 i, f, ll, sz = C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -111,6 +111,7 @@ SIGNATURES = {
     "step_maxpool3d_tf_backward_gather": (i, [i, vp, i, i, i, i, i, i, i, i, i, i, i, i, i, i, vp, i, vp, u8p, vp]),
     "step_clip_from_u8": (i, [vp, i, i, i, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i, vp, vp]),
     "step_clip_augment_u8": (i, [vp, i, i, i, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i, i, vp, vp]),
+    "step_clip_gather_u8": (i, [u8p, ll, i, i, i, ip, i, i, i, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i, i, vp, vp]),
     "step_avgpool_hw": (i, [i, vp, i, i, i, i, i, i, i, vp, vp]),
     "step_transpose_cs": (i, [vp, i, vp, i, i, i, ll, i, vp]),
     "step_act_grad": (i, [i, vp, i, i, vp, i, fp, ll, i, i, fp, vp, vp]),

@@ -963,6 +963,97 @@ __global__ __launch_bounds__(256) void clip_augment_u8_kernel(const unsigned cha
     }
 }
 
+// Indexed clip gather (include/step_amd.h: step_clip_gather_u8): frame f = n * T + t of the batch is read from ring slot slot_of[f], whole and
+// unaugmented.  The thread's share and its order are clip_augment_u8_kernel's -- AUG_RUN columns of one output row, the three planes, the same
+// taps (aug_coord, aug_tap), blend, normalisation and stores -- under the identity plan entry, whose constants fold PhotometricDistort, the
+// mirror and the erase rectangles away: bit for bit what that kernel writes for a BaseTransform plan (kernel cases).  The thread body is
+// restated, not shared: as a common inline function it moved clip_augment_u8_kernel's instruction stream.  Flat grid over
+// N * T * Ho * ceil(Wo / 8) threads; the slot is clamped to the ring, so no table can make the kernel read outside it.
+template <typename T>
+__global__ __launch_bounds__(256) void clip_gather_u8_kernel(const unsigned char* __restrict__ ring, long long slot_bytes, int n_slots, int Hs, int Ws,
+                                                             const int* __restrict__ slot_of, T* __restrict__ dst, long long frames, int Ho, int Wo,
+                                                             int scale, int rgb, float m0, float m1, float m2, float s0, float s1, float s2,
+                                                             int vec_ok) {
+#pragma clang fp contract(off)
+    const int runs = (Wo + AUG_RUN - 1) / AUG_RUN;
+    const long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (item >= frames * Ho * runs) return;
+    const int run = (int)(item % runs);
+    const int dy = (int)((item / runs) % Ho);
+    const long long f = item / ((long long)runs * Ho);
+    const int slot = min(max(slot_of[f], 0), n_slots - 1);
+    const unsigned char* frame = ring + (size_t)slot * (size_t)slot_bytes;
+    step_aug_clip pc;                                                   // BaseTransform's plan: the whole frame, nothing drawn
+    pc.src = 0; pc.Hs = Hs; pc.Ws = Ws; pc.cx = 0; pc.cy = 0; pc.cw = Ws; pc.ch = Hs; pc.flags = 0; pc.perm = 0x24;
+    pc.brightness = pc.contrast = pc.saturation = pc.hue = 0.f; pc.n_rects = 0; pc.rect_off = 0;
+    const bool same = Ws == Wo && Hs == Ho;
+    const double rx = (double)Ws / Wo, ry = (double)Hs / Ho;
+    int sy = dy; float fy = 0.f;
+    if (!same) aug_coord(dy, Hs, ry, sy, fy);
+    const int sy1 = min(sy + 1, Hs - 1);
+    const float gy = aug_sub(1.f, fy);
+    const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+    float o[3][AUG_RUN];
+#pragma unroll
+    for (int j = 0; j < AUG_RUN; ++j) {
+        const int dx = run * AUG_RUN + j;
+        float v[3] = {0.f, 0.f, 0.f};
+        if (dx < Wo) {
+            if (same) {
+                aug_tap(frame, pc, nullptr, nullptr, dx, dy, scale, v);
+            } else {
+                int sx; float fx;
+                aug_coord(dx, Ws, rx, sx, fx);
+                const int sx1 = min(sx + 1, Ws - 1);
+                const float gx = aug_sub(1.f, fx);
+                float a[3], b[3], c[3], d[3];
+                aug_tap(frame, pc, nullptr, nullptr, sx, sy, scale, a);
+                aug_tap(frame, pc, nullptr, nullptr, sx1, sy, scale, b);
+                aug_tap(frame, pc, nullptr, nullptr, sx, sy1, scale, c);
+                aug_tap(frame, pc, nullptr, nullptr, sx1, sy1, scale, d);
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const float r0 = aug_add(aug_mul(a[ch], gx), aug_mul(b[ch], fx));
+                    const float r1 = aug_add(aug_mul(c[ch], gx), aug_mul(d[ch], fx));
+                    v[ch] = aug_add(aug_mul(r0, gy), aug_mul(r1, fy));
+                }
+            }
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) o[ch][j] = aug_div(aug_sub(v[ch], mean[ch]), stdv[ch]);
+    }
+    const size_t HW = (size_t)Ho * Wo;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        T* d = dst + ((size_t)f * 3 + (rgb ? 2 - ch : ch)) * HW + (size_t)dy * Wo + run * AUG_RUN;
+        if (vec_ok) {                                                   // Wo % 8 == 0 and a 16-byte aligned clip: whole runs, 16-byte stores
+            if constexpr (sizeof(T) == 2) {
+                u32x4 ov;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    ov[q] = (unsigned)elem<T>::bits16(o[ch][2 * q]) | ((unsigned)elem<T>::bits16(o[ch][2 * q + 1]) << 16);
+                *(u32x4*)d = ov;
+            } else {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    u32x4 ov;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        unsigned u;
+                        __builtin_memcpy(&u, &o[ch][4 * q + e], 4);
+                        ov[e] = u;
+                    }
+                    ((u32x4*)d)[q] = ov;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < AUG_RUN; ++j)
+                if (run * AUG_RUN + j < Wo) d[j] = elem<T>::from_f32(o[ch][j]);
+        }
+    }
+}
+
 template <typename T>
 __global__ void avgpool_hw_kernel(const T* __restrict__ x, T* __restrict__ y, int ND, int H, int W, int C, int kh,
                                   int kw, long long total) {
@@ -1290,6 +1381,29 @@ int step_clip_augment_u8(const void* plan_block, int N, int T, int Ho, int Wo, i
         case STEP_F32: STEP_LAUNCH((clip_augment_u8_kernel<float>), grid, dim3(256), stream, blk, (float*)clip, T, Ho, Wo, scale, rgb ? 1 : 0, m0, m1, m2, s0, s1, s2, vec_ok); break;
         case STEP_BF16: STEP_LAUNCH((clip_augment_u8_kernel<bf16_t>), grid, dim3(256), stream, blk, (bf16_t*)clip, T, Ho, Wo, scale, rgb ? 1 : 0, m0, m1, m2, s0, s1, s2, vec_ok); break;
         default: STEP_LAUNCH((clip_augment_u8_kernel<f16_t>), grid, dim3(256), stream, blk, (f16_t*)clip, T, Ho, Wo, scale, rgb ? 1 : 0, m0, m1, m2, s0, s1, s2, vec_ok); break;
+    }
+    return STEP_LAUNCH_CHECK();
+}
+
+int step_clip_gather_u8(const unsigned char* ring, long long slot_bytes, int n_slots, int Hs, int Ws, const int* slot_of, int N, int T, int Ho,
+                        int Wo, int scale, const float* mean3, const float* std3, int rgb, int dtype, void* clip, step_stream_t stream) {
+    if (N < 0 || T <= 0 || n_slots <= 0 || Hs <= 0 || Ws <= 0 || Ho <= 0 || Wo <= 0 || scale < 0 || scale > 2) return STEP_E_SHAPE;
+    if (slot_bytes < (long long)Hs * Ws * 3 || (slot_bytes & 15)) return STEP_E_SHAPE;
+    if (dtype != STEP_F32 && dtype != STEP_BF16 && dtype != STEP_F16) return STEP_E_DTYPE;
+    if (N == 0) return STEP_OK;
+    if (!ring || !slot_of || !clip) return STEP_E_NULL;
+    if ((size_t)ring & 15) return STEP_E_ALIGN;
+    const float m0 = mean3 ? mean3[0] : 0.f, m1 = mean3 ? mean3[1] : 0.f, m2 = mean3 ? mean3[2] : 0.f;   // host pointers (3 floats)
+    const float s0 = std3 ? std3[0] : 1.f, s1 = std3 ? std3[1] : 1.f, s2 = std3 ? std3[2] : 1.f;
+    const long long frames = (long long)N * T;
+    const long long gx = (frames * Ho * ((Wo + AUG_RUN - 1) / AUG_RUN) + 255) / 256;
+    if (gx > 0x7fffffffLL) return STEP_E_SHAPE;
+    const dim3 grid((unsigned)gx);
+    const int vec_ok = (Wo % AUG_RUN == 0 && ((size_t)clip & 15) == 0) ? 1 : 0;
+    switch (dtype) {
+        case STEP_F32: STEP_LAUNCH((clip_gather_u8_kernel<float>), grid, dim3(256), stream, ring, slot_bytes, n_slots, Hs, Ws, slot_of, (float*)clip, frames, Ho, Wo, scale, rgb ? 1 : 0, m0, m1, m2, s0, s1, s2, vec_ok); break;
+        case STEP_BF16: STEP_LAUNCH((clip_gather_u8_kernel<bf16_t>), grid, dim3(256), stream, ring, slot_bytes, n_slots, Hs, Ws, slot_of, (bf16_t*)clip, frames, Ho, Wo, scale, rgb ? 1 : 0, m0, m1, m2, s0, s1, s2, vec_ok); break;
+        default: STEP_LAUNCH((clip_gather_u8_kernel<f16_t>), grid, dim3(256), stream, ring, slot_bytes, n_slots, Hs, Ws, slot_of, (f16_t*)clip, frames, Ho, Wo, scale, rgb ? 1 : 0, m0, m1, m2, s0, s1, s2, vec_ok); break;
     }
     return STEP_LAUNCH_CHECK();
 }
