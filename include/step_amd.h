@@ -52,7 +52,7 @@ enum {
     STEP_E_ALIGN = -5
 };
 
-/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (43: step_clip_gather_u8). */
+/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (44: step_anchor_sample). */
 STEP_API const char* step_version(void);
 STEP_API int step_abi_version(void);
 
@@ -907,6 +907,56 @@ STEP_API int step_select_train(const float* cand, const float* cand_first, const
                                int before, int after, int topk, float cls_thresh, float reg_thresh, int max_pos_num, int neg_ratio,
                                int sampling, int budget, float* sel, float* tgt, float* mask, float* inv, int32_t* counts,
                                step_stream_t stream);
+
+/* Classification pre-training (train_cls.py, stage 1 of the two-stage recipe): the boxes the loader samples around every ground-truth box,
+ * data/ava_cls.py:200-261 sample_anchors inside __getitem__ -- up to 100 sequential trials per box, each a jaccard_numpy call -- for all
+ * clips of a batch in ONE launch, with the draws taken from the device-side generator of step_dropout_forward.  Same rule as the reference,
+ * NOT the reference's samples under the reference's seeds (step_amd/selection.py sample_anchors is the host form that reproduces those):
+ * the relation step_select_train has to train_select.
+ *
+ * Launch: one workgroup of up to 16 waves, a wave per (clip, ground truth) pair and round, lane = trial; the same workgroup advances the
+ * generator's offset by 1 at its end (also for B == 0 or Gmax == 0: the call counts).
+ *
+ * Inputs.  gt [B,Gmax,F,4+NC] fp32 pixel boxes (the layout step_select_train takes; only the box at frame `mid` is read), gt_count [B]
+ * int32 (clamped to [0, Gmax]); width, height: the frame size the boxes are divided by; T: frames per output tube; mode 0 train, 1 eval;
+ * rng_state {seed, offset}.  S = pos_num * (1 + neg_ratio), neg_num = pos_num * neg_ratio.  pos_thresh / neg_thresh are widened from
+ * fp32 to double before any comparison (0.75f is 0.75, 0.2f is NOT 0.2).
+ * Outputs.  tubes [B*Gmax*S, T, 4] fp32: the rows compactly, clip b owns rows clip_start[b] .. clip_start[b+1]-1, inside a clip ground truth
+ *   by ground truth, every row the sampled pixel box repeated over the T frames (ava_cls.py:353); rows from clip_start[B] on are zero.
+ *   clip_start [B+1] int32.  tubes / clip_start are step_select_train's cand / clip_start (N = B*Gmax*S, Amax = Gmax*S) as they lie.
+ *   counts [B*Gmax,2] int32: per pair q = b*Gmax + g the SAMPLED positives (0 when the box itself stands in; 1 in eval mode) and the
+ *   negatives; (0, 0) for g >= gt_count[b].  A pair with g < gt_count[b] owns max(positives, 1) + negatives rows, the others none.
+ *
+ * The rule, per pair (b, g < G = gt_count[b]), in float64 with every operation rounded on its own (no contraction).  min(a, b) = b < a ? b
+ *   : a, max(a, b) = b > a ? b : a (Python's), uniform(a, b) = a + (b - a) * u.
+ * Boxes.  a_o = gt[b,o,mid,0:4] / (W, H, W, H) for o < G; of the pair's own box: w = a[2] - a[0], h = a[3] - a[1], x = a[0] + 0.5 w,
+ *   y = a[1] + 0.5 h.
+ * Candidate of a trial: c = [x' - 0.5 w', y' - 0.5 h', x' + 0.5 w', y' + 0.5 h'].  iou_o = jaccard_numpy: intersection sides
+ *   min(a_o[2], c[2]) - max(a_o[0], c[0]) (and in y) clamped below at 0, inter their product, union = area(a_o) + area(c) - inter,
+ *   iou_o = inter / union.  P: iou_g > pos_thresh and exactly G - 1 of the iou_o < neg_thresh.  N: all G of them < neg_thresh.
+ * Loop A (mode 0 only), trials j = 0..49, draws (phase 0, k = 16 j + slot), slots 0-3:
+ *   w' = uniform(0.8 w, min(1, 1.2 w))   h' = uniform(0.8 h, min(1, 1.2 h))
+ *   x' = uniform(max(0.5 w', x - 0.2 w), min(1 - 0.5 w', x + 0.2 w))   y' = uniform(max(0.5 h', y - 0.2 h), min(1 - 0.5 h', y + 0.2 h))
+ *   j* = the trial of the pos_num-th P, or 49 when there are fewer.  Positives: the P trials j <= j*.  Negatives of loop A: the first
+ *   neg_num N trials with j <= j*.
+ * Loop B (both modes), trials j = 0..49, draws (phase 1, k = 16 j + 3 * quantity + {0 first option, 1 second option, 2 choice}), quantities
+ *   w', h', x', y' in this order, the first option chosen iff the choice's u < 0.5:
+ *   w' = uniform(0.3 w, 0.7 w) | min(1, uniform(1.5 w, 2 w))              h' likewise with h
+ *   x' = uniform(max(0.5 w', x - w), max(0.5 w', x - 0.3 w)) | uniform(min(1 - 0.5 w', x + 0.3 w), min(1 - 0.5 w', x + w))
+ *   y' = uniform(max(0.5 h', x - h), max(0.5 h', y - 0.3 h)) | uniform(min(1 - 0.5 h', y + 0.3 h), min(1 - 0.5 h', y + h))
+ *   (x - h in y's first option is the reference's line 242 as written).  The N trials are taken in order while the pair holds fewer than
+ *   neg_num negatives, loop A's included.
+ * Rows of the pair: the positives in trial order -- or gt[b,g,mid,0:4] itself, copied bit for bit, when there is none, and always in mode
+ *   1 -- then the negatives in the order taken, loop A's first.  A sampled box is c * (W, H, W, H) in float64, rounded to fp32.
+ * Draws.  {seed, offset} are read on the device; draw (q, phase, k) is step_select_train's: Philox block (q << 20) | (phase << 16) | k at
+ *   that offset, u = ((w0 << 21) | (w1 >> 11)) * 2^-53.  The launch owns its offset, so the stream is shared with the dropout passes and
+ *   step_select_train without collisions, and a replayed graph draws anew on every replay.
+ *
+ * Errors: pos_num < 1, neg_ratio < 0, T < 1, mid outside [0, F), mode not 0 / 1 -> STEP_E_SHAPE; Gmax > 64 or Gmax * S > 1024 ->
+ * STEP_E_UNSUPPORTED (step_select_train's limits for the same buffers).  A refused call writes nothing and leaves the offset alone. */
+STEP_API int step_anchor_sample(const float* gt, const int32_t* gt_count, int B, int Gmax, int F, int NC, int mid, float width, float height,
+                                int T, int pos_num, int neg_ratio, float pos_thresh, float neg_thresh, int mode,
+                                unsigned long long* rng_state, float* tubes, int32_t* clip_start, int32_t* counts, step_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -404,9 +404,197 @@ __global__ __launch_bounds__(64) void select_finish_kernel(const int32_t* counts
     rng[1] += 1ull;
 }
 
+// ---- classification pre-training: boxes sampled around the ground truths (step_anchor_sample; include/step_amd.h has the rule) --------
+// What data/ava_cls.py:200-261 (sample_anchors) does per ground-truth box inside the loader's __getitem__ -- up to 100 sequential trials,
+// each a jaccard_numpy call -- for all clips of a batch in one launch.  A trial's outcome does not depend on earlier trials, only which
+// accepted trials are TAKEN does: one wave per (clip, ground truth) pair, lane = trial (50 of 64), two ballots per loop, and the "up to the
+// pos_num-th positive" / "the first n negatives" rules are bit operations on the ballot masks.  One workgroup walks the pairs, a wave each
+// per round, so that the rows can be written compactly behind an exclusive prefix of the per-pair row counts.  float64 throughout, every
+// operation rounded on its own (the file is compiled without contraction), draws from the generator's stream like select_train_kernel.
+constexpr int ANC_TRIALS = 50;
+constexpr int ANC_MAX_WAVES = 16;
+
+struct AnchorParams {
+    const float* gt; const int32_t* gt_count; unsigned long long* rng;
+    float* tubes; int32_t* clip_start; int32_t* counts;
+    int B, Gmax, F, NC, mid, T, pos_num, neg_num, mode;
+    double W, H, pos_thresh, neg_thresh;
+};
+
+__device__ __forceinline__ double anc_min(double a, double b) { return b < a ? b : a; }           // Python's min(a, b) / max(a, b): the first
+__device__ __forceinline__ double anc_max(double a, double b) { return b > a ? b : a; }           // argument unless the second one beats it
+__device__ __forceinline__ double anc_uniform(double a, double b, double u) { return a + (b - a) * u; }   // random.uniform
+
+// the box of ground truth g of clip b at frame `mid`, divided by (W, H, W, H)
+__device__ __forceinline__ void anc_box(const AnchorParams& p, int b, int g, double (&a)[4]) {
+    const float* q = p.gt + (((size_t)b * p.Gmax + g) * p.F + p.mid) * (4 + p.NC);
+    a[0] = (double)q[0] / p.W; a[1] = (double)q[1] / p.H; a[2] = (double)q[2] / p.W; a[3] = (double)q[3] / p.H;
+}
+
+// jaccard_numpy(anchors, c) against the G boxes of the clip: bit 0 = P (own IoU above pos_thresh, every other one below neg_thresh),
+// bit 1 = N (all G below neg_thresh)
+__device__ __forceinline__ int anc_accept(const AnchorParams& p, int b, int g, int G, const double (&c)[4]) {
+    const double area_c = (c[2] - c[0]) * (c[3] - c[1]);
+    int below = 0;
+    bool own = false;
+    for (int o = 0; o < G; ++o) {
+        double a[4];
+        anc_box(p, b, o, a);
+        double iw = (a[2] < c[2] ? a[2] : c[2]) - (a[0] > c[0] ? a[0] : c[0]);
+        double ih = (a[3] < c[3] ? a[3] : c[3]) - (a[1] > c[1] ? a[1] : c[1]);
+        iw = iw < 0.0 ? 0.0 : iw; ih = ih < 0.0 ? 0.0 : ih;
+        const double inter = iw * ih;
+        const double uni = (a[2] - a[0]) * (a[3] - a[1]) + area_c - inter;
+        const double iou = inter / uni;
+        below += iou < p.neg_thresh ? 1 : 0;
+        if (o == g) own = iou > p.pos_thresh;
+    }
+    return ((own && below == G - 1) ? 1 : 0) | (below == G ? 2 : 0);
+}
+
+__device__ __forceinline__ unsigned long long anc_first(unsigned long long m, int n) {            // the lowest n set bits of m
+    unsigned long long r = 0;
+    for (int i = 0; i < n && m; ++i) { r |= m & (~m + 1ull); m &= m - 1ull; }
+    return r;
+}
+
+__global__ __launch_bounds__(64 * ANC_MAX_WAVES) void anchor_sample_kernel(AnchorParams p) {
+    __shared__ int s_rows[ANC_MAX_WAVES];
+    __shared__ int s_base;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    const unsigned long long seed = p.rng[0], off = p.rng[1];
+    const int npairs = p.B * p.Gmax;
+    const int S = p.pos_num + p.neg_num;
+    const size_t rowlen = (size_t)p.T * 4;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int base = 0; base < npairs; base += nw) {
+        const int q = base + wave;
+        const int b = q < npairs ? q / p.Gmax : 0, g = q < npairs ? q % p.Gmax : 0;
+        int G = 0;
+        if (q < npairs) { G = p.gt_count[b]; G = G < 0 ? 0 : G > p.Gmax ? p.Gmax : G; }
+        const bool live = q < npairs && g < G;
+        double ca[4] = {0.0, 0.0, 0.0, 0.0}, cb[4] = {0.0, 0.0, 0.0, 0.0};
+        unsigned long long posm = 0, nega = 0, negb = 0;
+        int npos = 0;
+        if (live) {                                                        // (wave-uniform: all 64 lanes take part in the ballots)
+            double a[4];
+            anc_box(p, b, g, a);
+            const double w = a[2] - a[0], h = a[3] - a[1];
+            const double x = a[0] + 0.5 * w, y = a[1] + 0.5 * h;
+            const bool trial = lane < ANC_TRIALS;
+            const int j = trial ? lane : 0;
+            if (p.mode == 0) {                                             // loop A (ava_cls.py:216-232)
+                const double nwd = anc_uniform(0.8 * w, anc_min(1.0, 1.2 * w), sel_draw(seed, off, q, 0, 16 * j + 0));
+                const double nhd = anc_uniform(0.8 * h, anc_min(1.0, 1.2 * h), sel_draw(seed, off, q, 0, 16 * j + 1));
+                const double nx = anc_uniform(anc_max(0.5 * nwd, x - 0.2 * w), anc_min(1.0 - 0.5 * nwd, x + 0.2 * w), sel_draw(seed, off, q, 0, 16 * j + 2));
+                const double ny = anc_uniform(anc_max(0.5 * nhd, y - 0.2 * h), anc_min(1.0 - 0.5 * nhd, y + 0.2 * h), sel_draw(seed, off, q, 0, 16 * j + 3));
+                ca[0] = nx - 0.5 * nwd; ca[1] = ny - 0.5 * nhd; ca[2] = nx + 0.5 * nwd; ca[3] = ny + 0.5 * nhd;
+                const int acc = anc_accept(p, b, g, G, ca);
+                const unsigned long long Pm = __ballot(trial && (acc & 1)), Nm = __ballot(trial && (acc & 2));
+                unsigned long long m = Pm;                                 // j*: the trial of the pos_num-th P, or the last trial
+                int seen = m ? 1 : 0;
+                for (; seen < p.pos_num && (m & (m - 1ull)); ++seen) m &= m - 1ull;
+                const int jstar = (seen == p.pos_num) ? __builtin_ctzll(m) : ANC_TRIALS - 1;
+                const unsigned long long upto = (2ull << jstar) - 1ull;
+                posm = Pm & upto;
+                nega = anc_first(Nm & upto, p.neg_num);
+                npos = __builtin_popcountll(posm);
+            } else {
+                npos = 1;                                                  // eval: the ground-truth box itself
+            }
+            {                                                              // loop B (ava_cls.py:236-252)
+                double u[12];
+                for (int k = 0; k < 12; ++k) u[k] = sel_draw(seed, off, q, 1, 16 * j + k);
+                const double w0 = anc_uniform(0.3 * w, 0.7 * w, u[0]), w1 = anc_min(1.0, anc_uniform(1.5 * w, 2.0 * w, u[1]));
+                const double nwd = u[2] < 0.5 ? w0 : w1;
+                const double h0 = anc_uniform(0.3 * h, 0.7 * h, u[3]), h1 = anc_min(1.0, anc_uniform(1.5 * h, 2.0 * h, u[4]));
+                const double nhd = u[5] < 0.5 ? h0 : h1;
+                const double x0 = anc_uniform(anc_max(0.5 * nwd, x - w), anc_max(0.5 * nwd, x - 0.3 * w), u[6]);
+                const double x1 = anc_uniform(anc_min(1.0 - 0.5 * nwd, x + 0.3 * w), anc_min(1.0 - 0.5 * nwd, x + w), u[7]);
+                const double nx = u[8] < 0.5 ? x0 : x1;
+                const double y0 = anc_uniform(anc_max(0.5 * nhd, x - h), anc_max(0.5 * nhd, y - 0.3 * h), u[9]);       // x - h: the reference's line 242
+                const double y1 = anc_uniform(anc_min(1.0 - 0.5 * nhd, y + 0.3 * h), anc_min(1.0 - 0.5 * nhd, y + h), u[10]);
+                const double ny = u[11] < 0.5 ? y0 : y1;
+                cb[0] = nx - 0.5 * nwd; cb[1] = ny - 0.5 * nhd; cb[2] = nx + 0.5 * nwd; cb[3] = ny + 0.5 * nhd;
+                const int acc = anc_accept(p, b, g, G, cb);
+                const unsigned long long Nm = __ballot(trial && (acc & 2));
+                negb = anc_first(Nm, p.neg_num - __builtin_popcountll(nega));
+            }
+        }
+        const int na = __builtin_popcountll(nega), nneg = na + __builtin_popcountll(negb);
+        const int prow = live ? (npos > 0 ? npos : 1) : 0;                 // no positive: the ground-truth box stands in
+        if (lane == 0) s_rows[wave] = prow + nneg;
+        __syncthreads();
+        int row0 = s_base, total = 0;
+        for (int v = 0; v < nw; ++v) { if (v < wave) row0 += s_rows[v]; total += s_rows[v]; }
+        if (q < npairs && lane == 0) {
+            p.counts[2 * q] = npos; p.counts[2 * q + 1] = nneg;
+            if (g == 0) p.clip_start[b] = row0;
+        }
+        if (live) {
+            const unsigned long long below = (1ull << lane) - 1ull;
+            const double sc[4] = {p.W, p.H, p.W, p.H};
+            int r = -1;
+            float v4[4];
+            if (posm >> lane & 1ull) {
+                r = __builtin_popcountll(posm & below);
+                for (int k = 0; k < 4; ++k) v4[k] = (float)(ca[k] * sc[k]);
+            } else if (nega >> lane & 1ull) {
+                r = prow + __builtin_popcountll(nega & below);
+                for (int k = 0; k < 4; ++k) v4[k] = (float)(ca[k] * sc[k]);
+            }
+            if (r >= 0) {
+                float* dst = p.tubes + ((size_t)row0 + r) * rowlen;
+                for (int t = 0; t < p.T; ++t) { dst[4 * t] = v4[0]; dst[4 * t + 1] = v4[1]; dst[4 * t + 2] = v4[2]; dst[4 * t + 3] = v4[3]; }
+            }
+            if (negb >> lane & 1ull) {                                     // (a lane can hold a row of loop A and one of loop B)
+                r = prow + na + __builtin_popcountll(negb & below);
+                float* dst = p.tubes + ((size_t)row0 + r) * rowlen;
+                for (int k = 0; k < 4; ++k) v4[k] = (float)(cb[k] * sc[k]);
+                for (int t = 0; t < p.T; ++t) { dst[4 * t] = v4[0]; dst[4 * t + 1] = v4[1]; dst[4 * t + 2] = v4[2]; dst[4 * t + 3] = v4[3]; }
+            }
+            if (npos == 0 || p.mode != 0) {                                // the box itself, bit for bit
+                const float* src = p.gt + (((size_t)b * p.Gmax + g) * p.F + p.mid) * (4 + p.NC);
+                float* dst = p.tubes + (size_t)row0 * rowlen;
+                for (int i = lane; i < p.T * 4; i += 64) dst[i] = src[i & 3];
+            }
+        }
+        __syncthreads();
+        if (tid == 0) s_base += total;                                     // (read again only behind the next round's barrier)
+    }
+    __syncthreads();
+    const int rows = s_base;
+    if (tid == 0) { p.clip_start[p.B] = rows; p.rng[1] = off + 1ull; }
+    if (npairs == 0) for (int b = tid; b < p.B; b += blockDim.x) p.clip_start[b] = 0;
+    const size_t end = (size_t)npairs * S * rowlen;
+    for (size_t i = (size_t)rows * rowlen + tid; i < end; i += blockDim.x) p.tubes[i] = 0.0f;
+}
+
 }  // namespace step
 
 using namespace step;
+
+extern "C" int step_anchor_sample(const float* gt, const int32_t* gt_count, int B, int Gmax, int F, int NC, int mid, float width, float height,
+                                  int T, int pos_num, int neg_ratio, float pos_thresh, float neg_thresh, int mode, unsigned long long* rng_state,
+                                  float* tubes, int32_t* clip_start, int32_t* counts, step_stream_t stream) {
+    if (B < 0 || Gmax < 0 || F <= 0 || NC < 0 || mid < 0 || mid >= F || (mode != 0 && mode != 1)) return STEP_E_SHAPE;
+    if (pos_num < 1 || neg_ratio < 0 || T < 1) return STEP_E_SHAPE;
+    const long long S = (long long)pos_num * (1 + (long long)neg_ratio);
+    if (Gmax > SEL_MAX_GT || (long long)Gmax * S > SEL_MAX_TUBES) return STEP_E_UNSUPPORTED;
+    if ((long long)B * Gmax > 0x3fffffffLL) return STEP_E_UNSUPPORTED;
+    if (!rng_state || !clip_start) return STEP_E_NULL;
+    if ((uintptr_t)rng_state & 7) return STEP_E_ALIGN;
+    const long long npairs = (long long)B * Gmax;
+    if (npairs > 0 && (!gt || !gt_count || !tubes || !counts)) return STEP_E_NULL;
+    AnchorParams p;
+    p.gt = gt; p.gt_count = gt_count; p.rng = rng_state; p.tubes = tubes; p.clip_start = clip_start; p.counts = counts;
+    p.B = B; p.Gmax = Gmax; p.F = F; p.NC = NC; p.mid = mid; p.T = T; p.pos_num = pos_num; p.neg_num = npairs > 0 ? pos_num * neg_ratio : 0; p.mode = mode;
+    p.W = (double)width; p.H = (double)height; p.pos_thresh = (double)pos_thresh; p.neg_thresh = (double)neg_thresh;
+    const int waves = npairs < 1 ? 1 : npairs > ANC_MAX_WAVES ? ANC_MAX_WAVES : (int)npairs;
+    STEP_LAUNCH(anchor_sample_kernel, dim3(1), dim3(64u * (unsigned)waves), stream, p);
+    return STEP_LAUNCH_CHECK();
+}
 
 extern "C" int step_select_prepare(const float* prob, const float* loc, const float* first, const float* last, int N, int T, int Tw, int NC,
                                    const int32_t* clip_of, const float* gt_mid, const int32_t* gt_count, int Gmax, float width, float height,

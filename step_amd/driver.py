@@ -278,6 +278,44 @@ def _postprocess_general(h, nums, conf, thr, etopk, topk, W, H):
     return clips
 
 
+def classified_rows(args, prob, flat_tubes, nums, conf_thresh=None):
+    """The body of train_cls.py's validate() (:508-543): the classification stage scores the boxes it was GIVEN, so there is no valid_tubes
+    and NO NMS -- per clip and class, in tube order, every tube with prob[tube, class] > conf_thresh gives a row: the box of the tube's
+    middle frame divided by [W,H,W,H], the class, the score.  prob [N,NC] (a cls_only head's output), flat_tubes [N,Tl,5] (frame-index
+    column first) or [N,Tl,4], nums = tubes per clip (host ints).  Returns what postprocess() returns for ONE iteration -- a list over clips of
+    {boxes [m,4] fp32 normalised, scores [m], labels [m], tubes [m]} -- so detections_csv and evaluate.FrameMAP.add_detections take it
+    unchanged.  One comparison for the keep mask, then the row compaction of postprocess() (step_detect_compact, <= 64 tubes per clip; the
+    nonzero / gather form beyond that) and its one host synchronisation for the row counts."""
+    conf = float(getattr(args, "conf_thresh", 0.01) if conf_thresh is None else conf_thresh)
+    W, H = float(args.image_size[0]), float(args.image_size[1])
+    nums = [int(v) for v in nums]
+    dev = prob.device
+    B = len(nums)
+    if B == 0 or sum(nums) == 0:
+        e = torch.zeros(0, device=dev)
+        return [{"boxes": e.view(0, 4), "scores": e, "labels": e.long(), "tubes": e.long()} for _ in nums]
+    scores = prob.float().contiguous()
+    NC = scores.shape[1]
+    boxes = flat_tubes[:, int(flat_tubes.shape[1] / 2), -4:].float().contiguous()                     # :515
+    idx, valid = _clip_groups(nums, dev)
+    kmax = idx.shape[1]
+    keep = ((scores[idx].permute(0, 2, 1) > conf) & valid.view(B, 1, kmax)).to(torch.uint8).contiguous()     # [B,NC,kmax] (:520)
+    if COMPACT_KERNEL and kmax <= 64:
+        n = torch.as_tensor(nums, device=dev, dtype=torch.int32)
+        start = (torch.cumsum(n, 0) - n).to(torch.int32)
+        rb, rs, kc, kj, cnt = ops.detect_compact(keep.view(1, B, NC, kmax), [boxes], [scores], start, W, H)
+        per = cnt.tolist()                                                                            # the one host sync
+        cap = NC * kmax
+        return [{"boxes": rb[b * cap:b * cap + per[b]], "scores": rs[b * cap:b * cap + per[b]], "labels": kc[b * cap:b * cap + per[b]],
+                 "tubes": kj[b * cap:b * cap + per[b]]} for b in range(B)]
+    kb, kc, kj = torch.nonzero(keep, as_tuple=True)
+    tube = idx[kb, kj]
+    rb = boxes[tube] / torch.tensor([W, H, W, H], device=dev)                                         # :533-534
+    rs = scores[tube, kc]
+    per = torch.bincount(kb, minlength=B).tolist()
+    return [{"boxes": bx, "scores": sc, "labels": cl, "tubes": tb} for bx, sc, cl, tb in zip(rb.split(per), rs.split(per), kc.split(per), kj.split(per))]
+
+
 def detections_csv(dets, infos, label_dict=None):
     """The text test.py:210-218 writes for one iteration: `dets` = one entry of postprocess()'s result, infos = per clip
     {'video_name', 'fid'}; label_dict maps class index -> label id (identity + 1 when None)."""

@@ -37,16 +37,25 @@ class _HeadOutputsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, reg, tubes, targets, N, Tl, T, NC):
-        prob, ll, fl, la, lc, lo, ln, tubes32, targets32 = ops.head_outputs(logits.detach(), reg.detach(), N, Tl, T, NC, tubes, targets)
+        # reg None: a cls_only head (two_branch.py:246) -- the kernel then writes prob and the classification loss only
+        prob, ll, fl, la, lc, lo, ln, tubes32, targets32 = ops.head_outputs(logits.detach(), None if reg is None else reg.detach(), N, Tl, T, NC,
+                                                                            tubes, targets)
         ctx.save_for_backward(logits, reg, tubes32, targets32)
         ctx.dims = (N, Tl, T, NC)
+        if reg is None:
+            ctx.mark_non_differentiable(prob)
+            return prob, lc
         ctx.mark_non_differentiable(prob, ll, fl, la)
         return prob, ll, fl, la, lc, lo, ln
 
     @staticmethod
-    def backward(ctx, gp, gll, gfl, gla, g_cls, g_loc, g_nbr):
+    def backward(ctx, gp, *grads):
         logits, reg, tubes32, targets32 = ctx.saved_tensors
         N, Tl, T, NC = ctx.dims
+        if reg is None:
+            g_logits, _ = ops.head_outputs_backward(logits.detach(), None, N, Tl, T, NC, tubes32, targets32, grads[0], None, None)
+            return g_logits, None, None, None, None, None, None, None
+        gll, gfl, gla, g_cls, g_loc, g_nbr = grads
         g_logits, g_reg = ops.head_outputs_backward(logits.detach(), reg.detach(), N, Tl, T, NC, tubes32, targets32, g_cls, g_loc, g_nbr)
         return g_logits, g_reg, None, None, None, None, None, None
 
@@ -384,10 +393,25 @@ class TwoBranchNet(nn.Module):
             logits = self._u_cls_ctx(ctx, relu=False, res=self._u_cls_feat(flat, relu=False))
         else:
             logits = self._u_cls_feat(flat, relu=False)
-        fused_tail = FUSED_HEAD_OUTPUTS and SYNC_FREE_LOSSES and not self.cls_only
+        fused_tail = FUSED_HEAD_OUTPUTS and SYNC_FREE_LOSSES
         global_class = None if fused_tail else logits.reshape(N, Tl, self.num_classes).float().mean(1)
 
         # ---- local branch
+        if self.cls_only and fused_tail:
+            # frame mean + sigmoid + the classification loss: step_head_outputs with reg == NULL, one launch (and one in backward); the
+            # returned tuple is the chain's: three one-element zeros for the boxes, two zero losses
+            z = torch.zeros(5, device=logits.device)               # fill kernel: capturable
+            if targets is not None:
+                tubes, targets = tubes.to(dev), targets.to(dev)
+                if torch.is_grad_enabled() and logits.requires_grad:
+                    prob, lcls = _HeadOutputsFn.apply(logits, None, tubes, targets, N, Tl, self.T, self.num_classes)
+                else:
+                    o = ops.head_outputs(logits, None, N, Tl, self.T, self.num_classes, tubes, targets)
+                    prob, lcls = o[0], o[4]
+            else:
+                o = ops.head_outputs(logits, None, N, Tl, self.T, self.num_classes)
+                prob, lcls = o[0], o[4]
+            return (prob, z[0:1], z[1:2], z[2:3], lcls.reshape(-1), z[3:4], z[4:5])
         if self.cls_only:                                          # (two_branch.py:246: three one-element zeros)
             zero = torch.zeros(1, device=global_class.device, dtype=global_class.dtype)      # fill kernel: capturable
             local_loc, first_loc, last_loc = zero, zero.clone(), zero.clone()

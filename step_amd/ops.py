@@ -1131,6 +1131,38 @@ def select_train(cand, cand_first, cand_last, score, iou, clip_start, max_tubes,
     return out
 
 
+def anchor_sample(gt, gt_count, rng, mid, width, height, T, pos_num=1, neg_ratio=3, pos_thresh=0.75, neg_thresh=0.2, mode="train", out=None):
+    """step_anchor_sample: the boxes train_cls.py's loader samples around every ground truth, all clips in one launch (include/step_amd.h
+    has the rule).  gt [B,Gmax,F,4+NC] float32 pixel boxes, gt_count [B] int32 (one device), rng a step_amd.rng.DeviceRNG (its offset
+    advances by one on the device), mode "train" | "eval".  -> (tubes [B*Gmax*S,T,4], clip_start [B+1] int32, counts [B*Gmax,2] int32),
+    S = pos_num * (1 + neg_ratio): step_select_train's cand / clip_start as they lie; out = such a tuple writes into the caller's (static)
+    buffers.  No host synchronisation."""
+    L = _lib.lib()
+    if mode not in ("train", "eval"):
+        raise ValueError("step_amd: anchor_sample mode is 'train' or 'eval', got %r" % (mode,))
+    dev = gt.device
+    if gt.dtype != torch.float32 or not gt.is_contiguous() or gt.dim() != 4 or gt.shape[3] < 4:
+        raise RuntimeError("step_amd: anchor_sample wants gt as a contiguous float32 tensor [B,Gmax,F,4+NC], got %s %s" % (tuple(gt.shape), gt.dtype))
+    B, Gmax, F, NC = gt.shape[0], gt.shape[1], gt.shape[2], gt.shape[3] - 4
+    if gt_count.dtype != torch.int32 or not gt_count.is_contiguous() or gt_count.device != dev or tuple(gt_count.shape) != (B,):
+        raise RuntimeError("step_amd: anchor_sample wants gt_count as a contiguous int32 tensor [B=%d] on %s" % (B, dev))
+    if rng.state.device != dev:
+        raise RuntimeError("step_amd: anchor_sample wants the generator on %s" % (dev,))
+    S = int(pos_num) * (1 + int(neg_ratio))
+    shapes = ((B * Gmax * max(S, 0), int(T), 4), (B + 1,), (B * Gmax, 2))
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=torch.float32 if k == 0 else torch.int32, device=dev) for k, sh in enumerate(shapes))
+    for k, (t, sh) in enumerate(zip(out, shapes)):
+        if tuple(t.shape) != sh or t.dtype != (torch.float32 if k == 0 else torch.int32) or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError("step_amd: anchor_sample output %d wants shape %s, got %s %s" % (k, sh, tuple(t.shape), t.dtype))
+    tubes, clip_start, counts = out
+    _capi.check(L.step_anchor_sample(_lib.dptr(gt), _lib.dptr(gt_count), B, Gmax, F, NC, int(mid), float(width), float(height), int(T),
+                                     int(pos_num), int(neg_ratio), float(pos_thresh), float(neg_thresh), 0 if mode == "train" else 1,
+                                     _lib.dptr(rng.state), _lib.dptr(tubes), _lib.dptr(clip_start), _lib.dptr(counts), _lib.stream_ptr(dev)),
+                "step_anchor_sample")
+    return out
+
+
 def _check_head_targets(name, dev, N, Tl, NC, tubes, targets):
     """The kernel hard-codes tubes [N,Tl,5] and targets [N,3,6+NC] (row 2 = 'last'): anything else would be read out of bounds and give
     wrong losses silently, where the torch chain it replaces (two_branch.py:294-333) would have raised."""

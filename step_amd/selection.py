@@ -13,6 +13,10 @@ exactly, because they decide WHICH tubes are trained on:
 
 All three `temporal_mode`s ("predict": every shipped script; "extrapolate"; "mean") are supported, like step_amd/driver.py.
 
+`sample_anchors` / `cls_select` are the same for the classification pre-training stage (train_cls.py; data/ava_cls.py:200-261): the loader's
+rejection sampling around the ground-truth boxes, pinned to the reference's `random` stream (tests/golden/cls_golden.npz), and the per-clip
+selection of train_cls.py:263-291.  `DeviceClsSelector` is their opt-in device form (step_anchor_sample + step_select_train).
+
 `DeviceSelector` is the opt-in device form of the same rule (step_select_train, include/step_amd.h): no host synchronisation, static
 output shapes, draws from the device-side generator -- its own stream of draws and index-ordered ties, so it selects other tubes than
 the reference does under the reference's seeds.  `train_select` stays the default and the one that is pinned to the reference.
@@ -343,3 +347,150 @@ class DeviceSelector:
         return ops.select_train(cand, first, last, score, iou, clip_start, n_max, gt, gt_count, pad_tubes, self.rng, mid, before, after, a.topk,
                                 a.cls_thresh[step - 1], a.reg_thresh[step - 1], a.max_pos_num, a.neg_ratio, a.selection_sampling, self.budget,
                                 out=self.out[step])
+
+
+# ---- classification pre-training (train_cls.py: stage 1 of the reference's two-stage recipe) --------------------------------------------
+def _jaccard(boxes, box):
+    """IoU of every row of boxes [G,4] with one box [4] in the arithmetic of data/augmentations.py:15-39: intersection sides clamped below at
+    0, union = area + area - intersection; no guard against a zero union."""
+    hi = np.minimum(boxes[:, 2:], box[2:])
+    lo = np.maximum(boxes[:, :2], box[:2])
+    side = np.clip(hi - lo, a_min=0, a_max=np.inf)
+    inter = side[:, 0] * side[:, 1]
+    union = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1]) + (box[2] - box[0]) * (box[3] - box[1]) - inter
+    return inter / union
+
+
+def _centred(cx, cy, bw, bh):
+    return np.array([cx - 0.5 * bw, cy - 0.5 * bh, cx + 0.5 * bw, cy + 0.5 * bh], dtype=float)
+
+
+def sample_anchors(anchors, pos_num=1, neg_ratio=1, pos_thresh=0.75, neg_thresh=0.2, mode='train'):
+    """-> [rows, 4]: per box of `anchors` ([G,4], normalised to [0, 1]) its sampled positives -- or the box itself when none was found, and
+    always outside mode 'train' -- followed by its sampled negatives (data/ava_cls.py:200-261).
+
+    Train mode first tries up to 50 boxes of 0.8-1.2 times the size within 0.2 of the centre: one that overlaps its own box by more than
+    pos_thresh and every other box by less than neg_thresh is a positive, one below neg_thresh everywhere a negative; the loop ends with the
+    pos_num-th positive.  Then, in both modes, up to 50 boxes of 0.3-0.7 or 1.5-2 times the size, shifted by 0.3-1 of it, fill the negatives
+    up to pos_num * neg_ratio.  Every draw is one call of `random.uniform` / `random.choice` in the reference's order (both options of a
+    choice are drawn before the choice; the loop that fills the negatives draws one whole trial even when nothing is missing), so that with
+    the same `random` seed the same boxes come out, bit for bit in float64, and the stream is left where the reference leaves it."""
+    want_neg = pos_num * neg_ratio
+    uni, pick = random.uniform, random.choice
+    rows = []
+    for i in range(anchors.shape[0]):
+        box = anchors[i]
+        w = box[2] - box[0]
+        h = box[3] - box[1]
+        x = box[0] + 0.5 * w
+        y = box[1] + 0.5 * h
+        pos, neg = [], []
+
+        def is_negative(c):
+            iou = _jaccard(anchors, c)
+            return (iou < neg_thresh).sum() == iou.shape[0]
+
+        if mode == 'train':
+            for _ in range(50):
+                bw = uni(0.8 * w, min(1, 1.2 * w))
+                bh = uni(0.8 * h, min(1, 1.2 * h))
+                cx = uni(max(0.5 * bw, x - 0.2 * w), min(1 - 0.5 * bw, x + 0.2 * w))
+                cy = uni(max(0.5 * bh, y - 0.2 * h), min(1 - 0.5 * bh, y + 0.2 * h))
+                c = _centred(cx, cy, bw, bh)
+                iou = _jaccard(anchors, c)
+                below = (iou < neg_thresh).sum()
+                if len(pos) < pos_num and iou[i] > pos_thresh and below == iou.shape[0] - 1:
+                    pos.append(c)
+                elif len(neg) < want_neg and below == iou.shape[0]:
+                    neg.append(c)
+                if len(pos) == pos_num:
+                    break
+        else:
+            pos.append(box)
+        for _ in range(50):
+            bw = pick((uni(0.3 * w, 0.7 * w), min(1, uni(1.5 * w, 2 * w))))
+            bh = pick((uni(0.3 * h, 0.7 * h), min(1, uni(1.5 * h, 2 * h))))
+            cx = pick((uni(max(0.5 * bw, x - w), max(0.5 * bw, x - 0.3 * w)), uni(min(1 - 0.5 * bw, x + 0.3 * w), min(1 - 0.5 * bw, x + w))))
+            # (x - h below is the reference's rule, ava_cls.py:242: the distribution of the negatives follows it)
+            cy = pick((uni(max(0.5 * bh, x - h), max(0.5 * bh, y - 0.3 * h)), uni(min(1 - 0.5 * bh, y + 0.3 * h), min(1 - 0.5 * bh, y + h))))
+            c = _centred(cx, cy, bw, bh)
+            if len(neg) < want_neg and is_negative(c):
+                neg.append(c)
+            if len(neg) == want_neg:
+                break
+        rows.extend(pos if pos else [box])
+        rows.extend(neg)
+    return np.stack(rows, axis=0)
+
+
+def cls_select(targets, tubes, args=None):
+    """The per-clip body of train_cls.py:263-291 -> (selected_tubes, target_tubes), one array per clip: select_proposals on the middle frames
+    (cls_thresh 0.75, at most 5 positives, negatives by IoU-weighted draws, 3 per positive; draws from `random` / `numpy.random` in the
+    reference's order), the selected tubes [n,T,4] fp32 and the targets [n,3,6+NC]: a positive carries its ground truth's box and labels, a
+    negative zeros; column 4 (the classification flag) is 1 on every row; the one row is repeated for the three loss frames."""
+    selected, wanted = [], []
+    for b in range(len(targets)):
+        gt, cur = np.asarray(targets[b]), np.asarray(tubes[b])
+        nc = gt.shape[2] - 4
+        if args is not None and nc != args.num_classes:
+            raise ValueError("cls_select: targets carry %d classes, args.num_classes is %d" % (nc, args.num_classes))
+        mid = 0                                                     # int(max_chunks / 2) with max_chunks = 1
+        pos, neg, _ = select_proposals(gt[:, mid].reshape(gt.shape[0], 1, -1), cur[:, int(cur.shape[1] / 2)].reshape(cur.shape[0], 1, -1),
+                                       None, 0.75, 5, "uniform", 3)
+        n = len(pos) + len(neg)
+        sel = np.zeros((n, cur.shape[1], 4), np.float32)
+        row = np.zeros((n, 1, 6 + nc), np.float32)
+        for r, (g, a) in enumerate(pos + neg):
+            sel[r] = cur[a]
+            if r < len(pos):
+                row[r, :, :4] = gt[g, mid, :4]
+                row[r, :, 6:] = gt[g, mid, 4:]
+        row[:, :, 4] = 1
+        selected.append(sel)
+        wanted.append(np.concatenate([row, row, row], axis=1))
+    return selected, wanted
+
+
+class DeviceClsSelector:
+    """sample_anchors + cls_select for a FIXED batch on the device (opt-in): select() is step_anchor_sample followed by step_select_train
+    (score and iou NULL: the candidates are the sampled tubes, the table is the kernel's own) on the current stream, into static buffers --
+    two launches and two offsets of `rng` per iteration (and one strided copy of the row mask into the targets' flag column), nothing returned
+    to the host, so the calls can be recorded in a graph and draw anew
+    on every replay.  The draws are the device generator's, not the reference's.  cls_thresh 0.75, at most 5 positives, 3 negatives per
+    positive, weights IoU + 1e-6 (train_cls.py:266-270); reg_thresh is above 1, so no negative gets a box or labels; budget 20 slots per
+    clip.  Two differences from cls_select's targets, neither of which a cls_only head reads (it takes targets[:, 1] and its flag and label
+    columns only): the device form writes the CENTRE row alone -- rows 0 and 2, which the host form fills with copies of it, stay zero --
+    and column 5 of a positive's centre row (the regression flag) is 1 where the host form leaves 0."""
+    CLS_THRESH, MAX_POS, NEG_RATIO, BUDGET = 0.75, 5, 3, 20
+
+    def __init__(self, args, batch, Gmax, dev, rng, pos_num=1, neg_ratio=3, mode="train"):
+        import torch
+        self.args, self.batch, self.Gmax, self.device, self.rng = args, int(batch), int(Gmax), torch.device(dev), rng
+        self.pos_num, self.neg_ratio, self.mode = int(pos_num), int(neg_ratio), mode
+        self.chunks = args.NUM_CHUNKS[1]
+        self.T = args.T * self.chunks
+        self.budget = self.BUDGET
+        S = self.pos_num * (1 + self.neg_ratio)
+        K, nc, d = self.batch * self.budget, args.num_classes, self.device
+        self.sampled = (torch.zeros((self.batch * self.Gmax * S, self.T, 4), device=d), torch.zeros((self.batch + 1,), dtype=torch.int32, device=d),
+                        torch.zeros((self.batch * self.Gmax, 2), dtype=torch.int32, device=d))
+        self.out = (torch.zeros((K, self.T, 5), device=d), torch.zeros((K, 3, 6 + nc), device=d), torch.zeros((K, 1), device=d),
+                    torch.zeros((1,), device=d), torch.zeros((self.batch, 2), dtype=torch.int32, device=d))
+
+    def select(self, gt, gt_count, pad_tubes):
+        """gt [B,Gmax,chunks,4+NC] float32 pixel boxes, gt_count [B] int32, pad_tubes [B,T,4] (the box of the padded slots), on the device
+        -> (sel [B*20,T,5], tgt [B*20,3,6+NC], mask [B*20,1], inv [1], counts [B,2]), the static buffers."""
+        from . import ops
+        a = self.args
+        if tuple(gt.shape[:3]) != (self.batch, self.Gmax, self.chunks):
+            raise RuntimeError("DeviceClsSelector: gt wants [B=%d,Gmax=%d,chunks=%d,4+NC], got %s" % (self.batch, self.Gmax, self.chunks, tuple(gt.shape)))
+        mid = self.chunks // 2
+        tubes, clip_start, _ = ops.anchor_sample(gt, gt_count, self.rng, mid, float(a.image_size[0]), float(a.image_size[1]), self.T, self.pos_num,
+                                                 self.neg_ratio, 0.75, 0.2, self.mode, out=self.sampled)
+        S = self.pos_num * (1 + self.neg_ratio)
+        out = ops.select_train(tubes, None, None, None, None, clip_start, self.Gmax * S, gt, gt_count, pad_tubes, self.rng, mid, -1, -1, -1,
+                               self.CLS_THRESH, 2.0, self.MAX_POS, self.NEG_RATIO, "uniform", self.budget, out=self.out)
+        # train_cls.py:278,283 sets the classification flag on EVERY selected row (step_select_train: on the positives): one strided copy of
+        # the row mask into column 4 of the centre rows, stream-ordered like the two launches
+        out[1][:, 1, 4].copy_(out[2][:, 0])
+        return out

@@ -12,7 +12,7 @@ from . import dist as sdist
 from .driver import GraphedInference, inference, inference_flat, postprocess
 from .backbone import wgrad_into_grad
 from .optim import FlatAdam, FlatSGD
-from .selection import DeviceSelector, train_select
+from .selection import DeviceClsSelector, DeviceSelector, cls_select, sample_anchors, train_select
 from .driver import _flat_tubes
 from .tube_math import generate_anchors
 
@@ -29,18 +29,18 @@ def step_cfg(**kw):
     return NS(**base)
 
 
-def build_nets(dev, seed=123, heads=3, **cfg):
+def build_nets(dev, seed=123, heads=3, cls_only=False, **cfg):
     args = step_cfg(**cfg)                                        # (overrides of the recipe: dropout=0.3 is scripts/train_step.sh:41)
     torch.manual_seed(seed)                                       # config.py:38 man_seed
     base = BaseNet(args).to(dev).eval()
     ctx = ContextNet(args).to(dev).eval()
     nets = {"roi_net": ROINet("align", 7)}
     for i in range(heads):
-        d = TwoBranchNet(args).to(dev).eval()
+        d = (TwoBranchNet(args, cls_only=True) if cls_only else TwoBranchNet(args)).to(dev).eval()      # (cls_only: train_cls.py:97)
         d.set_device(dev)
         nets["det_net%d" % i] = d
     with torch.no_grad():                                         # keep box deltas small, like a trained regressor
-        for i in range(heads):
+        for i in range(0 if cls_only else heads):
             for nme in ("local_reg", "neighbor_reg1", "neighbor_reg2"):
                 getattr(nets["det_net%d" % i], nme).weight.mul_(0.05)
     return args, base, ctx, nets
@@ -109,7 +109,7 @@ class C4TrainStep:
                  optimizer="adam", dropout=0.0, rng_seed=0, grad_wire="fp32", wire_feedback=True):
         # replicas: the same weights on every rank (same init seed, then rank 0's copy is broadcast once, as DDP does);
         # `seed` only varies the rank's clips
-        self.args, self.base, self.ctx, self.nets = build_nets(dev, 123, heads=max_iter, dropout=dropout)
+        self.args, self.base, self.ctx, self.nets = self._build_nets(dev, max_iter, dropout)
         # dropout > 0 (the reference's recipe: 0.3): the heads' three dropout sites draw from the device-side generator (step_amd.Dropout), whose
         # offset advances inside the captured step; the state exists before any capture and is written from the host only here
         srng.manual_seed(rng_seed)
@@ -147,6 +147,16 @@ class C4TrainStep:
         # fp32 master weights either way; a 16-bit clip makes every activation / data gradient 16-bit (fp32 accumulate),
         # weight gradients stay fp32
         self.x = ava_clips(seed, batch).to(dev).to(dtype)
+        self.batch = batch
+        self.loss = None
+        self._init_tubes(dev, batch, tubes_per_clip, max_iter)
+
+    def _build_nets(self, dev, max_iter, dropout):
+        """(args, BaseNet, ContextNet, nets) of this workload (a subclass with other heads builds its own)"""
+        return build_nets(dev, 123, heads=max_iter, dropout=dropout)
+
+    def _init_tubes(self, dev, batch, tubes_per_clip, max_iter):
+        """the fixed tubes and targets every step trains on (a subclass that selects its tubes holds its own static state instead)"""
         anchors = torch.from_numpy(generate_anchors()[:tubes_per_clip] * 400.0).to(dev)                  # [K,4]
         K = tubes_per_clip
         self.steps = []
@@ -165,8 +175,7 @@ class C4TrainStep:
         t[:, :, 6 + 7] = 1
         self.targets = t
         self.clip_of = torch.arange(batch, device=dev).repeat_interleave(K)
-        self.batch, self.K = batch, K
-        self.loss = None
+        self.K = K
 
     @staticmethod
     def _ctx_per_tube(cx, k):
@@ -612,3 +621,186 @@ class C4SelectTrainStep(C4TrainStep):
             self._gU.replay()
         torch.autograd.graph.increment_version(self.params)
         return self.loss
+
+
+class C4ClsTrainStep(C4TrainStep):
+    """The reference's classification pre-training iteration (train_cls.py:230-322, stage 1 of its two-stage recipe: scripts/train_cls.sh
+    writes the checkpoint scripts/train_step.sh loads as --pretrain_path): backbone + ContextNet, ONE cls_only head on tubes of T = 9 frames
+    (NUM_CHUNKS 1), trained on boxes sampled around the ground truths -- sample_anchors in the loader (data/ava_cls.py:200-261, one positive
+    and three negatives per box), then select_proposals per clip (train_cls.py:263-291) -- with the classification loss alone; one backward,
+    one flat gradient exchange, one fused optimizer launch.  `gt`: 2 ground-truth boxes per clip on one frame, 3 positive classes each.
+
+    The three forms of C4SelectTrainStep:
+      step()          eager, ragged: the reference's program -- selection.sample_anchors and selection.cls_select on the host (the reference's
+                      `random` / `numpy.random` streams), the head sees exactly the selected tubes, loss.mean()
+      step_padded()   eager, STATIC shapes: 20 slots per clip (5 positives x (1 + 3)); padded slots hold the clip's first ground-truth box,
+                      all-zero targets and row weight 0, the loss is the masked sum over the real rows times 1 / (rows * classes); the context
+                      feature goes per tube as a broadcast (no .item() per tube, train_cls.py:307-308)
+      capture()       the padded form as ONE graph (C4TrainStep.capture: with a process group the split form around one eager flat
+                      all-reduce).  selection="host": sampling and selection read no network output, so step() draws them BEFORE the replay,
+                      into pinned blocks that are copied into the graph's static buffers; selection="device" (opt-in): step_anchor_sample and
+                      step_select_train (selection.DeviceClsSelector, draws from `self.rng`, two offsets per iteration) are inside the graph.
+    As in C4SelectTrainStep, step() before capture() is the ragged HOST form whatever `selection` says; `selection_ran` names the last one."""
+    BUDGET = DeviceClsSelector.BUDGET
+
+    def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, capturable=False, force_exchange=False, optimizer="adam", dropout=0.0,
+                 rng_seed=0, selection="host", grad_wire="fp32", wire_feedback=True):
+        if selection not in ("host", "device"):
+            raise ValueError("C4ClsTrainStep: selection is 'host' or 'device', got %r" % (selection,))
+        self.selection = selection
+        self.selection_ran = None
+        self._seed = seed
+        super().__init__(dev, batch=batch, tubes_per_clip=0, seed=seed, max_iter=1, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
+                         optimizer=optimizer, dropout=dropout, rng_seed=rng_seed, grad_wire=grad_wire, wire_feedback=wire_feedback)
+
+    def _build_nets(self, dev, max_iter, dropout):
+        return build_nets(dev, 123, heads=1, cls_only=True, dropout=dropout, T=9, max_iter=1, NUM_CHUNKS={1: 1})     # scripts/train_cls.sh: --T 9
+
+    def _init_tubes(self, dev, batch, tubes_per_clip, max_iter):
+        a = self.args
+        rs = np.random.RandomState(self._seed)
+        anchors = (generate_anchors()[:34] * 400.0).astype(np.float32)
+        self.gt = []
+        for _ in range(batch):
+            t = np.zeros((2, 1, 4 + a.num_classes), np.float32)
+            for g_ in range(2):
+                t[g_, 0, :4] = np.clip(anchors[rs.randint(0, len(anchors))] + rs.uniform(-20, 20, 4).astype(np.float32), 0, 400)
+                t[g_, 0, 4 + rs.randint(0, a.num_classes, 3)] = 1
+            self.gt.append(t)
+        self.budget = self.BUDGET
+        K, Tl = batch * self.budget, a.T * a.NUM_CHUNKS[1]
+        self.Tl = Tl
+        self._selected = []
+        self.pad = np.stack([np.tile(t[0, 0, :4], (Tl, 1)) for t in self.gt]).astype(np.float32)       # a valid box for the padded slots' ROIAlign
+        if self.selection == "device":
+            self.selector = DeviceClsSelector(a, batch, 2, dev, self.rng)
+            self.d_gt = torch.from_numpy(np.stack(self.gt)).to(dev)
+            self.d_gt_count = torch.full((batch,), 2, dtype=torch.int32, device=dev)
+            self.d_pad = torch.from_numpy(self.pad).to(dev)
+            self.s_flat, self.s_tgt, self.s_mask, self.s_inv = self.selector.out[:4]
+        else:
+            shapes = ((K, Tl, 5), (K, 3, 6 + a.num_classes), (K, 1), (1,))
+            self.s_flat, self.s_tgt, self.s_mask, self.s_inv = (torch.zeros(sh, device=dev) for sh in shapes)
+            # TWO sets of pinned blocks, used in turn: the host fills the next iteration's set while the copies of the last one may still be
+            # queued behind a replay; a set is written again only after the event behind its copies has passed
+            self._pinned = [tuple(torch.zeros(sh).pin_memory() for sh in shapes) for _ in range(2)]
+            self._pinned_free = [None, None]
+            self._turn = 0
+            for hf, _, _, _ in self._pinned:
+                for b in range(batch):                            # (valid boxes before the first selection is copied in)
+                    hf[b * self.budget:(b + 1) * self.budget, :, 1:] = torch.from_numpy(self.pad[b])
+                    hf[b * self.budget:(b + 1) * self.budget, :, 0] = b * Tl + torch.arange(Tl, dtype=torch.float32)
+            self.s_flat.copy_(self._pinned[0][0])
+
+    @property
+    def selected(self):
+        """rows selected per clip in the last iteration; with the device selection this reads `counts` (and synchronises)"""
+        if self._selected is None:
+            return [int(v) for v in self.select_counts().sum(axis=1)]
+        return self._selected
+
+    def select_counts(self):
+        """device selection: [B, 2] (positives, negatives) of the last iteration, on the host; synchronises"""
+        return self.selector.out[4].cpu().numpy()
+
+    # ---- the host's sampling and selection (the reference's loader, then its training loop)
+    def _host_selection(self):
+        a = self.args
+        W, H = float(a.image_size[0]), float(a.image_size[1])
+        whwh = np.array([W, H, W, H], np.float64)
+        tubes = []
+        for t in self.gt:                                        # data/ava_cls.py:351-357, one clip after the other
+            boxes = sample_anchors(t[:, 0, :4].astype(np.float64) / whwh, neg_ratio=3, mode="train")
+            tubes.append(np.tile((boxes * whwh).astype(np.float32)[:, None, :], (1, self.Tl, 1)))
+        sel, tgt = cls_select(self.gt, tubes, a)
+        self._selected = [len(s_) for s_ in sel]
+        self.selection_ran = "host"
+        self.last_selection = (sel, tgt)
+        return sel, tgt
+
+    def _select_host_padded(self):
+        """the host selection into the pinned blocks, then four stream-ordered copies into the static buffers"""
+        a = self.args
+        sel, tgt = self._host_selection()
+        Bu = self.budget
+        k = self._turn
+        self._turn = 1 - k
+        if self._pinned_free[k] is not None:
+            self._pinned_free[k].synchronize()
+        blocks = self._pinned[k]
+        hf, ht, hm = blocks[0].numpy(), blocks[1].numpy(), blocks[2].numpy()
+        ht[...] = 0
+        hm[...] = 0
+        for b in range(self.batch):
+            n = len(sel[b])
+            if n > Bu:
+                raise RuntimeError("C4ClsTrainStep: %d tubes selected for one clip, budget %d" % (n, Bu))
+            hf[b * Bu:b * Bu + n, :, 1:] = sel[b]
+            hf[b * Bu + n:(b + 1) * Bu, :, 1:] = self.pad[b]
+            ht[b * Bu:b * Bu + n] = tgt[b]
+            hm[b * Bu:b * Bu + n] = 1
+        blocks[3][0] = 1.0 / (max(sum(self._selected), 1) * a.num_classes)
+        for dst, src in zip((self.s_flat, self.s_tgt, self.s_mask, self.s_inv), blocks):
+            dst.copy_(src, non_blocking=True)
+        if self.s_flat.is_cuda:
+            self._pinned_free[k] = torch.cuda.Event()
+            self._pinned_free[k].record()
+
+    # ---- the ragged eager iteration (the reference's program)
+    def step(self):
+        if self.graph is not None:
+            if self.selection == "host":
+                self._select_host_padded()                       # before the replay: the one graph reads the static buffers
+            return super().step()
+        sel, tgt = self._host_selection()
+        cf = self.base(self.x)
+        cx = self.ctx(cf)
+        flat, nums = _flat_tubes(sel, cf.device)
+        targets = torch.from_numpy(np.concatenate(tgt, axis=0)).to(cf.device)
+        clip_of = torch.as_tensor(np.repeat(np.arange(len(nums)), nums), device=cf.device)
+        pooled = self.nets["roi_net"](cf, flat)
+        pooled = pooled.reshape(flat.shape[0], self.Tl, *pooled.shape[1:])
+        o = self.heads[0](pooled, context_feat=cx[clip_of], tubes=flat, targets=targets)
+        loss = o[4].mean()                                       # train_cls.py:311
+        self.reducer.begin()
+        with wgrad_into_grad():
+            loss.backward()
+        scale = self.reducer.finish()
+        self.opt.step(grad_scale=scale, zero_grad=True)
+        self.loss = loss.detach()
+        return self.loss
+
+    # ---- the padded iteration: C4TrainStep's eager step, exchange, update and capture around this forward / backward
+    def forward_backward(self, exchange=False):
+        if self.selection == "device":                           # two launches, nothing comes back: part of the recording
+            self._selected = None
+            self.selection_ran = "device"
+            self.selector.select(self.d_gt, self.d_gt_count, self.d_pad)
+        K = self.batch * self.budget
+        cf = self.base(self.x)
+        cx = self.ctx(cf)
+        pooled = self.nets["roi_net"](cf, self.s_flat)
+        pooled = pooled.reshape(K, self.Tl, *pooled.shape[1:])
+        o = self.heads[0](pooled, context_feat=self._ctx_per_tube(cx, self.budget), tubes=self.s_flat, targets=self.s_tgt)
+        loss = (o[4].view(K, -1) * self.s_mask).sum() * self.s_inv[0]      # the reference's .mean() runs over the REAL rows only
+        if exchange:
+            self.reducer.begin()
+        with wgrad_into_grad():
+            loss.backward()
+        self.scale = self.reducer.finish() if exchange else 1.0
+        return loss
+
+    def _eager_step(self):
+        # (the host's selection is drawn outside a recording: capture() records this step, step() draws before each replay)
+        if self.selection == "host" and not (self.x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            self._select_host_padded()
+        return super()._eager_step()
+
+    def step_padded(self):
+        return self._eager_step()
+
+    def capture(self, warmup=2, mode="auto"):
+        """C4TrainStep.capture on the padded iteration: ONE graph ("cls-one"), or with a process group the split form ("cls-split")."""
+        super().capture(warmup=warmup, mode=mode)
+        self.graph_mode = "cls-" + self.graph_mode
+        return self

@@ -22,6 +22,9 @@ Every rank
      on every replay (`step_amd.Dropout`, `step_amd.rng`); --rng-seed S seeds it, rank r with S + r,
      --select-device trains on the reference's whole iteration with the proposal selection on the device, drawing from the same generator: one
      graph per iteration instead of two around the host's selection,
+     --cls trains the classification pre-training iteration instead (train_cls.py, the stage whose checkpoint the iteration above starts from): one
+     cls_only head on boxes sampled around the ground truths, ONE graph per iteration; the host draws sampling and selection before each
+     replay, --cls --select-device moves both into the graph (`step_anchor_sample`, `step_select_train`),
      --grad-wire bf16 sends the gradients as bfloat16 with error feedback (`step_amd.dist.GradWire`; --no-wire-feedback: plain rounding),
   6. rank 0 prints one JSON line per --log-every iterations and a final summary (loss, ms per iteration, clips/s of the whole job).
 
@@ -71,6 +74,10 @@ def main():
     ap.add_argument("--select-device", action="store_true",
                     help="implies --select, with the selection on the device (step_select_train, draws from the generator of --rng-seed): the whole "
                          "iteration is captured as ONE graph; the draws are not the reference's")
+    ap.add_argument("--cls", action="store_true",
+                    help="the classification pre-training iteration instead (train_cls.py, stage 1: workloads.C4ClsTrainStep -- one cls_only head on "
+                         "boxes sampled around the ground truths, captured as ONE graph); with --select-device the sampling and the selection run on "
+                         "the device (step_anchor_sample + step_select_train)")
     ap.add_argument("--grad-wire", default="fp32", choices=["fp32", "bf16"],
                     help="what the gradient exchange puts on the link: the fp32 arena, or bfloat16 with error feedback (step_amd.dist.GradWire: half the "
                          "bytes, the rounding error of what a rank sent is added to its next step's gradient)")
@@ -85,7 +92,10 @@ def main():
                     help="process-group backend (default: nccl = RCCL; gloo only to exercise the multi-rank program with ranks SHARING one GPU, "
                          "which RCCL refuses -- the exchange is then one eager flat all-reduce between two captured graphs)")
     a = ap.parse_args()
-    a.select = a.select or a.select_device
+    if a.cls and (a.feed != "none" or a.graph == "one" or a.select or a.tubes != ap.get_default("tubes")):
+        raise SystemExit("train_step_amd.py: --cls takes none of --feed, --graph one, --select and --tubes (its tubes are sampled around the "
+                         "ground truths; --select-device moves that sampling and the selection onto the device)")
+    a.select = (a.select or a.select_device) and not a.cls
     if a.optimizer == "sgd" and a.momentum <= 0:
         raise SystemExit("train_step_amd.py: --momentum must be positive (the workload's momentum buffer is allocated at construction)")
     if a.augment and a.feed != "u8":
@@ -105,7 +115,15 @@ def main():
                          "equal to the single-process loss, SURVEY 8e)")
     tdt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[a.dtype]
     graphed = not a.no_graph and a.dtype != "f32"               # (the fp32 step is GPU-bound and measured slower replayed than eager)
-    if a.select:
+    if a.cls:
+        import random
+        import numpy as np
+        random.seed(1000 + rank)                                 # (the host's sampling and selection draw from the reference's two RNG streams)
+        np.random.seed(1000 + rank)
+        w = workloads.C4ClsTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=graphed, optimizer=a.optimizer, dropout=a.dropout,
+                                     rng_seed=a.rng_seed + rank, selection="device" if a.select_device else "host", grad_wire=a.grad_wire,
+                                     wire_feedback=not a.no_wire_feedback)
+    elif a.select:
         import random
         import numpy as np
         random.seed(1000 + rank)                                 # (the selection draws from the reference's two host RNG streams)
@@ -207,7 +225,8 @@ def main():
                           "gradient_exchange": _exchange_label(w, world),
                           "grad_wire": a.grad_wire, "exchange_bytes_per_step": w.opt.numel * (2 if a.grad_wire == "bf16" else 4), "param_checksum": checksum,
                           "feed": a.feed + ("+augment" if a.augment else ""), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
-                          "dropout": a.dropout, "rng_offset": w.rng.offset(), **({"selection": w.selection_ran} if a.select else {}),
+                          "dropout": a.dropout, "rng_offset": w.rng.offset(), **({"selection": w.selection_ran} if (a.select or a.cls) else {}),
+                          **({"workload": "cls"} if a.cls else {}),
                           **({"adam_steps": w.opt.step_count} if a.optimizer == "adam" else {})}), flush=True)
     if world > 1:
         torch.distributed.barrier()
@@ -220,7 +239,7 @@ def _exchange_label(w, world):
         return None
     backend = torch.distributed.get_backend()
     lib = "RCCL" if backend == "nccl" else backend
-    if getattr(w, "graph_mode", None) in ("split", "select-split", "select-one-split"):
+    if getattr(w, "graph_mode", None) in ("split", "select-split", "select-one-split", "cls-split"):
         return "one eager flat %s all-reduce of the gradient arena between the two graphs, %d ranks" % (lib, world)
     where = "recorded in the step's graph" if w.graph is not None else "eager, overlapped with backward"
     return "bucketed %s all-reduce, %d buckets, %s, %d ranks" % (lib, len(w.reducer.buckets), where, world)
