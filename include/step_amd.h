@@ -52,7 +52,7 @@ enum {
     STEP_E_ALIGN = -5
 };
 
-/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (44: step_anchor_sample). */
+/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (45: step_grad_norm_flat / step_grad_clip_flat / step_lr_schedule). */
 STEP_API const char* step_version(void);
 STEP_API int step_abi_version(void);
 
@@ -736,6 +736,61 @@ STEP_API int step_sgd_flat_amp(float* param, float* grad, float* momentum_buf, l
 STEP_API int step_grad_pack16(int wire_dtype, const float* grad, float* residual, void* wire, long long n, float pre_scale,
                               step_stream_t stream);
 STEP_API int step_grad_unpack16(int wire_dtype, const void* wire, float* grad, long long n, step_stream_t stream);
+
+/* Gradient-norm clipping over the flat gradient arena: torch.nn.utils.clip_grad_norm_(params, max_norm) (L2 norm only) as one streaming
+ * pass, one small finishing launch and -- only where the step is clipped -- one in-place multiply.  Capturable: stream-ordered, no
+ * host read, caller-owned scratch.
+ * step_grad_norm_flat: the L2 norm of grad[0, n) and of every segment of the optimizer's seg_end table (as step_adam_flat: ascending,
+ * multiples of 4, seg_end[n_seg-1] == n, n_seg <= 4096; an empty segment has norm 0).  Sums of squares are fp64 ((double)g * (double)g
+ * is exact) in a FIXED ORDER that depends neither on the grid size nor on scheduling, so two runs give the same bits:
+ *   1. the arena is cut into chunks of STEP_GRAD_NORM_CHUNK elements at fixed positions.  Within a chunk, lane t of the 256-thread
+ *      workgroup adds the four elements of its 16-byte vectors t, t + 256, t + 512, ... in that order; the 64 lanes of a wavefront are
+ *      joined by an xor butterfly (strides 32, 16, 8, 4, 2, 1), the four wavefronts are added in index order.  Where segments meet
+ *      inside a chunk this is done once per segment over the elements of that segment.  The sum of chunk c's part of segment s goes to
+ *      workspace[c + s] (no two parts share a slot; the pass reads 4 n bytes once and uses no atomics);
+ *   2. the finishing launch (one workgroup) gives a wavefront to a segment: lane l adds the segment's parts l, l + 64, ... in chunk
+ *      order, the same butterfly joins the lanes; thread 0 then adds the segment sums in index order.
+ * With S = the total and scale = amp_state ? amp_state[0] : 1 (the LossScaler's state: a loss-scaled step is clipped in UN-scaled units)
+ *   seg_norm[s] = (float)(sqrt(S_s) * |grad_scale| / scale)                     (seg_norm may be NULL)
+ *   stats[0]    = total_norm = (float)(sqrt(S) * |grad_scale| / scale)
+ *   stats[1]    = clip_coef  = min(1, max_norm / (total_norm + 1e-6f))          fp32, torch's arithmetic
+ *   stats[2]    = nonfinite  = 1 where total_norm is inf / NaN (an inf / NaN element, or a finite sum beyond fp32), else 0
+ *   stats[3]    = 0
+ * A non-finite norm sets clip_coef = 1: the gradient is LEFT ALONE (torch would multiply it by 0 or NaN -- a documented divergence), so
+ * that the loss scaler's own scan still finds the overflow and skips the step.  grad_scale is the by-value factor of the optimizer
+ * entries (1 / world).  workspace: step_grad_norm_workspace_bytes(n, n_seg) bytes of 8-byte aligned device scratch; nothing in it needs
+ * initialising.  Errors, nothing written: max_norm <= 0 or NaN, n < 0, n % 4, n_seg <= 0 or > 4096, a workspace that is too short ->
+ * STEP_E_SHAPE; NULL grad / seg_end / workspace / stats -> STEP_E_NULL; grad not 16-byte or workspace not 8-byte aligned ->
+ * STEP_E_ALIGN.  n == 0 -> STEP_OK, nothing launched.  seg_end is DEVICE memory and the call reads nothing back: a table whose last
+ * entry is not n is refused ON THE DEVICE -- both launches return without writing -- and the status cannot report it.
+ * step_grad_clip_flat: grad[i] = grad[i] * stats[1], one rounding; a workgroup that reads a coefficient of exactly 1.0f returns without
+ * touching memory (bit-identical to the multiply), so a step that is not clipped pays only the norm pass.  n % 4, 16-byte aligned. */
+#define STEP_GRAD_NORM_CHUNK 8192
+STEP_API size_t step_grad_norm_workspace_bytes(long long n, int n_seg);
+STEP_API int step_grad_norm_flat(const float* grad, long long n, const long long* seg_end, int n_seg, float grad_scale,
+                                 const float* amp_state, float max_norm, void* workspace, size_t workspace_bytes, float* seg_norm,
+                                 float* stats, step_stream_t stream);
+STEP_API int step_grad_clip_flat(float* grad, long long n, const float* stats, step_stream_t stream);
+
+/* The reference's learning-rate schedules (utils/solver.py:96-172, stepped once per iteration at train.py:262) as ONE tiny launch that
+ * writes the optimizer's seg_lr table, so that a replayed training step takes no learning rate from the host.  The call increments
+ * *iter_dev (int64, device: the scheduler's last_epoch -- separate from the optimizer's step counter; a step skipped for overflow still
+ * advances the schedule, as scheduler.step() does in the reference's loop) and evaluates get_lr() for the new value t, in fp64, one
+ * thread per segment, rounded once to fp32: with base = base_lr[s] (device doubles),
+ *   t < warmup_iters:    base * (warmup_factor * (1 - a) + a),  a = t / warmup_iters                      (both kinds)
+ *   STEP_LR_COSINE:      base*min_ratio + (base * pow(cycle_decay, cycle - 1) - base*min_ratio) * (1 + cos(pi * fraction)) / 2
+ *                        cycle = min(bisect_right(milestones, t), n_milestones - 1), fraction = min((t - milestones[cycle-1]) /
+ *                        (milestones[cycle] - milestones[cycle-1]), 1); the table is the reference's own: warmup_iters PREPENDED to the
+ *                        user's milestones (n_milestones >= 2)
+ *   STEP_LR_STEP:        base * pow(gamma, bisect_right(milestones, t))                                    (n_milestones >= 0)
+ * p0 = min_ratio | gamma, p1 = cycle_decay | unused.  milestones: device int64, strictly ascending, at most STEP_LR_MAX_MILESTONES.
+ * Errors, nothing written: unknown kind, n_seg <= 0 or > 4096, n_milestones out of range, warmup_iters < 0 -> STEP_E_SHAPE; NULL
+ * iter_dev / base_lr / seg_lr (or milestones with n_milestones > 0) -> STEP_E_NULL. */
+enum { STEP_LR_COSINE = 0, STEP_LR_STEP = 1 };
+#define STEP_LR_MAX_MILESTONES 64
+STEP_API int step_lr_schedule(int kind, long long* iter_dev, const double* base_lr, float* seg_lr, int n_seg,
+                              const long long* milestones, int n_milestones, long long warmup_iters, double warmup_factor, double p0,
+                              double p1, step_stream_t stream);
 
 /* The tail of TwoBranchNet.forward (models/two_branch.py:246-342) behind its last two GEMMs, as ONE launch (and one for its backward):
  * the class logits averaged over a tube's frames and their sigmoid, the box regressions (local_loc = columns 0..3 of the fused

@@ -6,7 +6,7 @@ from .heads import ContextNet, Dropout, ROINet, TwoBranchNet  # noqa: F401
 from . import rng  # noqa: F401
 from .rng import DeviceRNG, manual_seed  # noqa: F401
 from . import dist  # noqa: F401
-from .optim import FlatAdam, FlatSGD, LossScaler  # noqa: F401
+from .optim import DeviceWarmupCosineLR, DeviceWarmupStepLR, FlatAdam, FlatSGD, LossScaler  # noqa: F401
 from . import evaluate  # noqa: F401
 from .evaluate import FrameMAP, ava_evaluation  # noqa: F401
 from . import augment  # noqa: F401

@@ -5,7 +5,7 @@ import ctypes as C
 F32, BF16, F16 = 0, 1, 2
 NCHW, NHWC = 0, 1
 ROI_BWD_GATHER, ROI_BWD_ATOMIC = 0, 1
-ABI_VERSION = 44
+ABI_VERSION = 45
 
 vp, fp, ip, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # raw device addresses
 i, f, ll, sz = C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -135,6 +135,10 @@ SIGNATURES = {
     "step_sgd_flat_amp": (i, [fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, i, vp, f, i, fp, f, f, i, vp]),
     "step_grad_pack16": (i, [i, fp, fp, vp, ll, f, vp]),
     "step_grad_unpack16": (i, [i, vp, fp, ll, vp]),
+    "step_grad_norm_workspace_bytes": (sz, [ll, i]),
+    "step_grad_norm_flat": (i, [fp, ll, vp, i, f, fp, f, vp, sz, fp, fp, vp]),
+    "step_grad_clip_flat": (i, [fp, ll, fp, vp]),
+    "step_lr_schedule": (i, [i, vp, vp, fp, i, vp, i, ll, C.c_double, C.c_double, C.c_double, vp]),
 }
 
 

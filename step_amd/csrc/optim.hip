@@ -11,7 +11,8 @@
 //   m += (g - m) * (1 - beta1)                 (Tensor.lerp_)
 //   v  = v * beta2 + (1 - beta2) * g * g
 //   p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
-// Also here, beside the optimizers they feed: the bf16 wire of the data-parallel gradient exchange (grad_pack16 / grad_unpack16).
+// Also here, beside the optimizers they feed: the bf16 wire of the data-parallel gradient exchange (grad_pack16 / grad_unpack16), the
+// gradient-norm clip in front of them (grad_norm / grad_clip) and the learning-rate schedules that write their seg_lr table (lr_schedule).
 #include "common.h"
 #include <cmath>
 #include <cstdlib>
@@ -234,6 +235,207 @@ __global__ __launch_bounds__(256) void grad_unpack16_kernel(const unsigned short
         }
     }
     for (long long e = done + gid; e < n; e += stride) grad[e] = bf16_bits_to_f32(wire[e]);
+}
+
+// ---- gradient-norm clipping (step_grad_norm_flat / step_grad_clip_flat: torch.nn.utils.clip_grad_norm_ over the gradient arena) -----
+// One streaming read of the arena (4 B per element, 16-byte vectors) + one single-workgroup finishing launch; the in-place multiply
+// (8 B per element) only moves data on a step that is clipped.  Sums of squares are fp64 -- (double)g * (double)g is exact, so a
+// contracted multiply-add and a separate one give the same bits, on the device and on the interpreter -- and their ORDER is fixed (the
+// contract is spelled out in include/step_amd.h): chunks of GN_CHUNK elements at fixed positions, whichever workgroup of the grid-stride
+// loop gets them; within a chunk a lane's vectors in ascending order, an xor butterfly across the wavefront (every lane ends with the same
+// bits: each stage adds the same two numbers on both sides), the four wavefronts in index order.  No atomics.
+constexpr int GN_CHUNK = STEP_GRAD_NORM_CHUNK;           // elements per chunk: 8 vectors per lane
+constexpr int GN_VPL = GN_CHUNK / 4 / 256;               // vectors per lane and chunk
+constexpr int GN_FIN_THREADS = 1024;                     // the finishing workgroup: 16 wavefronts ...
+constexpr int GN_FIN_SEGS = 4;                           // ... each summing this many segments at a time ...
+constexpr int GN_FIN_BATCH = 8;                          // ... from batches of this many loads per lane
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// first segment whose end lies beyond element e (the search of the optimizer kernels); n_seg - 1 where there is none
+__device__ __forceinline__ int seg_of(const long long* s_end, int n_seg, long long e) {
+    int lo = 0, hi = n_seg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s_end[mid] > e) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+template <int MAXSEG>
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, long long n, const long long* __restrict__ seg_end,
+                                                                int n_seg, double* __restrict__ ws) {
+    __shared__ long long s_end[MAXSEG];
+    __shared__ double s_wave[2][4];
+    int slot = 0;
+    for (int i = threadIdx.x; i < n_seg; i += blockDim.x) s_end[i] = seg_end[i];
+    __syncthreads();
+    if (s_end[n_seg - 1] != n) return;                     // a table that does not describe this arena: nothing is written (uniform)
+    const long long nchunk = (n + GN_CHUNK - 1) / GN_CHUNK, nvec = n >> 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (long long c = blockIdx.x; c < nchunk; c += gridDim.x) {
+        const long long c0 = c * GN_CHUNK, c1 = c0 + GN_CHUNK < n ? c0 + GN_CHUNK : n;
+        f32x4 v[GN_VPL];
+#pragma unroll
+        for (int j = 0; j < GN_VPL; ++j) {
+            const long long vec = (c0 >> 2) + j * 256 + threadIdx.x;
+            v[j] = vec < nvec ? *(const f32x4*)(g + vec * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        const int sa = seg_of(s_end, n_seg, c0), sb = seg_of(s_end, n_seg, c1 - 1);
+        for (int s = sa; s <= sb; ++s) {                   // usually one turn: the chunk lies inside one tensor
+            const long long lo = s > 0 ? s_end[s - 1] : 0, hi = s_end[s];
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < GN_VPL; ++j) {
+                const long long e = c0 + 4LL * (j * 256 + threadIdx.x);
+                if (sa == sb || (e >= lo && e < hi)) {     // (segment ends are multiples of 4: a vector never straddles two)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc += (double)v[j][k] * (double)v[j][k];
+                }
+            }
+            acc = wave_sum_f64(acc);
+            if (lane == 0) s_wave[slot][wave] = acc;
+            __syncthreads();                               // (two slots in turn: the barrier of the NEXT reduction orders this read before the slot's reuse)
+            if (threadIdx.x == 0) ws[c + s] = ((s_wave[slot][0] + s_wave[slot][1]) + s_wave[slot][2]) + s_wave[slot][3];
+            slot ^= 1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(GN_FIN_THREADS) void grad_norm_finish_kernel(long long n, const long long* __restrict__ seg_end, int n_seg,
+                                                                          const double* __restrict__ ws, float gscale,
+                                                                          const float* __restrict__ amp, float max_norm,
+                                                                          float* __restrict__ seg_norm, float* __restrict__ stats) {
+    __shared__ double s_seg[ADAM_MAX_SEG];
+    if (seg_end[n_seg - 1] != n) return;                   // as the streaming pass: refused on the device, nothing written
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    const double mul = fabs((double)gscale), scale = amp ? (double)amp[0] : 1.0;
+    // a wavefront sums GN_FIN_SEGS segments at a time: their loads are in flight together and their butterflies interleave.  Lane l adds
+    // its segment's parts l, l + 64, ... in chunk order; a batch is loaded first and then added in that order, missing parts as + 0.0 (the
+    // sums are >= 0: adding zero changes no bit)
+    for (int s0 = wave * GN_FIN_SEGS; s0 < n_seg; s0 += nwave * GN_FIN_SEGS) {
+        double acc[GN_FIN_SEGS];
+        long long nxt[GN_FIN_SEGS], last[GN_FIN_SEGS];
+#pragma unroll
+        for (int q = 0; q < GN_FIN_SEGS; ++q) {
+            const int s = s0 + q;
+            long long c = lane, cb = -1;
+            if (s < n_seg) {
+                long long lo = s > 0 ? seg_end[s - 1] : 0, hi = seg_end[s];
+                if (lo < 0) lo = 0;                        // (a table that is not ascending within [0, n] gives wrong sums, never a read outside
+                if (hi > n) hi = n;                        //  the workspace)
+                if (hi > lo) { c = lo / GN_CHUNK + lane; cb = (hi - 1) / GN_CHUNK; }
+            }
+            double v[GN_FIN_BATCH];
+#pragma unroll
+            for (int j = 0; j < GN_FIN_BATCH; ++j) v[j] = c + 64 * j <= cb ? ws[c + 64 * j + s] : 0.0;
+            acc[q] = 0.0;
+#pragma unroll
+            for (int j = 0; j < GN_FIN_BATCH; ++j) acc[q] += v[j];
+            nxt[q] = c + 64 * GN_FIN_BATCH;
+            last[q] = cb;
+        }
+#pragma unroll
+        for (int q = 0; q < GN_FIN_SEGS; ++q) {            // only a tensor beyond 64 x GN_FIN_BATCH chunks (4 M elements) comes here
+            const int s = s0 + q;
+            for (long long c = nxt[q]; c <= last[q]; c += 64 * GN_FIN_BATCH) {
+                double v[GN_FIN_BATCH];
+#pragma unroll
+                for (int j = 0; j < GN_FIN_BATCH; ++j) v[j] = c + 64 * j <= last[q] ? ws[c + 64 * j + s] : 0.0;
+#pragma unroll
+                for (int j = 0; j < GN_FIN_BATCH; ++j) acc[q] += v[j];
+            }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+            for (int q = 0; q < GN_FIN_SEGS; ++q) acc[q] += __shfl_xor(acc[q], m);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int q = 0; q < GN_FIN_SEGS; ++q) {
+                const int s = s0 + q;
+                if (s < n_seg) {
+                    s_seg[s] = acc[q];
+                    if (seg_norm) seg_norm[s] = (float)(sqrt(acc[q]) * mul / scale);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int s = 0; s < n_seg; ++s) tot += s_seg[s];
+        const float norm = (float)(sqrt(tot) * mul / scale);
+        const bool finite = (__builtin_bit_cast(unsigned int, norm) & 0x7f800000u) != 0x7f800000u;
+        float coef = 1.f;
+        if (finite) {
+            coef = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
+            if (!(coef < 1.f)) coef = 1.f;
+        }
+        stats[0] = norm; stats[1] = coef; stats[2] = finite ? 0.f : 1.f; stats[3] = 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void grad_clip_kernel(float* __restrict__ g, long long nvec, const float* __restrict__ stats) {
+    const float coef = stats[1];
+    if (coef == 1.f) return;                               // not clipped: x * 1.0f == x bit for bit, so nothing is read or written
+    for (long long vec = (long long)blockIdx.x * blockDim.x + threadIdx.x; vec < nvec; vec += (long long)blockDim.x * gridDim.x) {
+        f32x4 G = *(const f32x4*)(g + vec * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) G[j] = G[j] * coef;
+        *(f32x4*)(g + vec * 4) = G;
+    }
+}
+
+// ---- the reference's learning-rate schedules on the device (step_lr_schedule; utils/solver.py:96-172) --------------------------------
+// One workgroup: every thread reads the counter, a barrier, thread 0 writes it back incremented; then one thread per segment evaluates
+// get_lr() for the new last_epoch in fp64 -- the operations and their order are Python's -- and rounds once to fp32.
+constexpr int LR_MAX_MS = STEP_LR_MAX_MILESTONES;
+
+__device__ __forceinline__ int bisect_right_ll(const long long* a, int n, long long x) {
+    int k = 0;
+    while (k < n && a[k] <= x) ++k;
+    return k;
+}
+
+__global__ __launch_bounds__(256) void lr_schedule_kernel(int kind, long long* iter, const double* __restrict__ base_lr, float* __restrict__ seg_lr,
+                                                          int n_seg, const long long* __restrict__ milestones, int n_ms, long long warmup_iters,
+                                                          double warmup_factor, double p0, double p1) {
+    __shared__ long long s_ms[LR_MAX_MS];
+    const long long t = *iter + 1;
+    for (int i = threadIdx.x; i < n_ms; i += blockDim.x) s_ms[i] = milestones[i];
+    __syncthreads();
+    if (threadIdx.x == 0) *iter = t;
+    double factor = 0.0, floor_ratio = 0.0;                // lr = base * floor_ratio + (base * factor - base * floor_ratio) * shape, or base * factor
+    double shape = 0.0;
+    const bool warm = t < warmup_iters;
+    if (warm) {
+        const double alpha = (double)t / (double)warmup_iters;
+        factor = warmup_factor * (1.0 - alpha) + alpha;
+    } else if (kind == STEP_LR_COSINE) {
+        int cycle = bisect_right_ll(s_ms, n_ms, t);
+        if (cycle > n_ms - 1) cycle = n_ms - 1;
+        if (cycle < 1) cycle = 1;                          // (a table whose first entry is not warmup_iters: stay inside it)
+        double fraction = (double)(t - s_ms[cycle - 1]) / (double)(s_ms[cycle] - s_ms[cycle - 1]);
+        if (!(fraction < 1.0)) fraction = 1.0;
+        factor = pow(p1, (double)(cycle - 1));
+        floor_ratio = p0;
+        shape = 1.0 + cos(3.141592653589793 * fraction);
+    } else {
+        factor = pow(p0, (double)bisect_right_ll(s_ms, n_ms, t));
+    }
+    for (int s = threadIdx.x; s < n_seg; s += blockDim.x) {
+        const double base = base_lr[s];
+        double lr;
+        if (warm || kind != STEP_LR_COSINE) lr = base * factor;
+        else lr = base * floor_ratio + (base * factor - base * floor_ratio) * shape / 2.0;
+        seg_lr[s] = (float)lr;
+    }
 }
 
 // ---- activation gradient of the fused conv unit ---------------------------------------------------------------------
@@ -556,6 +758,61 @@ int step_grad_unpack16(int wire_dtype, const void* wire, float* grad, long long 
     const unsigned short* w = (const unsigned short*)wire;
     if (vec) STEP_LAUNCH((grad_unpack16_kernel<true>), grid, dim3(256), stream, w, grad, n);
     else STEP_LAUNCH((grad_unpack16_kernel<false>), grid, dim3(256), stream, w, grad, n);
+    return STEP_LAUNCH_CHECK();
+}
+
+static long long grad_norm_chunks(long long n) { return (n + GN_CHUNK - 1) / GN_CHUNK; }
+
+size_t step_grad_norm_workspace_bytes(long long n, int n_seg) {
+    if (n < 0 || n_seg <= 0 || n_seg > ADAM_MAX_SEG) return 0;
+    return (size_t)(grad_norm_chunks(n) + n_seg) * sizeof(double);       // slot c + s: chunk c's part of segment s
+}
+
+int step_grad_norm_flat(const float* grad, long long n, const long long* seg_end, int n_seg, float grad_scale, const float* amp_state,
+                        float max_norm, void* workspace, size_t workspace_bytes, float* seg_norm, float* stats, step_stream_t stream) {
+    if (!(max_norm > 0.f) || n < 0 || (n & 3) || n_seg <= 0 || n_seg > ADAM_MAX_SEG) return STEP_E_SHAPE;
+    if (n == 0) return STEP_OK;
+    if (!grad || !seg_end || !workspace || !stats) return STEP_E_NULL;
+    if (((uintptr_t)grad & 15) || ((uintptr_t)workspace & 7)) return STEP_E_ALIGN;
+    if (workspace_bytes < step_grad_norm_workspace_bytes(n, n_seg)) return STEP_E_SHAPE;
+    long long blocks = grad_norm_chunks(n);
+    if (blocks > 256LL * 8) blocks = 256LL * 8;             // 8 workgroups per CU resident at once, grid-stride over the chunks beyond
+#ifdef STEP_EMUL
+    if (blocks > 2) blocks = 2;                            // (host emulator: let small cases walk the grid-stride loop)
+#endif
+    if (n_seg <= 512)
+        STEP_LAUNCH((grad_norm_partial_kernel<512>), dim3((unsigned)blocks), dim3(256), stream, grad, n, seg_end, n_seg, (double*)workspace);
+    else
+        STEP_LAUNCH((grad_norm_partial_kernel<ADAM_MAX_SEG>), dim3((unsigned)blocks), dim3(256), stream, grad, n, seg_end, n_seg,
+                    (double*)workspace);
+    STEP_LAUNCH(grad_norm_finish_kernel, dim3(1), dim3(GN_FIN_THREADS), stream, n, seg_end, n_seg, (const double*)workspace, grad_scale,
+                amp_state, max_norm, seg_norm, stats);
+    return STEP_LAUNCH_CHECK();
+}
+
+int step_grad_clip_flat(float* grad, long long n, const float* stats, step_stream_t stream) {
+    if (n < 0 || (n & 3)) return STEP_E_SHAPE;
+    if (n == 0) return STEP_OK;
+    if (!grad || !stats) return STEP_E_NULL;
+    if ((uintptr_t)grad & 15) return STEP_E_ALIGN;
+    const long long nvec = n >> 2;
+    long long blocks = (nvec + 255) / 256;
+    if (blocks > 256LL * 32) blocks = 256LL * 32;           // as grad_scan: a pure streaming pass
+#ifdef STEP_EMUL
+    if (blocks > 2) blocks = 2;
+#endif
+    STEP_LAUNCH(grad_clip_kernel, dim3((unsigned)blocks), dim3(256), stream, grad, nvec, stats);
+    return STEP_LAUNCH_CHECK();
+}
+
+int step_lr_schedule(int kind, long long* iter_dev, const double* base_lr, float* seg_lr, int n_seg, const long long* milestones,
+                     int n_milestones, long long warmup_iters, double warmup_factor, double p0, double p1, step_stream_t stream) {
+    if (kind != STEP_LR_COSINE && kind != STEP_LR_STEP) return STEP_E_SHAPE;
+    if (n_seg <= 0 || n_seg > ADAM_MAX_SEG || warmup_iters < 0) return STEP_E_SHAPE;
+    if (n_milestones < (kind == STEP_LR_COSINE ? 2 : 0) || n_milestones > LR_MAX_MS) return STEP_E_SHAPE;
+    if (!iter_dev || !base_lr || !seg_lr || (n_milestones > 0 && !milestones)) return STEP_E_NULL;
+    STEP_LAUNCH(lr_schedule_kernel, dim3(1), dim3(256), stream, kind, iter_dev, base_lr, seg_lr, n_seg, milestones, n_milestones, warmup_iters,
+                warmup_factor, p0, p1);
     return STEP_LAUNCH_CHECK();
 }
 

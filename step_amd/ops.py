@@ -1275,3 +1275,47 @@ def tube_update(flat, local_loc, first_loc, last_loc, clip_of, first_off, last_o
                                    float(height), _lib.dptr(pl), _lib.dptr(pf), _lib.dptr(pla), _lib.dptr(nxt),
                                    _lib.stream_ptr(dev)), "step_tube_update")
     return pl, pf, pla, nxt
+
+
+def grad_norm_workspace(n, n_seg, device):
+    """the fp64 scratch step_grad_norm_flat wants for an arena of n elements in n_seg segments (uninitialised: every slot read is written first)"""
+    nbytes = int(_lib.lib().step_grad_norm_workspace_bytes(int(n), int(n_seg)))
+    return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)
+
+
+def grad_norm_flat(grad, seg_end, max_norm, grad_scale=1.0, amp_state=None, workspace=None, seg_norm=None, stats=None):
+    """step_grad_norm_flat -> (stats, seg_norm, workspace): stats = {total_norm, clip_coef, nonfinite, 0} (4 device floats), seg_norm the
+    per-segment norms, both in units of grad * |grad_scale| / amp_state[0].  No synchronisation; pass the three buffers back in to
+    launch without an allocation (a captured step)."""
+    L = _lib.lib()
+    n, n_seg = grad.numel(), seg_end.numel()
+    if workspace is None:
+        workspace = grad_norm_workspace(n, n_seg, grad.device)
+    if seg_norm is None:
+        seg_norm = torch.zeros(n_seg, dtype=torch.float32, device=grad.device)
+    if stats is None:
+        stats = torch.zeros(4, dtype=torch.float32, device=grad.device)
+    _capi.check(L.step_grad_norm_flat(_lib.dptr(grad), n, _lib.dptr(seg_end), n_seg, float(grad_scale), _lib.dptr(amp_state), float(max_norm),
+                                      _lib.dptr(workspace), workspace.numel() * 8, _lib.dptr(seg_norm), _lib.dptr(stats),
+                                      _lib.stream_ptr(grad.device)), "step_grad_norm_flat")
+    return stats, seg_norm, workspace
+
+
+def grad_clip_flat(grad, stats):
+    """step_grad_clip_flat: grad *= stats[1] in place (nothing is touched where the coefficient is exactly 1)."""
+    _capi.check(_lib.lib().step_grad_clip_flat(_lib.dptr(grad), grad.numel(), _lib.dptr(stats), _lib.stream_ptr(grad.device)),
+                "step_grad_clip_flat")
+    return grad
+
+
+LR_KINDS = {"cosine": 0, "step": 1}
+
+
+def lr_schedule(kind, counter, base_lr, seg_lr, milestones, warmup_iters, warmup_factor, p0, p1=1.0):
+    """step_lr_schedule: counter (int64[1]) += 1, seg_lr[s] = float(get_lr(counter) of base_lr[s]) -- the reference's WarmupCosineLR
+    ("cosine": milestones with warmup_iters prepended, p0 = min_ratio, p1 = cycle_decay) or WarmupStepLR ("step": p0 = gamma).
+    counter, base_lr (float64), seg_lr (float32) and milestones (int64) are device tensors."""
+    _capi.check(_lib.lib().step_lr_schedule(LR_KINDS[kind], _lib.dptr(counter), _lib.dptr(base_lr), _lib.dptr(seg_lr), seg_lr.numel(),
+                                            _lib.dptr(milestones) if milestones.numel() else None, milestones.numel(), int(warmup_iters),
+                                            float(warmup_factor), float(p0), float(p1), _lib.stream_ptr(seg_lr.device)), "step_lr_schedule")
+    return seg_lr

@@ -63,6 +63,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
     host / device step count, and everything of step() around the subclass's launch (`_launch`)."""
 
     grad_wire = None                                             # a step_amd.dist.GradWire registers itself here (on the instance)
+    lr_scheduler = None                                          # a DeviceWarmupCosineLR / DeviceWarmupStepLR attaches itself here: it owns _seg_lr
+    grad_norm = None                                             # clip_grad_norm_ leaves {total_norm, clip_coef, nonfinite, 0} (device) here ...
+    seg_grad_norm = None                                         # ... and the per-tensor norms, in the order of _entries, here
+    _norm_ws = None
 
     def _check_groups(self):
         """hyper-parameters that one launch cannot vary must agree across the groups"""
@@ -154,17 +158,50 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _refresh_tables(self):
         lr = [float(self.param_groups[gi]["lr"]) for gi, _, _, _ in self._entries]
         wd = [float(self.param_groups[gi]["weight_decay"]) for gi, _, _, _ in self._entries]
+        if self.lr_scheduler is not None:                        # a device scheduler writes _seg_lr itself (step_lr_schedule): only the decay
+            if self._tables != (None, wd):
+                self._seg_wd.copy_(torch.tensor(wd, dtype=torch.float32))
+                self._tables = (None, wd)
+            return
         if self._tables != (lr, wd):                             # the schedulers rewrite group['lr'] every iteration
             self._seg_lr.copy_(torch.tensor(lr, dtype=torch.float32))
             self._seg_wd.copy_(torch.tensor(wd, dtype=torch.float32))
             self._tables = (lr, wd)
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale=1.0, zero_grad=False, scaler=None):
+    def clip_grad_norm_(self, max_norm, grad_scale=1.0, scaler=None, norm_type=2.0):
+        """torch.nn.utils.clip_grad_norm_(params, max_norm) over the gradient arena, on the device: one streaming pass and a finishing launch
+        (step_grad_norm_flat), then the in-place multiply (step_grad_clip_flat), which touches nothing on a step that is not clipped.
+        Returns the total norm as a DEVICE scalar -- nothing here synchronises, so the call can be recorded in a captured step -- and leaves
+        `self.grad_norm` = {total_norm, clip_coef, nonfinite, 0} and `self.seg_grad_norm` (one norm per tensor, the order of `_entries`)
+        behind.  The workspace is allocated on the first call: the warm-up steps ahead of a capture create it.
+
+        Units: the norm is that of grad * |grad_scale| (the factor step() takes: 1 / world after a SUM all-reduce), divided by the loss
+        scale when `scaler` is given -- a LossScaler step is clipped in UN-scaled units.  Only the L2 norm is supported.
+        GradWire: call this after the exchange (step(max_grad_norm=) does): it acts on the exchanged gradient, the wire's residual is not
+        involved.  LossScaler: an inf / NaN gradient (or a norm beyond fp32) gives nonfinite = 1 and a coefficient of 1 -- the gradient
+        is left as it is, where torch would multiply it by 0 or NaN, so that the scaler's own scan in step() still skips the step."""
+        if float(norm_type) != 2.0:
+            raise ValueError("%s.clip_grad_norm_: only the L2 norm (norm_type=2) is supported, got %r" % (type(self).__name__, norm_type))
+        from . import ops
+        if self.grad_norm is None:
+            self._norm_ws = ops.grad_norm_workspace(self.numel, len(self._entries), self.device)
+            self.grad_norm = torch.zeros(4, dtype=torch.float32, device=self.device)
+            self.seg_grad_norm = torch.zeros(len(self._entries), dtype=torch.float32, device=self.device)
+        ops.grad_norm_flat(self.flat_grad, self._seg_end, max_norm, grad_scale=grad_scale, amp_state=None if scaler is None else scaler.state,
+                           workspace=self._norm_ws, seg_norm=self.seg_grad_norm, stats=self.grad_norm)
+        ops.grad_clip_flat(self.flat_grad, self.grad_norm)
+        return self.grad_norm[0]
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale=1.0, zero_grad=False, scaler=None, max_grad_norm=None, norm_type=2.0):
         """optimizer.step() (train.py:348): one kernel launch.  grad_scale multiplies every gradient on the way in
         (1/world_size after a SUM all-reduce, 1/loss_scale); zero_grad=True clears the gradient arena in the same pass.
         scaler = a LossScaler whose scale the loss was multiplied by: the gradients are scanned for inf / nan, unscaled, and the
-        step is skipped on overflow (apex O1 / GradScaler semantics), all on the device (step_adam_flat_amp / step_sgd_flat_amp)."""
+        step is skipped on overflow (apex O1 / GradScaler semantics), all on the device (step_adam_flat_amp / step_sgd_flat_amp).
+        max_grad_norm = a positive number: clip_grad_norm_(max_grad_norm, grad_scale, scaler) runs ahead of the update -- behind the
+        side-stream weight gradients and the stray-gradient fold, hence on the exchanged gradient (a GradWire's residual is not involved),
+        in un-scaled units under a LossScaler, whose skip an overflow still reaches (see clip_grad_norm_).  None launches nothing."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -179,6 +216,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if scaler is not None and self.grad_wire is not None and self.grad_wire.error_feedback:
             raise RuntimeError("%s.step(scaler=...): the gradient wire keeps an error-feedback residual, which would be in units of a loss "
                                "scale that changes on overflow -- use GradWire(error_feedback=False) with a LossScaler" % type(self).__name__)
+        if max_grad_norm is not None:
+            self.clip_grad_norm_(max_grad_norm, grad_scale=grad_scale, scaler=scaler, norm_type=norm_type)
         self._launch(_lib.lib(), float(grad_scale), int(bool(zero_grad)), scaler)
         # the kernel wrote through raw pointers: bump the autograd version counters (the packed-weight caches of
         # backbone.py / heads.py are keyed on them)
@@ -367,3 +406,101 @@ class FlatSGD(_FlatOptimizer):
         if len(have) != 1:
             raise ValueError("FlatSGD.load_state_dict: some parameters have a momentum buffer and some do not")
         self.step_count = max(self.step_count, 1) if have.pop() else 0
+
+
+class _DeviceLRScheduler:
+    """The reference's per-iteration learning-rate schedules (utils/solver.py:96-172; `scheduler.step()` at train.py:262) with the iteration
+    counter and the arithmetic on the device: `.step()` is ONE launch of step_lr_schedule, which advances `last_epoch` (an int64 on the
+    device) and writes the optimizer's `seg_lr` table, so it can be recorded in a captured training step ahead of `optimizer.step()` and
+    a replayed iteration takes no learning rate from the host.  For FlatAdam / FlatSGD built with capturable=True.
+
+    As torch's _LRScheduler: the base lrs are the groups' `initial_lr` (set from `lr` at construction when last_epoch == -1, required
+    otherwise), and construction takes the first step (last_epoch -1 -> 0).  The schedule's counter is its own: a step the LossScaler
+    skips for overflow still advances it, as the reference's loop does.  While a scheduler is attached the optimizer's `_refresh_tables`
+    keeps writing the weight decay but leaves `seg_lr` alone; `param_groups[i]['lr']` is refreshed by get_last_lr() (which synchronises),
+    for logging."""
+
+    _kind = None
+
+    def __init__(self, optimizer, milestones, warmup_iters, warmup_factor, last_epoch, p0, p1):
+        if not isinstance(optimizer, _FlatOptimizer) or not optimizer.capturable:
+            raise RuntimeError("%s: wants a FlatAdam / FlatSGD built with capturable=True" % type(self).__name__)
+        milestones = [int(m) for m in milestones]
+        if milestones != sorted(milestones):
+            raise ValueError("Milestones should be a list of increasing integers. Got {}".format(milestones))
+        table = self._table(milestones, int(warmup_iters))
+        if len(table) > 64:
+            raise ValueError("%s: at most 64 milestones" % type(self).__name__)
+        if any(b <= a for a, b in zip(table, table[1:])) and self._kind == "cosine":
+            raise ValueError("%s: warmup_iters and the milestones must be strictly increasing, got %s" % (type(self).__name__, table))
+        if optimizer.lr_scheduler is not None:
+            raise RuntimeError("%s: the optimizer already has a device scheduler" % type(self).__name__)
+        self.optimizer, self.milestones = optimizer, milestones
+        self.warmup_iters, self.warmup_factor = int(warmup_iters), float(warmup_factor)
+        self._p0, self._p1 = float(p0), float(p1)
+        if last_epoch == -1:
+            for g in optimizer.param_groups:
+                g.setdefault("initial_lr", g["lr"])
+        elif any("initial_lr" not in g for g in optimizer.param_groups):
+            raise KeyError("param 'initial_lr' is not specified in param_groups when resuming an optimizer")
+        self.base_lrs = [float(g["initial_lr"]) for g in optimizer.param_groups]
+        dev = optimizer.device
+        self._base = torch.tensor([self.base_lrs[gi] for gi, _, _, _ in optimizer._entries], dtype=torch.float64).to(dev)
+        self._ms = torch.tensor(table, dtype=torch.int64).to(dev)
+        self._iter = torch.full((1,), int(last_epoch), dtype=torch.int64).to(dev)
+        optimizer.lr_scheduler = self
+        optimizer._tables = None
+        self.step()                                              # torch's _initial_step
+
+    def _table(self, milestones, warmup_iters):
+        return milestones
+
+    def step(self):
+        from . import ops
+        ops.lr_schedule(self._kind, self._iter, self._base, self.optimizer._seg_lr, self._ms, self.warmup_iters, self.warmup_factor, self._p0, self._p1)
+
+    @property
+    def last_epoch(self):
+        return int(self._iter.item())
+
+    def get_last_lr(self):
+        """the learning rates the last step() wrote, one per group (reads the device table: synchronises); also refreshes
+        param_groups[i]['lr'] for logging"""
+        table = self.optimizer._seg_lr.tolist()
+        lrs = list(self.base_lrs)
+        for k, (gi, _, _, _) in enumerate(self.optimizer._entries):
+            lrs[gi] = table[k]
+        for g, lr in zip(self.optimizer.param_groups, lrs):
+            g["lr"] = lr
+        return lrs
+
+    def state_dict(self):
+        return {"last_epoch": self.last_epoch}
+
+    def load_state_dict(self, sd):
+        """resume: the counter is set to last_epoch and seg_lr re-evaluated for it (no step is taken)"""
+        self._iter.fill_(int(sd["last_epoch"]) - 1)
+        self.step()
+
+
+class DeviceWarmupCosineLR(_DeviceLRScheduler):
+    """utils/solver.py:96-138 WarmupCosineLR -- linear warm-up, then cosine annealing with restarts at `milestones`, the peak decayed by
+    `cycle_decay` per cycle, the floor at `min_ratio` x base -- on the device (see _DeviceLRScheduler)."""
+    _kind = "cosine"
+
+    def __init__(self, optimizer, milestones, min_ratio=0., cycle_decay=1., warmup_iters=1000, warmup_factor=1. / 10, last_epoch=-1):
+        self.min_ratio, self.cycle_decay = min_ratio, cycle_decay
+        super().__init__(optimizer, milestones, warmup_iters, warmup_factor, last_epoch, min_ratio, cycle_decay)
+
+    def _table(self, milestones, warmup_iters):
+        return [warmup_iters] + milestones                       # the reference's own table (solver.py:116)
+
+
+class DeviceWarmupStepLR(_DeviceLRScheduler):
+    """utils/solver.py:140-172 WarmupStepLR -- linear warm-up, then base x gamma^(milestones passed) -- on the device (see
+    _DeviceLRScheduler)."""
+    _kind = "step"
+
+    def __init__(self, optimizer, milestones, gamma=0.1, warmup_iters=1000, warmup_factor=1. / 10, last_epoch=-1):
+        self.gamma = gamma
+        super().__init__(optimizer, milestones, warmup_iters, warmup_factor, last_epoch, gamma, 1.0)

@@ -106,7 +106,7 @@ class C4TrainStep:
     same `tubes_per_clip` anchor tubes, extended to the step's length."""
 
     def __init__(self, dev, batch=1, tubes_per_clip=5, seed=123, max_iter=3, dtype=torch.float32, capturable=False, force_exchange=False,
-                 optimizer="adam", dropout=0.0, rng_seed=0, grad_wire="fp32", wire_feedback=True):
+                 optimizer="adam", dropout=0.0, rng_seed=0, grad_wire="fp32", wire_feedback=True, max_grad_norm=None, lr_schedule=None):
         # replicas: the same weights on every rank (same init seed, then rank 0's copy is broadcast once, as DDP does);
         # `seed` only varies the rank's clips
         self.args, self.base, self.ctx, self.nets = self._build_nets(dev, max_iter, dropout)
@@ -128,6 +128,12 @@ class C4TrainStep:
             self.opt = FlatSGD(self.params, lr=1e-5, momentum=0.9, weight_decay=1e-7, capturable=capturable)
         else:
             raise ValueError("C4TrainStep: optimizer is 'adam' or 'sgd', got %r" % (optimizer,))
+        # max_grad_norm: FlatAdam / FlatSGD.step(max_grad_norm=) -- the gradient-norm clip in front of the optimizer launch, on the EXCHANGED
+        # gradient; lr_schedule: a callable that builds a device scheduler on the optimizer (lambda opt: DeviceWarmupCosineLR(opt, [..])),
+        # stepped in front of every optimizer step.  Both are launches of the step itself: capture() records them (in the split form, in the
+        # update graph), and the replayed iteration takes neither a norm decision nor a learning rate from the host
+        self.max_grad_norm = max_grad_norm
+        self.sched = lr_schedule(self.opt) if lr_schedule is not None else None
         self.graph = None
         self.graph_mode = None                                   # "one" | "split" after capture()
         self._g_update = None
@@ -203,9 +209,16 @@ class C4TrainStep:
         self.scale = self.reducer.finish() if exchange else 1.0
         return loss
 
+    def _update(self, grad_scale):
+        """scheduler.step() (train.py:262) and optimizer.step() (train.py:348) of one iteration: the device schedule, the clip, the update
+        that also clears the gradients for the next backward"""
+        if self.sched is not None:
+            self.sched.step()
+        self.opt.step(grad_scale=grad_scale, zero_grad=True, max_grad_norm=self.max_grad_norm)
+
     def _eager_step(self):
         loss = self.forward_backward(exchange=True)
-        self.opt.step(grad_scale=self.scale, zero_grad=True)     # gradients are clean for the next backward
+        self._update(self.scale)
         self.loss = loss.detach()
         return self.loss
 
@@ -311,7 +324,7 @@ class C4TrainStep:
             world = dd.get_world_size() if (dd.is_available() and dd.is_initialized()) else 1
             g2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g2, **kw):
-                self.opt.step(grad_scale=1.0 / world, zero_grad=True)
+                self._update(1.0 / world)
             self.graph, self._g_update, self.graph_mode = g1, g2, "split"
         # host-side caches now carry the version stamps of a step whose kernels only run on replay: make them stale again for
         # any eager use of the modules after this point
@@ -348,11 +361,13 @@ class C4SelectTrainStep(C4TrainStep):
     uncaptured calls step_padded() (train_step_amd.py --select-device --no-graph does)."""
 
     def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, tubes_per_clip=34, capturable=False, force_exchange=False, budget=None,
-                 optimizer="adam", dropout=0.0, rng_seed=0, selection="host", grad_wire="fp32", wire_feedback=True):
+                 optimizer="adam", dropout=0.0, rng_seed=0, selection="host", grad_wire="fp32", wire_feedback=True, max_grad_norm=None,
+                 lr_schedule=None):
         if selection not in ("host", "device"):
             raise ValueError("C4SelectTrainStep: selection is 'host' or 'device', got %r" % (selection,))
         super().__init__(dev, batch=batch, tubes_per_clip=5, seed=seed, max_iter=3, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
-                         optimizer=optimizer, dropout=dropout, rng_seed=rng_seed, grad_wire=grad_wire, wire_feedback=wire_feedback)
+                         optimizer=optimizer, dropout=dropout, rng_seed=rng_seed, grad_wire=grad_wire, wire_feedback=wire_feedback,
+                         max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
         rs = np.random.RandomState(seed)
         anchors = (generate_anchors()[:tubes_per_clip] * 400.0).astype(np.float32)
         self.init_tubes = [np.tile(anchors[:, None, :], (1, 3, 1)) for _ in range(batch)]
@@ -448,7 +463,7 @@ class C4SelectTrainStep(C4TrainStep):
         with wgrad_into_grad():
             loss.backward()
         scale = self.reducer.finish()
-        self.opt.step(grad_scale=scale, zero_grad=True)
+        self._update(scale)
         self.loss = loss.detach()
         return self.loss
 
@@ -535,7 +550,7 @@ class C4SelectTrainStep(C4TrainStep):
             loss.backward()
         if update:
             scale = self.reducer.finish()
-            self.opt.step(grad_scale=scale, zero_grad=True)
+            self._update(scale)
         self.loss = loss.detach()
         return self.loss
 
@@ -578,7 +593,7 @@ class C4SelectTrainStep(C4TrainStep):
                 world = dd.get_world_size() if (dd.is_available() and dd.is_initialized()) else 1
                 gU = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gU, pool=g.pool(), **kw):
-                    self.opt.step(grad_scale=1.0 / world, zero_grad=True)
+                    self._update(1.0 / world)
             self._gF, self._gB, self._gU = g, None, gU
             self.graph, self.graph_mode = g, ("select-one-split" if grouped else "select-one")
             torch.autograd.graph.increment_version(self.params)
@@ -604,7 +619,7 @@ class C4SelectTrainStep(C4TrainStep):
             world = dd.get_world_size() if (dd.is_available() and dd.is_initialized()) else 1
             gU = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gU, pool=pool, **kw):
-                self.opt.step(grad_scale=1.0 / world, zero_grad=True)
+                self._update(1.0 / world)
         self._gF, self._gB, self._gU = gF, gB, gU
         self.graph, self.graph_mode = gF, ("select-split" if grouped else "select")
         torch.autograd.graph.increment_version(self.params)
@@ -644,14 +659,15 @@ class C4ClsTrainStep(C4TrainStep):
     BUDGET = DeviceClsSelector.BUDGET
 
     def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, capturable=False, force_exchange=False, optimizer="adam", dropout=0.0,
-                 rng_seed=0, selection="host", grad_wire="fp32", wire_feedback=True):
+                 rng_seed=0, selection="host", grad_wire="fp32", wire_feedback=True, max_grad_norm=None, lr_schedule=None):
         if selection not in ("host", "device"):
             raise ValueError("C4ClsTrainStep: selection is 'host' or 'device', got %r" % (selection,))
         self.selection = selection
         self.selection_ran = None
         self._seed = seed
         super().__init__(dev, batch=batch, tubes_per_clip=0, seed=seed, max_iter=1, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
-                         optimizer=optimizer, dropout=dropout, rng_seed=rng_seed, grad_wire=grad_wire, wire_feedback=wire_feedback)
+                         optimizer=optimizer, dropout=dropout, rng_seed=rng_seed, grad_wire=grad_wire, wire_feedback=wire_feedback,
+                         max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
 
     def _build_nets(self, dev, max_iter, dropout):
         return build_nets(dev, 123, heads=1, cls_only=True, dropout=dropout, T=9, max_iter=1, NUM_CHUNKS={1: 1})     # scripts/train_cls.sh: --T 9
@@ -766,7 +782,7 @@ class C4ClsTrainStep(C4TrainStep):
         with wgrad_into_grad():
             loss.backward()
         scale = self.reducer.finish()
-        self.opt.step(grad_scale=scale, zero_grad=True)
+        self._update(scale)
         self.loss = loss.detach()
         return self.loss
 

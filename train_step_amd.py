@@ -26,6 +26,9 @@ Every rank
      cls_only head on boxes sampled around the ground truths, ONE graph per iteration; the host draws sampling and selection before each
      replay, --cls --select-device moves both into the graph (`step_anchor_sample`, `step_select_train`),
      --grad-wire bf16 sends the gradients as bfloat16 with error feedback (`step_amd.dist.GradWire`; --no-wire-feedback: plain rounding),
+     --clip-grad-norm X clips the (exchanged) gradient to an L2 norm of X inside the step (`step_grad_norm_flat` / `step_grad_clip_flat`) and
+     logs the norm; --scheduler cosine|step runs the reference's WarmupCosineLR / WarmupStepLR on the device (`step_lr_schedule`, recorded in
+     the graph: the replayed iteration takes no learning rate from the host; the lr is read back on log iterations only),
   6. rank 0 prints one JSON line per --log-every iterations and a final summary (loss, ms per iteration, clips/s of the whole job).
 
 Data: synthetic AVA-shaped clips [B,36,3,400,400] and fixed anchor tubes (there is no dataset in this repository; the reference's
@@ -66,6 +69,19 @@ def main():
     ap.add_argument("--rng-seed", type=int, default=0, help="seed S of the dropout generator; rank r seeds S + r, so data-parallel ranks draw different masks")
     ap.add_argument("--warmup-iters", type=int, default=3, help="eager iterations before the capture (caches, workspaces, communicator)")
     ap.add_argument("--lr-decay-every", type=int, default=0, help="> 0: multiply every group's lr by 0.1 every that many iterations (scheduler stand-in)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None,
+                    help="clip the gradient's L2 norm to this value in front of the optimizer launch (torch.nn.utils.clip_grad_norm_ on the device, "
+                         "after the exchange); the log lines gain grad_norm")
+    ap.add_argument("--scheduler", default=None, choices=["cosine", "step"],
+                    help="the reference's WarmupCosineLR / WarmupStepLR (utils/solver.py:96-172) on the device, base lr = --lr, stepped once per iteration "
+                         "inside the captured step (step_amd.DeviceWarmupCosineLR / DeviceWarmupStepLR)")
+    ap.add_argument("--milestones", default="", help="--scheduler: comma-separated iterations (cosine: the end of each cycle; step: where the lr drops)")
+    ap.add_argument("--sched-warmup-iters", type=int, default=1000,
+                    help="--scheduler: iterations of linear warm-up, the schedulers' warmup_iters (--warmup-iters is the eager warm-up ahead of the capture)")
+    ap.add_argument("--warmup-factor", type=float, default=0.1, help="--scheduler: the lr factor the warm-up starts from")
+    ap.add_argument("--min-ratio", type=float, default=0.0, help="--scheduler cosine: the floor, as a ratio of the base lr")
+    ap.add_argument("--cycle-decay", type=float, default=1.0, help="--scheduler cosine: the peak is multiplied by this after every cycle")
+    ap.add_argument("--gamma", type=float, default=0.1, help="--scheduler step: the factor at every milestone")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--graph", default="auto", choices=["auto", "one", "split"])
     ap.add_argument("--select", action="store_true",
@@ -100,9 +116,14 @@ def main():
         raise SystemExit("train_step_amd.py: --momentum must be positive (the workload's momentum buffer is allocated at construction)")
     if a.augment and a.feed != "u8":
         raise SystemExit("train_step_amd.py: --augment needs --feed u8 (the augmentation reads the uint8 frames)")
+    if a.scheduler and a.lr_decay_every:
+        raise SystemExit("train_step_amd.py: --scheduler and --lr-decay-every both write the learning rate; pick one")
+    if a.clip_grad_norm is not None and not a.clip_grad_norm > 0:
+        raise SystemExit("train_step_amd.py: --clip-grad-norm must be positive")
     if not torch.cuda.is_available():
         raise SystemExit("train_step_amd.py needs a ROCm device (there is no CPU fallback)")
 
+    import step_amd
     from step_amd import dist as sdist, ops, workloads
     rank, world = sdist.init(a.backend)
     local = int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count()
@@ -115,26 +136,39 @@ def main():
                          "equal to the single-process loss, SURVEY 8e)")
     tdt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[a.dtype]
     graphed = not a.no_graph and a.dtype != "f32"               # (the fp32 step is GPU-bound and measured slower replayed than eager)
+    lr_schedule = None
+    if a.scheduler:
+        milestones = [int(v) for v in a.milestones.split(",") if v.strip()]
+
+        def lr_schedule(opt):
+            for g in opt.param_groups:                            # the schedule's base lr is --lr (the workload builds its optimizer with its own)
+                g["lr"] = a.lr
+            if a.scheduler == "cosine":
+                return step_amd.DeviceWarmupCosineLR(opt, milestones, min_ratio=a.min_ratio, cycle_decay=a.cycle_decay, warmup_iters=a.sched_warmup_iters,
+                                                     warmup_factor=a.warmup_factor)
+            return step_amd.DeviceWarmupStepLR(opt, milestones, gamma=a.gamma, warmup_iters=a.sched_warmup_iters, warmup_factor=a.warmup_factor)
+    extra = dict(max_grad_norm=a.clip_grad_norm, lr_schedule=lr_schedule)
+    capturable = graphed or bool(a.scheduler)                    # (a device scheduler wants the device-counted optimizer, captured or not)
     if a.cls:
         import random
         import numpy as np
         random.seed(1000 + rank)                                 # (the host's sampling and selection draw from the reference's two RNG streams)
         np.random.seed(1000 + rank)
-        w = workloads.C4ClsTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=graphed, optimizer=a.optimizer, dropout=a.dropout,
+        w = workloads.C4ClsTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=capturable, optimizer=a.optimizer, dropout=a.dropout,
                                      rng_seed=a.rng_seed + rank, selection="device" if a.select_device else "host", grad_wire=a.grad_wire,
-                                     wire_feedback=not a.no_wire_feedback)
+                                     wire_feedback=not a.no_wire_feedback, **extra)
     elif a.select:
         import random
         import numpy as np
         random.seed(1000 + rank)                                 # (the selection draws from the reference's two host RNG streams)
         np.random.seed(1000 + rank)
-        w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=graphed, optimizer=a.optimizer,
+        w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=capturable, optimizer=a.optimizer,
                                         dropout=a.dropout, rng_seed=a.rng_seed + rank, selection="device" if a.select_device else "host",
-                                        grad_wire=a.grad_wire, wire_feedback=not a.no_wire_feedback)
+                                        grad_wire=a.grad_wire, wire_feedback=not a.no_wire_feedback, **extra)
     else:
-        w = workloads.C4TrainStep(dev, batch=len(mine), tubes_per_clip=a.tubes, seed=123 + rank, dtype=tdt, capturable=graphed,
+        w = workloads.C4TrainStep(dev, batch=len(mine), tubes_per_clip=a.tubes, seed=123 + rank, dtype=tdt, capturable=capturable,
                                   optimizer=a.optimizer, dropout=a.dropout, rng_seed=a.rng_seed + rank, grad_wire=a.grad_wire,
-                                  wire_feedback=not a.no_wire_feedback)
+                                  wire_feedback=not a.no_wire_feedback, **extra)
     for g in w.opt.param_groups:
         g["lr"] = a.lr
         if a.optimizer == "sgd":
@@ -203,8 +237,10 @@ def main():
         if rank == 0 and a.log_every and (it + 1) % a.log_every == 0:
             lv = float(loss)                                      # (one host sync per log line)
             now = time.perf_counter()
-            print(json.dumps({"iter": it + 1, "loss": round(lv, 6), "ms_per_iter": round((now - tl) / a.log_every * 1e3, 3),
-                              "lr": w.opt.param_groups[0]["lr"]}), flush=True)
+            lr = w.sched.get_last_lr()[0] if w.sched is not None else w.opt.param_groups[0]["lr"]     # (device schedule: read back here only)
+            norm = {"grad_norm": round(float(w.opt.grad_norm[0]), 6)} if a.clip_grad_norm is not None else {}
+            print(json.dumps({"iter": it + 1, "loss": round(lv, 6), "ms_per_iter": round((now - tl) / a.log_every * 1e3, 3), "lr": lr, **norm}),
+                  flush=True)
             tl = now
     torch.cuda.synchronize()
     if world > 1:
@@ -227,6 +263,8 @@ def main():
                           "feed": a.feed + ("+augment" if a.augment else ""), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
                           "dropout": a.dropout, "rng_offset": w.rng.offset(), **({"selection": w.selection_ran} if (a.select or a.cls) else {}),
                           **({"workload": "cls"} if a.cls else {}),
+                          **({"clip_grad_norm": a.clip_grad_norm, "grad_norm": round(float(w.opt.grad_norm[0]), 6)} if a.clip_grad_norm is not None else {}),
+                          **({"scheduler": a.scheduler, "last_epoch": w.sched.last_epoch, "lr": w.sched.get_last_lr()[0]} if w.sched is not None else {}),
                           **({"adam_steps": w.opt.step_count} if a.optimizer == "adam" else {})}), flush=True)
     if world > 1:
         torch.distributed.barrier()
