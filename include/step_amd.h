@@ -199,8 +199,11 @@ STEP_API int step_nms_batched_f64(const double* boxes, const double* scores, con
  * direction become the whole frame), greedy NMS among them with the semantics of step_nms_batched (the reference compacts the
  * masked boxes first, order kept, so ties go to the lower tube).
  *   prob  [N, >= NC] fp32, row stride prob_stride elements     loc [N, >= 4] fp32, row stride loc_stride (x1,y1,x2,y2 in pixels)
- *   tube_start / tube_count [B] int32: clip b owns tubes tube_start[b] .. + tube_count[b] (<= kmax <= 64; more: STEP_E_UNSUPPORTED)
+ *   tube_start / tube_count [B] int32: clip b owns tubes tube_start[b] .. + tube_count[b] (<= kmax <= STEP_DETECT_TUBES_MAX = 1024;
+ *   more: STEP_E_UNSUPPORTED)
  *   keep [B, NC, kmax] uint8: 1 at the ORIGINAL slot of every surviving tube      boxes_out [N,4] (optional): the clamped boxes
+ * Launch: B * NC groups; kmax <= 64: one wavefront per group, slot = lane, state in registers; 64 < kmax <= 1024: one 256-thread
+ * workgroup per group, state in 28.3 KiB of LDS (no scratch buffer), one barrier per KEPT box.  Results are the same bit for bit.
  */
 STEP_API int step_detect_nms(const float* prob, long long prob_stride, int NC, const float* loc, long long loc_stride,
                              const int32_t* tube_start, const int32_t* tube_count, int B, int kmax, float conf_thresh,
@@ -213,6 +216,7 @@ STEP_API int step_detect_nms(const float* prob, long long prob_stride, int NC, c
  * original order): out_boxes [I*B*cap, 4] = box / [W,H,W,H] (test.py:197-198), out_scores, out_cls (class index), out_tube (index of the
  * tube inside its clip), counts [I*B] int32. */
 #define STEP_DETECT_ITERS_MAX 8
+#define STEP_DETECT_TUBES_MAX 1024
 STEP_API int step_detect_compact(const uint8_t* keep, const float* const* boxes, const float* const* scores, const long long* score_strides,
                                  const int32_t* tube_start, int I, int B, int NC, int kmax, float width, float height, float* out_boxes,
                                  float* out_scores, long long* out_cls, long long* out_tube, int32_t* counts, step_stream_t stream);

@@ -9,7 +9,8 @@
 // CPU calls per batch.  Here all groups go in ONE launch:
 //   * kmax <= 64  : one 64-lane wavefront per group, boxes live in registers, the greedy scan is a
 //                   loop of cross-lane broadcasts -- no LDS, no global scratch, no host round trip;
-//   * kmax  > 64  : one 256-thread workgroup per group with a global scratch rank table.
+//   * kmax  > 64  : one 256-thread workgroup per group with a global scratch rank table (step_nms_batched), or with all state in LDS
+//                   (step_detect_nms up to 1024 tubes: detect_nms_block_kernel).
 // Arithmetic: "+1" areas, IoU = inter / (area_i + area_j - inter) with every operation rounded
 // separately (__f*_rn: no FMA contraction), suppress when IoU >= threshold (nms_cpu.cpp:84 -- the
 // CUDA op uses '>', nms.cu:84; parity target is the CPU op), ties in score broken by lower index.
@@ -148,6 +149,126 @@ __global__ void detect_nms_wave_kernel(const float* __restrict__ prob, long long
         if (valid && !suppressed && rank > r && iou_ge(bx1, by1, bx2, by2, barea, x1, y1, x2, y2, area, thr)) suppressed = true;
     }
     if (lane < kmax) keep[((size_t)b * NC + c) * kmax + lane] = (valid && !suppressed) ? 1 : 0;
+}
+
+// The same contract for 64 < kmax <= STEP_DETECT_TUBES_MAX: one 256-thread workgroup per (clip, class), all state in LDS (28.3 KiB), no
+// global scratch.  Thread t owns slots t, t + 256, t + 512, t + 768 (the load and clamp of the wave kernel restated, not shared: DESIGN
+// 3.14).
+//   1. load / clamp / mask; the slot-order scores and the "masked" bitmap (one ballot per 64 slots) go to LDS; an unmasked slot's flag is
+//      cleared here.  A group with no masked slot leaves after this.
+//   2. rank of every masked slot by counting against LDS broadcasts of the MASKED scores only (the walk over the set bits is uniform for
+//      the workgroup); box, area and slot go to LDS at position rank: the list in NMS order.
+//   3. the scan, as in detect_merge_kernel: `alive` is a bitmap in rank order; the next kept box is the first set bit past the previous
+//      one (16 words: one ballot + ctz, every wave finds the same one); the four waves take the later words round-robin, lane = position,
+//      and clear the suppressed bits with ONE plain 64-bit store of the wave's ballot per word (a word belongs to one wave).  The search
+//      reads only bits at or past the leader, the scan clears only bits past it: ONE barrier per KEPT box.
+//   4. keep[slot_of[p]] = alive bit p.  Every slot < kmax is written exactly once (here or in 1).
+#define DN_SLOTS STEP_DETECT_TUBES_MAX
+#define DN_WORDS (DN_SLOTS / 64)
+#define DN_PER_THREAD (DN_SLOTS / 256)
+__global__ __launch_bounds__(256) void detect_nms_block_kernel(const float* __restrict__ prob, long long prob_stride, int NC,
+                                                               const float* __restrict__ loc, long long loc_stride,
+                                                               const int32_t* __restrict__ tube_start, const int32_t* __restrict__ tube_count,
+                                                               int kmax, float conf, float thr, float width, float height,
+                                                               uint8_t* __restrict__ keep, float* __restrict__ boxes_out) {
+    __shared__ float ssc[DN_SLOTS];                            // scores, SLOT order
+    __shared__ float rx1[DN_SLOTS], ry1[DN_SLOTS], rx2[DN_SLOTS], ry2[DN_SLOTS], rar[DN_SLOTS];   // boxes and areas, RANK order
+    __shared__ int32_t slot_of[DN_SLOTS];                      // rank -> slot
+    __shared__ unsigned long long masked[DN_WORDS];            // bit (j & 63) of word (j >> 6): slot j has score > conf
+    __shared__ unsigned long long alive[DN_WORDS];             // the same for list position p: not suppressed (yet)
+    const int b = blockIdx.x / NC, c = blockIdx.x % NC;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(tube_count[b], kmax);
+    const long long t0 = tube_start[b];
+    uint8_t* kp = keep + ((size_t)b * NC + c) * kmax;
+    const int swords = (n + 63) >> 6;                          // words of `masked` that hold a slot
+
+    float x1[DN_PER_THREAD], y1[DN_PER_THREAD], x2[DN_PER_THREAD], y2[DN_PER_THREAD], s[DN_PER_THREAD];
+    bool valid[DN_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < DN_PER_THREAD; ++u) {
+        const int j = tid + 256 * u;                           // word (j >> 6) = wave + 4 * u: written by this wave alone
+        x1[u] = 0.f; y1[u] = 0.f; x2[u] = 0.f; y2[u] = 0.f; s[u] = 0.f;
+        valid[u] = false;
+        if (j < n) {
+            const long long tube = t0 + j;
+            const float* bx = loc + tube * loc_stride;
+            x1[u] = fmaxf(0.f, bx[0]); y1[u] = fmaxf(0.f, bx[1]); x2[u] = fminf(width, bx[2]); y2[u] = fminf(height, bx[3]);
+            // (NaN coordinates: see detect_nms_wave_kernel)
+            const bool nan_in = (bx[0] != bx[0]) || (bx[1] != bx[1]) || (bx[2] != bx[2]) || (bx[3] != bx[3]);
+            if (nan_in || !((x1[u] < __fsub_rn(x2[u], 2.f)) && (y1[u] < __fsub_rn(y2[u], 2.f)))) { x1[u] = 0.f; y1[u] = 0.f; x2[u] = width; y2[u] = height; }
+            s[u] = prob[tube * prob_stride + c];
+            valid[u] = s[u] > conf;
+            if (c == 0 && boxes_out) {
+                float* o = boxes_out + tube * 4;
+                o[0] = x1[u]; o[1] = y1[u]; o[2] = x2[u]; o[3] = y2[u];
+            }
+            ssc[j] = s[u];
+        }
+        if (64 * (wave + 4 * u) < n) {                         // wave-uniform
+            const unsigned long long m = __ballot(valid[u]);
+            if (lane == 0) masked[wave + 4 * u] = m;
+        }
+        if (j < kmax && !valid[u]) kp[j] = 0;
+    }
+    __syncthreads();
+
+    int nv = 0;
+    int rank[DN_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < DN_PER_THREAD; ++u) rank[u] = 0;
+    for (int w = 0; w < swords; ++w) {
+        unsigned long long m = masked[w];
+        nv += __builtin_popcountll(m);
+        while (m) {                                            // uniform for the workgroup
+            const int j = 64 * w + __builtin_ctzll(m);
+            m &= m - 1ull;
+            const float sj = ssc[j];
+#pragma unroll
+            for (int u = 0; u < DN_PER_THREAD; ++u) rank[u] += score_before(sj, j, s[u], tid + 256 * u) ? 1 : 0;
+        }
+    }
+    if (nv == 0) return;                                       // nothing masked: the flags are cleared
+#pragma unroll
+    for (int u = 0; u < DN_PER_THREAD; ++u)
+        if (valid[u]) {                                        // ranks of the masked slots are a permutation of 0 .. nv - 1
+            const int r = rank[u];
+            rx1[r] = x1[u]; ry1[r] = y1[u]; rx2[r] = x2[u]; ry2[r] = y2[u];
+            rar[r] = box_area(x1[u], y1[u], x2[u], y2[u]);
+            slot_of[r] = tid + 256 * u;
+        }
+    const int nwords = (nv + 63) >> 6;
+    if (tid < nwords) alive[tid] = (64 * tid + 64 <= nv) ? ~0ull : ((1ull << (nv - 64 * tid)) - 1ull);
+    __syncthreads();
+
+    for (int from = 0; from < nv;) {
+        // the next kept box: the first set bit at or past `from`
+        const int wf = from >> 6;
+        unsigned long long word = (lane >= wf && lane < nwords) ? alive[lane] : 0ull;
+        if (lane == wf) word &= ~0ull << (from & 63);
+        const unsigned long long found = __ballot(word != 0ull);
+        if (!found) break;
+        const int wL = __builtin_ctzll(found);
+        const int L = 64 * wL + __builtin_ctzll(__shfl(word, wL));
+        const float lx1 = rx1[L], ly1 = ry1[L], lx2 = rx2[L], ly2 = ry2[L], larea = rar[L];
+        for (int w = wL + wave; w < nwords; w += 4) {
+            const unsigned long long cur = alive[w];
+            const unsigned long long later = w == wL ? (((L & 63) == 63) ? 0ull : (~0ull << ((L & 63) + 1))) : ~0ull;
+            if ((cur & later) == 0ull) continue;               // wave-uniform
+            const int p = 64 * w + lane;
+            bool sup = ((cur & later) >> lane) & 1ull;
+            if (sup) sup = iou_ge(lx1, ly1, lx2, ly2, larea, rx1[p], ry1[p], rx2[p], ry2[p], rar[p], thr);
+            const unsigned long long m = __ballot(sup);
+            if (m && lane == 0) alive[w] = cur & ~m;
+        }
+        from = L + 1;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int u = 0; u < DN_PER_THREAD; ++u) {
+        const int p = tid + 256 * u;
+        if (p < nv) kp[slot_of[p]] = (uint8_t)((alive[p >> 6] >> (p & 63)) & 1ull);
+    }
 }
 
 // One 256-thread workgroup per group, any n.  scratch: order int32[G*kmax], sup uint8[G*kmax].
@@ -664,11 +785,16 @@ int step_detect_nms(const float* prob, long long prob_stride, int NC, const floa
                     const int32_t* tube_count, int B, int kmax, float conf_thresh, float nms_thresh, float width, float height,
                     uint8_t* keep, float* boxes_out, step_stream_t stream) {
     if (B < 0 || NC < 0 || kmax < 0 || prob_stride < NC || loc_stride < 4) return STEP_E_SHAPE;
-    if (kmax > 64) return STEP_E_UNSUPPORTED;                 // (more tubes per clip: mask + step_nms_batched, as before)
+    if (kmax > STEP_DETECT_TUBES_MAX) return STEP_E_UNSUPPORTED;   // (more tubes per clip: mask + step_nms_batched)
     if (B == 0 || NC == 0 || kmax == 0) return STEP_OK;
     if (!prob || !loc || !tube_start || !tube_count || !keep) return STEP_E_NULL;
-    STEP_LAUNCH((detect_nms_wave_kernel), dim3((unsigned)(B * NC)), dim3(64), stream, prob, prob_stride, NC, loc, loc_stride, tube_start,
-                tube_count, kmax, conf_thresh, nms_thresh, width, height, keep, boxes_out);
+    if (kmax <= 64) {
+        STEP_LAUNCH((detect_nms_wave_kernel), dim3((unsigned)(B * NC)), dim3(64), stream, prob, prob_stride, NC, loc, loc_stride, tube_start,
+                    tube_count, kmax, conf_thresh, nms_thresh, width, height, keep, boxes_out);
+    } else {
+        STEP_LAUNCH((detect_nms_block_kernel), dim3((unsigned)(B * NC)), dim3(256), stream, prob, prob_stride, NC, loc, loc_stride, tube_start,
+                    tube_count, kmax, conf_thresh, nms_thresh, width, height, keep, boxes_out);
+    }
     return STEP_LAUNCH_CHECK();
 }
 

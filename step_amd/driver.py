@@ -24,6 +24,15 @@ from .tube_math import extrapolate_tubes, decode_coef, valid_tubes
 TUBE_KERNEL = True             # per-step tube bookkeeping as one HIP launch (False: the tensor-op restatement below)
 COMPACT_KERNEL = True          # postprocess: the detection rows of all iterations and clips compacted by one HIP launch (False: nonzero / gather / bincount);
                                # postprocess_merged always compacts with the launch: step_detect_merge reads its segments
+DETECT_BLOCK = True            # clips of 65 .. 1024 tubes take the fused path too (step_detect_nms' workgroup form); False: they go through
+                               # _general_rows (tensor operations around step_nms_batched), the routing before that form existed
+DETECT_TUBES_MAX = 1024        # STEP_DETECT_TUBES_MAX
+MERGE_ROWS_MAX = 65536         # step_detect_merge's bitmap: rows per (iteration, clip) segment
+
+
+def _fused_tubes():
+    """the most tubes per clip that the fused evaluation path takes"""
+    return DETECT_TUBES_MAX if DETECT_BLOCK else 64
 
 
 def _flat_tubes(tubes_list, device, dtype=torch.float32):
@@ -144,8 +153,9 @@ _POST_CONST = {}
 
 
 def _detect_keep(nums, NC, dev, members, conf, thr, W, H):
-    """The fused mask + valid_tubes + NMS launch (ops.detect_nms) of every iteration in `members` (one clip layout `nums`, <= 64 tubes per
-    clip) -> keep [I,B,NC,kmax], the clamped boxes and the middle-frame scores per iteration, tube_start [B] int32, [W,H,W,H]."""
+    """The fused mask + valid_tubes + NMS launch (ops.detect_nms) of every iteration in `members` (one clip layout `nums`, <= 1024 tubes
+    per clip: a wavefront per (clip, class) up to 64, a workgroup beyond) -> keep [I,B,NC,kmax], the clamped boxes and the middle-frame
+    scores per iteration, tube_start [B] int32, [W,H,W,H]."""
     B, kmax, I = len(nums), max(nums), len(members)
     # per-layout constants live on the device (a host -> device copy from pageable memory per call stalls the host; the layout of a
     # serving loop never changes)
@@ -196,7 +206,7 @@ def postprocess(args, history, conf_thresh=None, nms_thresh=None, evaluate_topk=
         if len(nums) == 0 or sum(nums) == 0:
             e = torch.zeros(0, device=h["pred_loc"].device)
             out[oi] = [{"boxes": e.view(0, 4), "scores": e, "labels": e.long(), "tubes": e.long()} for _ in nums]
-        elif max(nums) <= 64:
+        elif max(nums) <= _fused_tubes():
             fast.append((oi, h, nums))
         else:
             slow.append((oi, h, nums))
@@ -265,7 +275,8 @@ def _general_rows(h, nums, conf, thr, W, H):
 
 
 def _postprocess_general(h, nums, conf, thr, etopk, topk, W, H):
-    """One iteration with tensor operations + step_nms_batched: more than 64 tubes per clip (anchor modes 3 / 4)."""
+    """One iteration with tensor operations + step_nms_batched: more than 1024 tubes per clip (more than 64 with DETECT_BLOCK = False), and
+    the exact comparison for the fused path."""
     B = len(nums)
     kb, kc, rb, rs, rt = _general_rows(h, nums, conf, thr, W, H)
     per_clip = torch.bincount(kb, minlength=B).tolist()
@@ -284,7 +295,7 @@ def classified_rows(args, prob, flat_tubes, nums, conf_thresh=None):
     middle frame divided by [W,H,W,H], the class, the score.  prob [N,NC] (a cls_only head's output), flat_tubes [N,Tl,5] (frame-index
     column first) or [N,Tl,4], nums = tubes per clip (host ints).  Returns what postprocess() returns for ONE iteration -- a list over clips of
     {boxes [m,4] fp32 normalised, scores [m], labels [m], tubes [m]} -- so detections_csv and evaluate.FrameMAP.add_detections take it
-    unchanged.  One comparison for the keep mask, then the row compaction of postprocess() (step_detect_compact, <= 64 tubes per clip; the
+    unchanged.  One comparison for the keep mask, then the row compaction of postprocess() (step_detect_compact, <= 1024 tubes per clip; the
     nonzero / gather form beyond that) and its one host synchronisation for the row counts."""
     conf = float(getattr(args, "conf_thresh", 0.01) if conf_thresh is None else conf_thresh)
     W, H = float(args.image_size[0]), float(args.image_size[1])
@@ -300,7 +311,7 @@ def classified_rows(args, prob, flat_tubes, nums, conf_thresh=None):
     idx, valid = _clip_groups(nums, dev)
     kmax = idx.shape[1]
     keep = ((scores[idx].permute(0, 2, 1) > conf) & valid.view(B, 1, kmax)).to(torch.uint8).contiguous()     # [B,NC,kmax] (:520)
-    if COMPACT_KERNEL and kmax <= 64:
+    if COMPACT_KERNEL and kmax <= _fused_tubes():
         n = torch.as_tensor(nums, device=dev, dtype=torch.int32)
         start = (torch.cumsum(n, 0) - n).to(torch.int32)
         rb, rs, kc, kj, cnt = ops.detect_compact(keep.view(1, B, NC, kmax), [boxes], [scores], start, W, H)
@@ -366,7 +377,8 @@ def postprocess_merged(args, history, conf_thresh=None, nms_thresh=None, global_
 
     Same launches as postprocess() for the mask, NMS and row compaction; then the list order after top-k for all groups as batched tensor
     operations, ONE step_detect_merge launch per set of iterations that share a clip layout, and ONE host synchronisation behind it (rows,
-    selected rows and clusters per group in one copy) on the <= 64 tubes path; the general path keeps the synchronisation of its nonzero.
+    selected rows and clusters per group in one copy) on the fused path: <= 1024 tubes per clip and NC * kmax <= 65536 rows per segment
+    (step_detect_merge's limit); the general path beyond keeps the synchronisation of its nonzero.
 
     Returns a list over iterations of lists over clips of dicts {boxes [K,4] fp32 normalised merged boxes in cluster order, cluster [m]
     (index into boxes), labels [m], scores [m], tubes [m]}, rows in the order the reference writes them: cluster after cluster, members in
@@ -391,7 +403,7 @@ def postprocess_merged(args, history, conf_thresh=None, nms_thresh=None, global_
     for (nums, NC, dev), members in groups.items():
         B, kmax = len(nums), max(nums)
         cap = NC * kmax
-        if kmax <= 64:
+        if kmax <= 64 or (kmax <= _fused_tubes() and cap <= MERGE_ROWS_MAX):
             for m0 in range(0, len(members), 8):                                                      # (STEP_DETECT_ITERS_MAX iterations per launch)
                 part = members[m0:m0 + 8]
                 keep, bx_all, sc_all, start, _ = _detect_keep(nums, NC, dev, part, conf, thr, W, H)

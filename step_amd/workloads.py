@@ -14,7 +14,7 @@ from .backbone import wgrad_into_grad
 from .optim import FlatAdam, FlatSGD
 from .selection import DeviceClsSelector, DeviceSelector, cls_select, sample_anchors, train_select
 from .driver import _flat_tubes
-from .tube_math import generate_anchors
+from .tube_math import ANCHOR_MODES, anchor_tubes, generate_anchors
 
 
 def step_cfg(**kw):
@@ -47,9 +47,10 @@ def build_nets(dev, seed=123, heads=3, cls_only=False, **cfg):
 
 
 class C3Inference:
-    """B clips [36,3,400,400], `tubes` initial tubes per clip, 3 refinement steps, batched per-class NMS (test.py:140-218)."""
+    """B clips [36,3,400,400], `tubes` initial tubes per clip, 3 refinement steps, batched per-class NMS (test.py:140-218).
+    anchor_mode "1" .. "4": the whole anchor grid of that --anchor_mode instead (34 / 59 / 84 / 109 tubes per clip; `tubes` is not used)."""
 
-    def __init__(self, dev, dtype, batch=4, tubes=11, seed=123, graph=True, share=None):
+    def __init__(self, dev, dtype, batch=4, tubes=11, seed=123, graph=True, share=None, anchor_mode=None):
         # share = another C3Inference: the same networks (weights, packed-weight caches) on other clips -- a second batch in flight
         if share is not None:
             self.args, self.base, self.ctx, self.nets = share.args, share.base, share.ctx, share.nets
@@ -57,8 +58,13 @@ class C3Inference:
             self.args, self.base, self.ctx, self.nets = build_nets(dev, seed)
         g = torch.Generator().manual_seed(seed + (1000 if share is not None else 0))
         self.x = (torch.rand(batch, 36, 3, 400, 400, generator=g) * 2 - 1).to(dev).to(dtype)
-        anchors = generate_anchors()[:tubes] * 400.0
-        self.tubes = [np.tile(anchors[:, None, :], (1, 3, 1)).astype(np.float32) for _ in range(batch)]
+        if anchor_mode is None:
+            anchors = generate_anchors()[:tubes] * 400.0
+            self.tubes = [np.tile(anchors[:, None, :], (1, 3, 1)).astype(np.float32) for _ in range(batch)]
+        else:
+            if str(anchor_mode) not in ANCHOR_MODES:
+                raise ValueError("C3Inference: anchor_mode %r" % (anchor_mode,))
+            self.tubes = [(anchor_tubes(str(anchor_mode), T=3) * 400).astype(np.float32) for _ in range(batch)]
         self.batch = batch
         self.graphed = GraphedInference(self.args, self.base, self.ctx, self.nets, self.x, self.tubes) if graph else None
         if self.graphed is not None:

@@ -13,13 +13,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import step_amd  # noqa: E402,F401
 from step_amd import workloads  # noqa: E402
 from step_amd.driver import GraphedInference, inference, postprocess  # noqa: E402
-from step_amd.tube_math import generate_anchors  # noqa: E402
+from step_amd.tube_math import anchor_tubes, generate_anchors  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--tubes", type=int, default=11)
+    ap.add_argument("--anchor-mode", default=None, choices=("1", "2", "3", "4"),
+                    help="the whole anchor grid of that --anchor_mode (34 / 59 / 84 / 109 tubes per clip) instead of the first --tubes anchors")
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--train", action="store_true")
@@ -28,8 +30,12 @@ def main():
     tdt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[a.dtype]
     args, base, ctx, nets = workloads.build_nets(dev)
     x = (torch.rand(a.batch, 36, 3, 400, 400, device=dev) * 2 - 1).to(tdt)
-    anchors = generate_anchors()[:a.tubes] * 400.0
-    tubes = [np.tile(anchors[:, None, :], (1, 3, 1)).astype(np.float32) for _ in range(a.batch)]
+    if a.anchor_mode is None:
+        anchors = generate_anchors()[:a.tubes] * 400.0
+        tubes = [np.tile(anchors[:, None, :], (1, 3, 1)).astype(np.float32) for _ in range(a.batch)]
+    else:                                                     # as workloads.C3Inference(anchor_mode=...) builds them
+        tubes = [(anchor_tubes(a.anchor_mode, T=3) * 400).astype(np.float32) for _ in range(a.batch)]
+        a.tubes = int(tubes[0].shape[0])
 
     def run():
         with torch.no_grad():
