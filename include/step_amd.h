@@ -287,6 +287,12 @@ STEP_API int step_eval_ap(const long long* cls_start, const uint8_t* label, cons
  *  Weights are pre-packed by step_conv_pack_weight into MFMA fragment order.
  *  scale/shift are fp32 [Cout]: folded eval-mode BN (scale = gamma/sqrt(var+eps),
  *  shift = beta - mean*scale) or (1, bias) or NULL (=> 1, 0).
+ *  Non-finite values: the unit computes what Conv3d + BatchNorm3d + ReLU compute -- inf and NaN inputs propagate through the
+ *  sums, rounding to 16-bit storage overflows to inf (no saturation), and ReLU PROPAGATES a NaN of either sign and sends -0 and
+ *  every negative value to +0 (relu_nan, csrc/common.h; never fmaxf, which would replace a NaN by 0).  Only image pixels and the
+ *  Cin channels of the slice are operands: neighbour channels, zero-weight padding taps and K slots are never multiplied, so an
+ *  inf beside the operands cannot turn into inf x 0 = NaN.  Every fused form (_pre, _pre_pool, _group, _cat, step_pool_conv_forward)
+ *  gives the bits of its separate calls, NaN for NaN.
  */
 typedef struct step_conv_desc {
     int dtype;                 /* STEP_F32 | STEP_BF16 | STEP_F16 (activations and packed weights) */
@@ -558,6 +564,10 @@ STEP_API int step_stem_kernel_name(int dtype, char* buf, int buflen);
  * ceil-mode window overhangs are ignored.
  *  x [N,D,H,W,x_cstride] channels [x_coff, x_coff+C)  ->  y [N,Do,Ho,Wo,y_cstride] at y_coff
  *  Do/Ho/Wo are given by step_pool_out_size(L, k, s).
+ *  Non-finite values, as torch's MaxPool3d: a NaN of EITHER sign in a window is the window's result (max_nan / VecMax, the same rule in
+ *  fp32, bf16, fp16, both kernel forms and the host interpreter build), +inf wins, -inf loses to everything including the zeros of
+ *  the TF pad, and a window that holds nothing but -inf gives -inf.  The backward entry points below walk their windows with
+ *  `val > max`, which skips a NaN (no winner: no gradient); that is theirs alone.
  */
 STEP_API int step_pool_out_size(int L, int k, int s);
 STEP_API int step_maxpool3d_tf(int dtype, const void* x, int N, int D, int H, int W, int C, int x_cstride,

@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ z, 
 #pragma unroll
         for (int e = 0; e < BN_V; ++e) {
             v[e] = v[e] * sc[e] + sh[e];
-            if (relu) v[e] = fmaxf(v[e], 0.f);
+            if (relu) v[e] = relu_nan(v[e]);
         }
         bn_store4<T>(y + (size_t)m * ycs + c, v);
     }

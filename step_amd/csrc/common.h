@@ -91,6 +91,20 @@ template <> struct elem<f16_t> {
     __device__ static __forceinline__ float from_bits16(unsigned short h) { return f16_bits_to_f32(h); }
 };
 
+// ---- the non-finite contract of the forward kernels ("Non-finite contract") ------------------------------
+// ReLU and the max pools PROPAGATE a NaN of either sign, like torch.relu / MaxPool3d (fmaxf and v_max_f32 / v_pk_max_f16
+// return the other operand and would turn a NaN into a plausible number); ReLU sends -0 and every negative value to +0.
+// IEEE-754 2019 maximum: one v_maximum3_f32 on gfx950 -- the instruction count of the v_max_f32 it replaces; the host
+// interpreter compiles the same builtin, so both builds follow ONE rule.
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+// eight post-ReLU values as 16-bit patterns (>= +0, +inf, or a NaN of either sign): as UNSIGNED integers every NaN orders
+// above +inf and +0 stays neutral, so one v_pk_max_u16 per pair is a NaN-propagating max (the pooled epilogues of the
+// stem, step_conv_forward_pre_pool and their seam passes)
+__device__ __forceinline__ u32x4 pk_max_relu16(const u32x4& a, const u32x4& b) {
+    return __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(u16x8, a), __builtin_bit_cast(u16x8, b)));
+}
+
 // ---- 32x32 MFMA "k16 step": D(32x32) += A(32x16) * B(16x32) --------------------------------
 // Operand convention used by every kernel here: lane l holds, for row/col (l & 31), the EIGHT
 // consecutive k values  kbase + 8*(l>>5) + {0..7}  of its operand.

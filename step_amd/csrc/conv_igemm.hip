@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
                     }
                     u16x8 o;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] = elem<T>::bits16(p.relu ? fmaxf(v[e], 0.f) : v[e]);
+                    for (int e = 0; e < 8; ++e) o[e] = elem<T>::bits16(p.relu ? relu_nan(v[e]) : v[e]);
                     if (p.split > 0 && co >= p.split)
                         *(u16x8*)((T*)p.y2 + opix * p.y2_cstride + p.y2_coff + (co - p.split)) = o;
                     else
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvParams p) {
                 if (ok) {
                     float v = acc[i][r] * sc + sh;
                     if (rg) v += elem<T>::to_f32(rg[opix * p.r_cstride + p.r_coff + co]);
-                    if (p.relu) v = fmaxf(v, 0.f);
+                    if (p.relu) v = relu_nan(v);
                     if (p.split > 0 && co >= p.split)
                         ((T*)p.y2)[opix * p.y2_cstride + p.y2_coff + (co - p.split)] = elem<T>::from_f32(v);
                     else
@@ -978,10 +978,6 @@ int step_conv_forward_pre(const step_conv_desc* d, const void* x, const void* w_
 }  // extern "C"
 namespace step {
 struct PoolFixParams { void* y; const void* rowbuf; const void* colbuf; long long planes; int H, W, Hp, Wp, tiles_h, tiles_w, C, y_cstride, y_coff, PT; };
-typedef short s16x8_fix __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ u32x4 pk_max_nonneg16_fix(const u32x4& a, const u32x4& b) {
-    return __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(s16x8_fix, a), __builtin_bit_cast(s16x8_fix, b)));
-}
 __global__ __launch_bounds__(256) void pool_seam_fix_kernel(PoolFixParams p) {
     const int nbr = p.tiles_h - 1, nbc = p.tiles_w - 1, PT = p.PT;
     const int V = p.C / 8;
@@ -1009,18 +1005,18 @@ __global__ __launch_bounds__(256) void pool_seam_fix_kernel(PoolFixParams p) {
             const int t = (ph + 1) / PT;
             for (int dc = 0; dc < 3; ++dc) {
                 const int c = 2 * pw + dc;
-                if (c < p.W) m = pk_max_nonneg16_fix(m, *(const u32x4*)(rb + ((plane * p.tiles_h + t) * p.W + c) * (size_t)p.C + v * 8));
+                if (c < p.W) m = pk_max_relu16(m, *(const u32x4*)(rb + ((plane * p.tiles_h + t) * p.W + c) * (size_t)p.C + v * 8));
             }
             if (pw_seam) {
                 const int s_ = (pw + 1) / PT;
                 for (int dr = 0; dr < 2; ++dr)
-                    m = pk_max_nonneg16_fix(m, *(const u32x4*)(cb + ((plane * p.tiles_w + s_) * p.H + 2 * ph + dr) * (size_t)p.C + v * 8));
+                    m = pk_max_relu16(m, *(const u32x4*)(cb + ((plane * p.tiles_w + s_) * p.H + 2 * ph + dr) * (size_t)p.C + v * 8));
             }
         } else {
             const int s_ = (pw + 1) / PT;
             for (int dr = 0; dr < 3; ++dr) {
                 const int r = 2 * ph + dr;
-                if (r < p.H) m = pk_max_nonneg16_fix(m, *(const u32x4*)(cb + ((plane * p.tiles_w + s_) * p.H + r) * (size_t)p.C + v * 8));
+                if (r < p.H) m = pk_max_relu16(m, *(const u32x4*)(cb + ((plane * p.tiles_w + s_) * p.H + r) * (size_t)p.C + v * 8));
             }
         }
         *(u32x4*)yp = m;

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void pw_splitk_finish_kernel(ConvParams p, con
             v = ((part[0][e] + part[1][e]) + (part[2][e] + part[3][e])) + ((part[4][e] + part[5][e]) + (part[6][e] + part[7][e]));
             v = v * (p.scale ? p.scale[co] : 1.f) + (p.shift ? p.shift[co] : 0.f);
             if (p.res) v += elem<T>::to_f32(((const T*)p.res)[(size_t)row * p.r_cstride + p.r_coff + co]);
-            if (p.relu) v = fmaxf(v, 0.f);
+            if (p.relu) v = relu_nan(v);
             if (p.split > 0 && co >= p.split) ((T*)p.y2)[(size_t)row * p.y2_cstride + p.y2_coff + (co - p.split)] = elem<T>::from_f32(v);
             else ((T*)p.y)[(size_t)row * p.y_cstride + p.y_coff + co] = elem<T>::from_f32(v);
         }
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(WV * 64) void conv_pws_kernel(ConvParams p, int NBW
                     for (int e = 0; e < 4; ++e) {
                         v[e] = acc[i][4 * q + e] * s4[e] + h4[e];
                         if constexpr (RES) v[e] += elem<T>::from_bits16((unsigned short)(rq[q][e >> 1] >> (16 * (e & 1))));
-                        if (p.relu) v[e] = fmaxf(v[e], 0.f);
+                        if (p.relu) v[e] = relu_nan(v[e]);
                     }
                     d[q][0] = (unsigned)elem<T>::bits16(v[0]) | ((unsigned)elem<T>::bits16(v[1]) << 16);
                     d[q][1] = (unsigned)elem<T>::bits16(v[2]) | ((unsigned)elem<T>::bits16(v[3]) << 16);

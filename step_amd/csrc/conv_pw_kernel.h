@@ -321,7 +321,7 @@ __device__ __forceinline__ void conv_pw_body(const ConvParams& p, unsigned char*
                     }
                     u16x8 o;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] = elem<T>::bits16(p.relu ? fmaxf(v[e], 0.f) : v[e]);
+                    for (int e = 0; e < 8; ++e) o[e] = elem<T>::bits16(p.relu ? relu_nan(v[e]) : v[e]);
                     if (p.split > 0 && co >= p.split)
                         *(u16x8*)((T*)p.y2 + opix * p.y2_cstride + p.y2_coff + (co - p.split)) = o;
                     else
@@ -347,7 +347,7 @@ __device__ __forceinline__ void conv_pw_body(const ConvParams& p, unsigned char*
                         const size_t opix = (size_t)gm;
                         float v = acc[mb][i][r] * sc + sh;
                         if (rg) v += elem<T>::to_f32(rg[opix * p.r_cstride + p.r_coff + co]);
-                        if (p.relu) v = fmaxf(v, 0.f);
+                        if (p.relu) v = relu_nan(v);
                         if (p.split > 0 && co >= p.split)
                             ((T*)p.y2)[opix * p.y2_cstride + p.y2_coff + (co - p.split)] = elem<T>::from_f32(v);
                         else

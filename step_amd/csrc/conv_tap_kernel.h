@@ -51,7 +51,6 @@ namespace step {
 // weights of the slab's 32 channels (4 K-steps), and stores affine + ReLU + 16-bit rounding of the result into the halo slab --
 // exactly the values the separate layer would have written to memory (same K order, same rounding), zeros outside the image.
 // The intermediate tensor never exists: -2 x 51 MB of traffic and one launch per C2 step for +3 % matrix work in this kernel.
-typedef short s16x8_pool __attribute__((ext_vector_type(8)));
 #define NTAPS_EVEN_STEPS(KD, KH, KW, TPS) (((taps_padded((KD) * (KH) * (KW)) / (TPS)) & 1) == 0)
 
 // PERSIST (round 6; two-phase form, one channel group: p.gy == 1): the workgroup is a PERSISTENT tile loop -- the grid is p.gpersist workgroups
@@ -411,7 +410,7 @@ __device__ __forceinline__ void conv_tap_body(const ConvParams& p, unsigned char
                     for (int g = 0; g < 4; ++g) {
                         float v[4];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) { v[e] = fmaxf(a[4 * g + e] * sc[g][e] + sh[g][e], 0.f); v[e] = inb ? v[e] : 0.f; }
+                        for (int e = 0; e < 4; ++e) { v[e] = relu_nan(a[4 * g + e] * sc[g][e] + sh[g][e]); v[e] = inb ? v[e] : 0.f; }
                         d[g][0] = (unsigned)elem<T>::bits16(v[0]) | ((unsigned)elem<T>::bits16(v[1]) << 16);
                         d[g][1] = (unsigned)elem<T>::bits16(v[2]) | ((unsigned)elem<T>::bits16(v[3]) << 16);
                     }
@@ -460,7 +459,8 @@ __device__ __forceinline__ void conv_tap_body(const ConvParams& p, unsigned char
             // 4 pooled rows / columns and two of the three rows / columns of the fourth.  The tile writes the max over what it HAS to y and
             // its own first row and first column (raw values) to pool_row / pool_col; pool_seam_fix_kernel completes the pooled pixels on tile
             // seams from those.  Values are post-ReLU (>= +0): the zero padding of the reference's ConstantPad3d is neutral, out-of-image
-            // pixels of partial tiles enter as 0, and 16-bit patterns order like signed integers (one v_pk_max_i16 per pair).
+            // pixels of partial tiles enter as 0, and 16-bit patterns order like UNSIGNED integers with every NaN above +inf (pk_max_relu16: one
+            // v_pk_max_u16 per pair; a NaN of either sign comes out as NaN).
             constexpr int TP = NBT * 64 + 16;                            // bytes per tile pixel (+16: 16 lanes x 16 B at one channel offset spread over all banks)
             int tpix[MB];
 #pragma unroll
@@ -486,7 +486,7 @@ __device__ __forceinline__ void conv_tap_body(const ConvParams& p, unsigned char
                     for (int g = 0; g < 4; ++g) {
                         float v[4];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[mb][i][4 * g + e] * sc[g][e] + sh[g][e], 0.f);      // (the host admits relu = 1 only)
+                        for (int e = 0; e < 4; ++e) v[e] = relu_nan(acc[mb][i][4 * g + e] * sc[g][e] + sh[g][e]);      // (the host admits relu = 1 only)
                         d[g][0] = (unsigned)elem<T>::bits16(v[0]) | ((unsigned)elem<T>::bits16(v[1]) << 16);
                         d[g][1] = (unsigned)elem<T>::bits16(v[2]) | ((unsigned)elem<T>::bits16(v[3]) << 16);
                     }
@@ -521,7 +521,7 @@ __device__ __forceinline__ void conv_tap_body(const ConvParams& p, unsigned char
                         if (dr == 0 && dc == 0) continue;
                         if (2 * i2 + dr < 8 && 2 * j + dc < 8) {
                             const u32x4 o = *(const u32x4*)(base + (dr * 8 + dc) * TP);
-                            m = __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(s16x8_pool, m), __builtin_bit_cast(s16x8_pool, o)));
+                            m = pk_max_relu16(m, o);
                         }
                     }
                 const int od = d0 + pl_, ph = (h0 >> 1) + i2, pw = (w0 >> 1) + j, co = nb0 * 32 + v * 8;
@@ -585,7 +585,7 @@ __device__ __forceinline__ void conv_tap_body(const ConvParams& p, unsigned char
                         }
                         if (p.relu) {
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                            for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
                         }
                         d[g][0] = (unsigned)elem<T>::bits16(v[0]) | ((unsigned)elem<T>::bits16(v[1]) << 16);
                         d[g][1] = (unsigned)elem<T>::bits16(v[2]) | ((unsigned)elem<T>::bits16(v[3]) << 16);
@@ -623,7 +623,7 @@ __device__ __forceinline__ void conv_tap_body(const ConvParams& p, unsigned char
                         const size_t o = (size_t)opix[mb];
                         float v = acc[mb][i][r] * ldsS[cl + cd_row(r, lane)] + ldsS[NBT * 32 + cl + cd_row(r, lane)];
                         if (rg) v += elem<T>::to_f32(rg[o * p.r_cstride + p.r_coff + co]);
-                        if (p.relu) v = fmaxf(v, 0.f);
+                        if (p.relu) v = relu_nan(v);
                         yg[o * p.y_cstride + p.y_coff + co] = elem<T>::from_f32(v);
                     }
                 }
@@ -650,7 +650,7 @@ __device__ __forceinline__ void conv_tap_body(const ConvParams& p, unsigned char
                         const size_t opix = (((size_t)n * p.D + od) * p.H + oh) * p.W + ow;
                         float v = acc[mb][i][r] * sc + sh;
                         if (rg) v += elem<T>::to_f32(rg[opix * p.r_cstride + p.r_coff + co]);
-                        if (p.relu) v = fmaxf(v, 0.f);
+                        if (p.relu) v = relu_nan(v);
                         yg[opix * p.y_cstride + p.y_coff + co] = elem<T>::from_f32(v);
                     }
                 }
@@ -1027,9 +1027,11 @@ __device__ __forceinline__ void conv_tap_body(const ConvParams& p, unsigned char
             if (s_ + 1 < S && !new_slab)
                 read_frags(std::integral_constant<int, SET ^ 1>(), b1, nshift);
         }
-        mma_all(setc);
+        // the zero tap that pads an odd tap count (last slot of a slab) is NOT multiplied: its fragments are the shift-0 pixels, and
+        // inf x 0 = NaN would turn the +-inf those pixels rightly give their tap-0 neighbours into NaN (the two-phase form skips it too)
+        if (!(LAST && TPS > 1 && NTP != NTAPS && new_slab)) mma_all(setc);
         if (LAST) {
-            store_B(b2, R);                                // (past the end: a duplicate tile into a buffer nobody reads)
+            store_B(b2, R);                               // (past the end: a duplicate tile into a buffer nobody reads)
             load_B(woff3, R);
             adv_clamped();
             if (s_ + 1 < S && new_slab) {

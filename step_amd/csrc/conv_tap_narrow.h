@@ -282,7 +282,7 @@ __device__ __forceinline__ void conv_tap_narrow_body(const ConvParams& p, unsign
                     for (int e = 0; e < 4; ++e) v[e] = acc[mb][i][4 * g + e] * sc[g][e] + sh[g][e];
                     if (p.relu) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                        for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
                     }
                     d[g][0] = (unsigned)elem<T>::bits16(v[0]) | ((unsigned)elem<T>::bits16(v[1]) << 16);
                     d[g][1] = (unsigned)elem<T>::bits16(v[2]) | ((unsigned)elem<T>::bits16(v[3]) << 16);
@@ -313,7 +313,7 @@ __device__ __forceinline__ void conv_tap_narrow_body(const ConvParams& p, unsign
                 if (opix[mb] >= 0 && co < p.Cout) {
                     const size_t o = (size_t)opix[mb];
                     float v = acc[mb][i][r] * ldsS[co] + ldsS[NBn * 32 + co];
-                    if (p.relu) v = fmaxf(v, 0.f);
+                    if (p.relu) v = relu_nan(v);
                     yg[o * p.y_cstride + p.y_coff + co] = elem<T>::from_f32(v);
                 }
             }

@@ -102,7 +102,8 @@ __global__ __launch_bounds__(256) void head_outputs_kernel(HeadParams p) {
         if (train) {
             const float* ct = p.targets + (size_t)n * p.tstride + (p.tstride / 3);
             const float t = ct[6 + c] * ct[4];
-            p.loss_cls[i] = pos * (fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x))));
+            // (a masked target drops the product instead of multiplying by 0: +inf under a 0 target is a loss of +inf, as torch's (1 - t) * x, not inf * 0 = NaN)
+            p.loss_cls[i] = pos * (relu_nan(x) - (t != 0.f ? x * t : 0.f) + log1pf(expf(-fabsf(x))));
         }
     }
     if (p.reg) {

@@ -48,7 +48,7 @@ __global__ void maxpool3d_tf_kernel(const T* __restrict__ x, T* __restrict__ y, 
         const int n = (int)(pix / p.Do);
         float m[V];
 #pragma unroll
-        for (int i = 0; i < V; ++i) m[i] = -FLT_MAX;
+        for (int i = 0; i < V; ++i) m[i] = -__builtin_inff();              // (a window of -inf alone gives -inf, as in torch)
         for (int a = 0; a < p.kd; ++a) {
             const int pd = od * p.sd + a;
             if (pd >= p.Lpd) break;                 // ceil-mode overhang: ignored
@@ -67,10 +67,10 @@ __global__ void maxpool3d_tf_kernel(const T* __restrict__ x, T* __restrict__ y, 
                         float f[V];
                         Vec16<T, V>::unpack(*(const raw*)src, f);
 #pragma unroll
-                        for (int i = 0; i < V; ++i) m[i] = fmaxf(m[i], f[i]);
+                        for (int i = 0; i < V; ++i) m[i] = max_nan(m[i], f[i]);
                     } else {                          // explicit TF zero padding: value 0
 #pragma unroll
-                        for (int i = 0; i < V; ++i) m[i] = fmaxf(m[i], 0.f);
+                        for (int i = 0; i < V; ++i) m[i] = max_nan(m[i], 0.f);
                     }
                 }
             }

@@ -29,16 +29,18 @@ template <> struct Vec16<f16_t, 8> : Vec16h<f16_t> {};
 
 // element-wise max of two 16-byte channel vectors in the storage type (the max of two representable
 // values is representable: no rounding anywhere in a max pool).  enc / dec map a vector to and from the
-// form the max is taken in.
+// form the max is taken in.  The max PROPAGATES a NaN of either sign (the non-finite contract of common.h),
+// by the same rule in all three storage types and in the host interpreter.  (Forward pools only: the
+// backward kernels walk their windows with `val > max`, which skips a NaN, and share nothing with this.)
 template <typename T> struct VecMax;
 template <> struct VecMax<float> {
     __device__ static __forceinline__ f32x4 enc(const f32x4& a) { return a; }
     __device__ static __forceinline__ f32x4 dec(const f32x4& a) { return a; }
     __device__ static __forceinline__ f32x4 lowest() { const float m = -__builtin_inff(); f32x4 r = {m, m, m, m}; return r; }
-    __device__ static __forceinline__ f32x4 max(const f32x4& a, const f32x4& b) {
+    __device__ static __forceinline__ f32x4 max(const f32x4& a, const f32x4& b) {          // v_maximum3_f32
         f32x4 r;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = fmaxf(a[i], b[i]);
+        for (int i = 0; i < 4; ++i) r[i] = max_nan(a[i], b[i]);
         return r;
     }
 };
@@ -47,23 +49,27 @@ template <> struct VecMax<f16_t> {
     __device__ static __forceinline__ u16x8 enc(const u16x8& a) { return a; }
     __device__ static __forceinline__ u16x8 dec(const u16x8& a) { return a; }
     __device__ static __forceinline__ u16x8 lowest() { u16x8 r; for (int i = 0; i < 8; ++i) r[i] = 0xfc00; return r; }   // -inf
-    __device__ static __forceinline__ u16x8 max(const u16x8& a, const u16x8& b) {          // v_pk_max_f16
-        return __builtin_bit_cast(u16x8, __builtin_elementwise_max(__builtin_bit_cast(f16x8_hw, a), __builtin_bit_cast(f16x8_hw, b)));
+    __device__ static __forceinline__ u16x8 max(const u16x8& a, const u16x8& b) {          // v_pk_maximum3_f16 (v_pk_max_f16 drops a NaN)
+        return __builtin_bit_cast(u16x8, __builtin_elementwise_maximum(__builtin_bit_cast(f16x8_hw, a), __builtin_bit_cast(f16x8_hw, b)));
     }
 };
 template <> struct VecMax<bf16_t> {
     // gfx950 has no packed bf16 max, and widening to fp32 costs ~9 VALU ops per pair (measured: the pool was
-    // VALU-bound).  A sign-magnitude float orders like the two's-complement integer  x ^ ((x >> 15) & 0x7fff)
-    // (negative values get their magnitude bits flipped), so planes are re-keyed once when they enter LDS (3 ops
-    // per pair), every max is one v_pk_max_i16 per pair, and the same map brings the result back before the
-    // store.  0 keeps the key 0; -0 < +0; NaN orders beyond +-inf, so a positive NaN propagates.
+    // VALU-bound), so planes are re-keyed once when they enter LDS, every max is one v_pk_max_i16 per pair, and
+    // the same map -- an involution -- brings the result back before the store.  The key of a pattern x, as a
+    // two's-complement integer:  x for x >= +0,  0x7f80 - x (mod 2^16) for the negative ones: -0 -> -128, larger
+    // magnitudes below it, -inf -> -32768 (no key is lower), and the negative NaNs 0xff81 .. 0xffff -> 0x7fff ..
+    // 0x7f81, ABOVE +inf where the positive NaNs are: a NaN of either sign wins every max and comes back as a NaN.
+    // Per pair of elements: m = x >> 15 (arithmetic), key = (x ^ m) + (m & 0x7f81) -- v_pk_ashrrev_i16, v_and_b32 and
+    // ONE 32-bit v_xad_u32, because the sum never carries out of a 16-bit half (~x <= 0x7fff for a negative x).
     typedef short s16x8 __attribute__((ext_vector_type(8)));
     __device__ static __forceinline__ u16x8 enc(const u16x8& a) {
-        const s16x8 sa = __builtin_bit_cast(s16x8, a);
-        return __builtin_bit_cast(u16x8, sa ^ ((sa >> 15) & (short)0x7fff));
+        const u32x4 x = __builtin_bit_cast(u32x4, a);
+        const u32x4 m = __builtin_bit_cast(u32x4, __builtin_bit_cast(s16x8, a) >> 15);
+        return __builtin_bit_cast(u16x8, (x ^ m) + (m & 0x7f817f81u));
     }
     __device__ static __forceinline__ u16x8 dec(const u16x8& k) { return enc(k); }
-    __device__ static __forceinline__ u16x8 lowest() { u16x8 r; for (int i = 0; i < 8; ++i) r[i] = 0x8000; return r; }   // below every key
+    __device__ static __forceinline__ u16x8 lowest() { u16x8 r; for (int i = 0; i < 8; ++i) r[i] = 0x8000; return r; }   // the key of -inf: no key is lower
     __device__ static __forceinline__ u16x8 max(const u16x8& a, const u16x8& b) {
         return __builtin_bit_cast(u16x8, __builtin_elementwise_max(__builtin_bit_cast(s16x8, a), __builtin_bit_cast(s16x8, b)));
     }
@@ -80,7 +86,7 @@ template <typename T> struct VecMax {
     __device__ static inline u16x8 max(const u16x8& a, const u16x8& b) {
         float fa[8], fb[8];
         Vec16<T, 8>::unpack(a, fa); Vec16<T, 8>::unpack(b, fb);
-        for (int i = 0; i < 8; ++i) fa[i] = fmaxf(fa[i], fb[i]);
+        for (int i = 0; i < 8; ++i) fa[i] = max_nan(fa[i], fb[i]);
         return Vec16<T, 8>::pack(fa);
     }
 };

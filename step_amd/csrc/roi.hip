@@ -261,19 +261,32 @@ __global__ void roi_align_bwd_nchw_kernel(const float* __restrict__ grad, const 
 // sample row, bin column, sample column), every sample whose bilinear footprint touches it -- the same products gtop * w / count as
 // the scatter form above, no atomics, so the gradient is bit-reproducible run to run.  The footprint is separable: a sample row y
 // touches pixel row Y with weight hy (y_low == Y) and / or ly (y_high == Y) of bilinear_tap; likewise for columns.
+// A term whose bilinear weight is exactly 0 (a sample on an integer coordinate: its high neighbour; a sample clamped to the last row /
+// column: the second term of the same cell) is still a TERM of the reference's scatter -- gtop * 0 is 0 for a finite gradient and NaN
+// for a non-finite one -- so the gather keeps it.  axis_weight returns RBG_VOID when the sample has no term for row / column P, else the
+// sum of its terms' weights (0 .. 1), NEGATED (-0 included) when one of the terms has weight 0; axis_terms() takes the two axes apart.
+constexpr float RBG_VOID = 2.f;
 __device__ __forceinline__ float axis_weight(int size, float v, int P) {
-    if (v < -1.0f || v > (float)size) return 0.f;          // void sample (bilinear_tap's first test, per axis)
+    if (v < -1.0f || v > (float)size) return RBG_VOID;     // void sample (bilinear_tap's first test, per axis)
     if (v <= 0) v = 0;
     int lo = (int)v, hi;
     if (lo >= size - 1) { hi = lo = size - 1; v = (float)lo; } else { hi = lo + 1; }
+    if (lo != P && hi != P) return RBG_VOID;
     const float l = v - (float)lo, h = 1.f - l;
-    return (lo == P ? h : 0.f) + (hi == P && hi != lo ? l : 0.f);
+    const float w = (lo == P ? h : 0.f) + (hi == P ? l : 0.f);
+    return ((lo == P && h == 0.f) || (hi == P && l == 0.f)) ? -w : w;
+}
+__device__ __forceinline__ bool axis_void(float w) { return w > 1.5f; }
+// the weight of a (row, column) pair of terms and whether the reference multiplies the gradient by a zero weight there as well
+__device__ __forceinline__ float axis_terms(float wy, float wx, bool& zero_term) {
+    zero_term = ((__builtin_bit_cast(unsigned, wy) | __builtin_bit_cast(unsigned, wx)) >> 31) != 0;
+    return fabsf(wy) * fabsf(wx);
 }
 
 // One workgroup per feature cell, lanes along channels.  The bilinear weights of a roi depend on the cell only, not on the channel:
 // the first lanes compute the roi's row weights wy[bin row x sample row] and column weights wx[...] ONCE into LDS (every branch
 // here is workgroup-uniform -- it depends on blockIdx and the roi list only -- so the barriers inside the roi loop are legal), then
-// every lane walks the non-zero pairs.  (Each lane evaluating the weights itself: 205 us per call in the C4 step, VALU-bound.)
+// every lane walks the pairs of terms.  (Each lane evaluating the weights itself: 205 us per call in the C4 step, VALU-bound.)
 constexpr int RBG_MAXS = 128;                       // samples per axis the LDS tables hold (pooled size x sampling grid); larger: per-lane path
 constexpr int RBG_RB = 8;                           // rois per round of the listed walk: their weight tables are built together (two barriers per round, not per roi)
 constexpr int RBG_LIST = 512;                       // rois per cell the LDS candidate list holds; a cell that more rois touch walks all K headers
@@ -292,7 +305,7 @@ template <int V>
 __global__ void roi_align_bwd_gather_nhwc_kernel(const float* __restrict__ grad, const float* __restrict__ rois, int K, int C, int H, int W,
                                                  int ph, int pw, float scale, int sampling_ratio, float* __restrict__ gfeat) {
     __shared__ float wy_s[RBG_RB][RBG_MAXS], wx_s[RBG_RB][RBG_MAXS];
-    __shared__ int rng_s[RBG_RB][4];                  // per roi of the round: first / last sample row, first / last sample column with a non-zero weight
+    __shared__ int rng_s[RBG_RB][4];                  // per roi of the round: first / last sample row, first / last sample column with a term for this cell
     __shared__ int list_s[RBG_LIST];
     __shared__ float box_s[RBG_LIST][5];              // the listed rois' rows: the rounds below read their geometry from LDS, not through a chain of global loads
     __shared__ int nlist_s;
@@ -355,12 +368,12 @@ __global__ void roi_align_bwd_gather_nhwc_kernel(const float* __restrict__ grad,
                 if (i < SY) {
                     const float w = axis_weight(H, sample_y(g, i / g.grid_h, i % g.grid_h), Y);
                     wy_s[r][i] = w;
-                    if (w != 0.f) { atomicMin(&rng_s[r][0], i); atomicMax(&rng_s[r][1], i); }
+                    if (!axis_void(w)) { atomicMin(&rng_s[r][0], i); atomicMax(&rng_s[r][1], i); }
                 } else {
                     const int j = i - SY;
                     const float w = axis_weight(W, sample_x(g, j / g.grid_w, j % g.grid_w), X);
                     wx_s[r][j] = w;
-                    if (w != 0.f) { atomicMin(&rng_s[r][2], j); atomicMax(&rng_s[r][3], j); }
+                    if (!axis_void(w)) { atomicMin(&rng_s[r][2], j); atomicMax(&rng_s[r][3], j); }
                 }
             }
         }
@@ -375,12 +388,13 @@ __global__ void roi_align_bwd_gather_nhwc_kernel(const float* __restrict__ grad,
             for (int sy = y0; sy <= y1; ++sy) {
                 const int p = sy / g.grid_h;
                 const float wy = tables ? wy_s[r][sy] : axis_weight(H, sample_y(g, p, sy % g.grid_h), Y);
-                if (wy == 0.f) continue;
+                if (axis_void(wy)) continue;
                 for (int sx = x0; sx <= x1; ++sx) {
                     const int q = sx / g.grid_w;
                     const float wx = tables ? wx_s[r][sx] : axis_weight(W, sample_x(g, q, sx % g.grid_w), X);
-                    if (wx == 0.f) continue;
-                    const float w = wy * wx;
+                    if (axis_void(wx)) continue;
+                    bool zt;
+                    const float w = axis_terms(wy, wx, zt);
 #pragma unroll
                     for (int k = 0; k < MAXCV; ++k) {
                         const int c = cbase + (tid + k * nthr) * V;
@@ -388,7 +402,7 @@ __global__ void roi_align_bwd_gather_nhwc_kernel(const float* __restrict__ grad,
                             float gt[V];
                             VecIO<float, V>::load(grad + ((size_t)(n * ph + p) * pw + q) * C + c, gt);
 #pragma unroll
-                            for (int i = 0; i < V; ++i) acc[k][i] += gt[i] * w / g.count;
+                            for (int i = 0; i < V; ++i) { acc[k][i] += gt[i] * w / g.count; if (zt) acc[k][i] += gt[i] * 0.f; }
                         }
                     }
                 }
@@ -414,13 +428,14 @@ __global__ void roi_align_bwd_gather_nhwc_kernel(const float* __restrict__ grad,
         for (int p = 0; p < ph; ++p)
             for (int iy = 0; iy < g.grid_h; ++iy) {
                 const float wy = tables ? wy_s[0][p * g.grid_h + iy] : axis_weight(H, sample_y(g, p, iy), Y);
-                if (wy == 0.f) continue;
-                // (a sample whose OTHER coordinate is void contributes nothing: its column weight below is 0)
+                if (axis_void(wy)) continue;
+                // (a sample whose OTHER coordinate is void contributes nothing: its column weight below is RBG_VOID)
                 for (int q = 0; q < pw; ++q)
                     for (int ix = 0; ix < g.grid_w; ++ix) {
                         const float wx = tables ? wx_s[0][q * g.grid_w + ix] : axis_weight(W, sample_x(g, q, ix), X);
-                        if (wx == 0.f) continue;
-                        const float w = wy * wx;
+                        if (axis_void(wx)) continue;
+                        bool zt;
+                    const float w = axis_terms(wy, wx, zt);
 #pragma unroll
                         for (int k = 0; k < MAXCV; ++k) {
                             const int c = cbase + (tid + k * nthr) * V;
@@ -428,7 +443,7 @@ __global__ void roi_align_bwd_gather_nhwc_kernel(const float* __restrict__ grad,
                                 float gt[V];
                                 VecIO<float, V>::load(grad + ((size_t)(n * ph + p) * pw + q) * C + c, gt);
 #pragma unroll
-                                for (int i = 0; i < V; ++i) acc[k][i] += gt[i] * w / g.count;
+                                for (int i = 0; i < V; ++i) { acc[k][i] += gt[i] * w / g.count; if (zt) acc[k][i] += gt[i] * 0.f; }
                             }
                         }
                     }
@@ -458,12 +473,15 @@ __global__ void roi_align_bwd_gather_nchw_kernel(const float* __restrict__ grad,
             for (int p = 0; p < ph; ++p)
                 for (int iy = 0; iy < g.grid_h; ++iy) {
                     const float wy = axis_weight(H, sample_y(g, p, iy), Y);
-                    if (wy == 0.f) continue;
+                    if (axis_void(wy)) continue;
                     for (int q = 0; q < pw; ++q)
                         for (int ix = 0; ix < g.grid_w; ++ix) {
                             const float wx = axis_weight(W, sample_x(g, q, ix), X);
-                            if (wx == 0.f) continue;
-                            acc += gr[p * pw + q] * (wy * wx) / g.count;
+                            if (axis_void(wx)) continue;
+                            bool zt;
+                            const float w = axis_terms(wy, wx, zt);
+                            acc += gr[p * pw + q] * w / g.count;
+                            if (zt) acc += gr[p * pw + q] * 0.f;
                         }
                 }
         }

@@ -124,6 +124,10 @@ __global__ __launch_bounds__(256) void stem_igemm_kernel(StemParams p) {
                     for (int q = 0; q < ES / 2; ++q) h2[q] = *(const u32x4*)(ap + 16 * q);
                     __builtin_memcpy(&a, h2, sizeof(a));
                 }
+                if (j == 1 && khalf) {                   // the 8th tap (zero weight) is the pixel after the window: cleared, inf x 0 = NaN is no part of this output
+#pragma unroll
+                    for (int e = 4; e < 8; ++e) a[e] = 0;
+                }
                 const int ks = (kd * 7 + kh) * 2 + j;
 #pragma unroll
                 for (int i = 0; i < NB; ++i) {
@@ -150,7 +154,7 @@ __global__ __launch_bounds__(256) void stem_igemm_kernel(StemParams p) {
                 const int oh = oh0 + (mm >> 4), ow = ow0 + (mm & 15);
                 if (oh < p.Ho && ow < p.Wo) {
                     float v = acc[i][r] * sc + sh;
-                    if (p.relu) v = fmaxf(v, 0.f);
+                    if (p.relu) v = relu_nan(v);
                     const size_t opix = (((size_t)n * p.To + od) * p.Ho + oh) * p.Wo + ow;
                     yg[opix * p.y_cstride + p.y_coff + co] = elem<T>::from_f32(v);
                 }
@@ -201,12 +205,9 @@ __device__ __forceinline__ u16x8 lds_read_frag_a4(const unsigned char* p) {
 // holds everything for 7 of its 8 pooled rows / columns and two of the three rows / columns of the eighth.  The tile writes the max
 // over what it HAS to y and its own first row and first column (raw values) to rowbuf / colbuf; stem_pool_fix_kernel then completes
 // the pooled pixels on tile seams from those.  Values are post-ReLU (>= +0), so the zero padding of the reference's ConstantPad3d is
-// neutral, out-of-image pixels of partial tiles enter as 0, and 16-bit patterns order like signed integers (one v_pk_max_i16 per pair).
+// neutral, out-of-image pixels of partial tiles enter as 0, and 16-bit patterns order like UNSIGNED integers with every NaN above +inf
+// (pk_max_relu16, common.h: one v_pk_max_u16 per pair; a NaN of either sign comes out as NaN).
 constexpr int STS_TPITCH = 144;                     // bytes per pixel of the epilogue's LDS tile: 64 channels x 2 B + 16 B (16 lanes x 16 B at one channel offset spread over all banks)
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ u32x4 pk_max_nonneg16(const u32x4& a, const u32x4& b) {
-    return __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(s16x8_t, a), __builtin_bit_cast(s16x8_t, b)));
-}
 
 template <typename T, int NB_ = 2, bool VEC = true, bool POOL = false, bool U8 = false>
 __global__ __launch_bounds__(256) STEP_WAVES_PER_SIMD(3) void stem_stream_kernel(StemParams p) {
@@ -404,7 +405,14 @@ __global__ __launch_bounds__(256) STEP_WAVES_PER_SIMD(3) void stem_stream_kernel
         constexpr int J = decltype(jc)::value;
         const int aoff = slotoff + (J < 9 ? (2 * (J / 3)) * PITCH + (J % 3) * 16 + kh_row : (J == 9 ? 6 * PITCH + kh_q : 6 * PITCH + 32));
 #pragma unroll
-        for (int mb = 0; mb < 2; ++mb) fa[SET][mb] = lds_read_frag_a4(abase[mb] + aoff);
+        for (int mb = 0; mb < 2; ++mb) {
+            frag_t f = lds_read_frag_a4(abase[mb] + aoff);
+            // K slots whose weights are zero are cleared on the pixel side too: they hold the pixel AFTER the window (q = 2: the last 3
+            // elements) or a second copy of the row (J = 10, upper half), and inf x 0 = NaN would reach an output the value is no part of
+            if constexpr ((J < 9 && J % 3 == 2) || J == 10) { f[5] = 0; f[6] = 0; f[7] = 0; }
+            if constexpr (J == 10) { const frag_t z = {0, 0, 0, 0, 0, 0, 0, 0}; f = khalf ? z : f; }
+            fa[SET][mb] = f;
+        }
 #pragma unroll
         for (int i = 0; i < NB; ++i) fb[SET][i] = *(const frag_t*)(bwave + (J / 4) * BBUF + i * NBREG + (J % 4) * FRAGB);
     };
@@ -543,7 +551,7 @@ __global__ __launch_bounds__(256) STEP_WAVES_PER_SIMD(3) void stem_stream_kernel
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     v[e] = acc[mb][i][4 * g + e] * sc[e] + sh[e];
-                    if (p.relu) v[e] = fmaxf(v[e], 0.f);
+                    if (p.relu) v[e] = relu_nan(v[e]);
                 }
                 if (!vec_epi && !POOL) {                      // channel counts / offsets off the 16-byte grid: element stores
 #pragma unroll
@@ -595,7 +603,7 @@ __global__ __launch_bounds__(256) STEP_WAVES_PER_SIMD(3) void stem_stream_kernel
 #pragma unroll
                 for (int dc = 0; dc < 3; ++dc) {
                     if (dr == 0 && dc == 0) continue;
-                    if (2 * j + dr < 16 && 2 * q + dc < 16) m = pk_max_nonneg16(m, *(const u32x4*)(base + (dr * 16 + dc) * STS_TPITCH));
+                    if (2 * j + dr < 16 && 2 * q + dc < 16) m = pk_max_relu16(m, *(const u32x4*)(base + (dr * 16 + dc) * STS_TPITCH));
                 }
             const int ph = (oh0 >> 1) + j, pw = (ow0 >> 1) + q;
             if (ph < p.Hp && pw < p.Wp)
@@ -654,18 +662,18 @@ __global__ __launch_bounds__(256) void stem_pool_fix_kernel(StemParams p) {
             const int t = (ph + 1) >> 3;
             for (int dc = 0; dc < 3; ++dc) {
                 const int c = 2 * pw + dc;
-                if (c < p.Wo) m = pk_max_nonneg16(m, *(const u32x4*)(rb + ((plane * p.tiles_h + t) * p.Wo + c) * (size_t)p.Cout + v * 8));
+                if (c < p.Wo) m = pk_max_relu16(m, *(const u32x4*)(rb + ((plane * p.tiles_h + t) * p.Wo + c) * (size_t)p.Cout + v * 8));
             }
             if (pw_seam) {
                 const int s = (pw + 1) >> 3;
                 for (int dr = 0; dr < 2; ++dr)
-                    m = pk_max_nonneg16(m, *(const u32x4*)(cb + ((plane * p.tiles_w + s) * p.Ho + 2 * ph + dr) * (size_t)p.Cout + v * 8));
+                    m = pk_max_relu16(m, *(const u32x4*)(cb + ((plane * p.tiles_w + s) * p.Ho + 2 * ph + dr) * (size_t)p.Cout + v * 8));
             }
         } else {
             const int s = (pw + 1) >> 3;
             for (int dr = 0; dr < 3; ++dr) {
                 const int r = 2 * ph + dr;
-                if (r < p.Ho) m = pk_max_nonneg16(m, *(const u32x4*)(cb + ((plane * p.tiles_w + s) * p.Ho + r) * (size_t)p.Cout + v * 8));
+                if (r < p.Ho) m = pk_max_relu16(m, *(const u32x4*)(cb + ((plane * p.tiles_w + s) * p.Ho + r) * (size_t)p.Cout + v * 8));
             }
         }
         *(u32x4*)yp = m;

@@ -97,16 +97,18 @@ def pack_weight(bk, w, dt, perm=None):
     return out
 
 
-def run_conv(bk, x, w, scale, shift, dt, relu=True, res=None, x_pad=(0, 0), y_pad=(0, 0), use_ws=False):
+def run_conv(bk, x, w, scale, shift, dt, relu=True, res=None, x_pad=(0, 0), y_pad=(0, 0), use_ws=False, poison=None):
     """x NCDHW fp32, w torch layout; x_pad/y_pad = extra channels (before, after) in the buffers.
-    use_ws: call step_conv_forward_ws with the scratch buffer step_conv_workspace_bytes asks for."""
+    use_ws: call step_conv_forward_ws with the scratch buffer step_conv_workspace_bytes asks for.
+    poison: the value of the extra input channels on both sides (default: 77 before, -55 after); NaN makes a read of them -- even one
+    multiplied by a zero-padded weight -- show in the output."""
     N, Cin, D, H, W = x.shape
     Cout = w.shape[0]
     xc = cl(x)
     xb = np.zeros(xc.shape[:-1] + (x_pad[0] + Cin + x_pad[1],), np.float32)
     xb[..., x_pad[0]:x_pad[0] + Cin] = xc
-    xb[..., :x_pad[0]] = 77.0           # must never be read
-    xb[..., x_pad[0] + Cin:] = -55.0
+    xb[..., :x_pad[0]] = 77.0 if poison is None else poison           # must never be read
+    xb[..., x_pad[0] + Cin:] = -55.0 if poison is None else poison
     xe = bk.dev(encode(xb, dt))
     yb = bk.dev(np.zeros((N, D, H, W, y_pad[0] + Cout + y_pad[1]), NP_DT[dt]))
     wp = pack_weight(bk, w, dt)
@@ -129,9 +131,12 @@ def run_conv(bk, x, w, scale, shift, dt, relu=True, res=None, x_pad=(0, 0), y_pa
     return uncl(y[..., y_pad[0]:y_pad[0] + Cout])
 
 
-def ref_conv(x, w, scale, shift, dt, relu=True, res=None):
+def ref_conv(x, w, scale, shift, dt, relu=True, res=None, f64=False):
+    """f64: the whole restatement in double (the result is NOT rounded to the storage type)"""
     xq = torch.from_numpy(quantize(x, dt))
     wq = torch.from_numpy(quantize(w, dt))
+    if f64:
+        xq, wq = xq.double(), wq.double()
     y = F.conv3d(xq, wq, padding=tuple(k // 2 for k in w.shape[2:]))
     if scale is not None:
         y = y * torch.from_numpy(scale).view(1, -1, 1, 1, 1)
@@ -156,9 +161,12 @@ def run_stem(bk, x_ntchw, w, scale, shift, dt):
     return uncl(decode(y.get(), dt))
 
 
-def ref_stem(x, w, scale, shift, dt):
+def ref_stem(x, w, scale, shift, dt, f64=False):
     xq = torch.from_numpy(quantize(x, dt)).permute(0, 2, 1, 3, 4)
-    y = F.conv3d(F.pad(xq, (2, 3, 2, 3, 2, 3)), torch.from_numpy(quantize(w, dt)), stride=2)
+    wq = torch.from_numpy(quantize(w, dt))
+    if f64:
+        xq, wq = xq.double(), wq.double()
+    y = F.conv3d(F.pad(xq, (2, 3, 2, 3, 2, 3)), wq, stride=2)
     return F.relu(y * torch.from_numpy(scale).view(1, -1, 1, 1, 1) + torch.from_numpy(shift).view(1, -1, 1, 1, 1)).numpy()
 
 
