@@ -102,6 +102,28 @@ def ava_clips(seed, batch):
     return torch.rand(batch, 36, 3, 400, 400, generator=g) * 2 - 1
 
 
+def write_padded_slots(flat, tgt, mask, inv, sel, tgts, pad, budget, num_classes, who):
+    """One step's host selection into its padded host blocks (numpy, in place): `budget` slots per clip, clip b's selected rows sel[b] /
+    tgts[b] first, the box pad[b] [Tl, 4] (valid for ROIAlign), all-zero targets and row weight 0 in the rest; column 0 of `flat` is the
+    frame index inside the step's feature frames flattened over clips; inv[0] = 1 / (real rows x classes), the masked mean's factor."""
+    Tl = flat.shape[1]
+    tgt[...] = 0
+    mask[...] = 0
+    n_real = 0
+    for b in range(len(sel)):
+        n = len(sel[b])
+        if n > budget:
+            raise RuntimeError("%s: %d tubes selected for one clip, budget %d" % (who, n, budget))
+        lo, hi = b * budget, (b + 1) * budget
+        flat[lo:lo + n, :, 1:] = sel[b]
+        flat[lo + n:hi, :, 1:] = pad[b]
+        flat[lo:hi, :, 0] = b * Tl + np.arange(Tl, dtype=np.float32)
+        tgt[lo:lo + n] = tgts[b]
+        mask[lo:lo + n] = 1
+        n_real += n
+    inv[0] = 1.0 / (max(n_real, 1) * num_classes)
+
+
 class C4TrainStep:
     """One optimisation step on `batch` AVA-shaped clips per rank (fp32): backbone + ContextNet + the max_iter = 3 heads on
     tubes of 3, 3 and 9 frames (NUM_CHUNKS 1, 1, 3), the three losses of train.py:318-331 summed over the steps
@@ -208,12 +230,21 @@ class C4TrainStep:
             pooled = pooled.reshape(self.batch * self.K, Tl, *pooled.shape[1:])
             o = head(pooled, context_feat=self._ctx_per_tube(cx, self.K)[:, :, t0:t0 + Tl], tubes=flat, targets=self.targets)
             loss = loss + o[4].mean() + 5 * o[5].mean() + o[6].mean()
+        return self._backward(loss, exchange)
+
+    def _backward(self, loss, exchange):
+        """backward into the gradient arena; exchange=True overlaps the bucketed all-reduce with it.  The averaging factor is left in self.scale."""
         if exchange:
             self.reducer.begin()
         with wgrad_into_grad():                                   # weight gradients go straight into FlatAdam's arena
             loss.backward()
         self.scale = self.reducer.finish() if exchange else 1.0
         return loss
+
+    def _finish(self, loss):
+        self._update(self.scale)
+        self.loss = loss.detach()
+        return self.loss
 
     def _update(self, grad_scale):
         """scheduler.step() (train.py:262) and optimizer.step() (train.py:348) of one iteration: the device schedule, the clip, the update
@@ -223,23 +254,43 @@ class C4TrainStep:
         self.opt.step(grad_scale=grad_scale, zero_grad=True, max_grad_norm=self.max_grad_norm)
 
     def _eager_step(self):
-        loss = self.forward_backward(exchange=True)
-        self._update(self.scale)
-        self.loss = loss.detach()
-        return self.loss
+        return self._finish(self.forward_backward(exchange=True))
 
     def step(self):
         if self.graph is not None:
             self.opt._refresh_tables()                           # lr / weight_decay of param_groups -> the device tables the captured Adam reads (schedulers keep working)
             self.graph.replay()                                  # ~800 launches (+ the bucket all-reduces of a multi-rank step), one submission
-            if self._g_update is not None:                       # "split" form: forward / backward replayed, the exchange eager, the update replayed
-                sdist.allreduce_flat(self.opt.flat_grad, wire=self.wire, single_rank=self.force_exchange)
-                self._g_update.replay()
-            # the replay re-packed the weights at its start and Adam changed them at its end: any eager use of the modules between
-            # replays (validation) must see its packed-weight caches as stale
-            torch.autograd.graph.increment_version(self.params)
-            return self.loss
+            return self._replay_tail()
         return self._eager_step()
+
+    def _replay_tail(self):
+        if self._g_update is not None:                           # split forms: forward / backward replayed, the exchange eager, the update replayed
+            sdist.allreduce_flat(self.opt.flat_grad, wire=self.wire, single_rank=self.force_exchange)
+            self._g_update.replay()
+        # the replay re-packed the weights at its start and Adam changed them at its end: any eager use of the modules between
+        # replays (validation) must see its packed-weight caches as stale
+        torch.autograd.graph.increment_version(self.params)
+        return self.loss
+
+    @staticmethod
+    def _world():
+        dd = torch.distributed
+        return dd.get_world_size() if (dd.is_available() and dd.is_initialized()) else 1
+
+    def _record(self, fn, pool=None):
+        """fn() recorded (not executed) as a graph of its own, in `pool` or a fresh one"""
+        # with a live process group its watchdog / heartbeat threads may touch the runtime while this thread records: only THIS thread's
+        # calls are checked against the capture
+        kw = {"capture_error_mode": "thread_local"} if self.reducer.active else {}
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=pool, **kw):
+            fn()
+        return g
+
+    def _record_update(self, pool=None):
+        """the update as a graph of its own, replayed behind ONE eager flat all-reduce (nothing of the process group is recorded)"""
+        scale = 1.0 / self._world()
+        return self._record(lambda: self._update(scale), pool)
 
     def _warm(self, warmup):
         dev = self.x.device
@@ -301,15 +352,9 @@ class C4TrainStep:
             import time
             torch.cuda.synchronize(dev)
             time.sleep(float(os.environ.get("STEP_PG_DRAIN_S", "1.0")))
-        # with a live process group its watchdog / heartbeat threads may touch the runtime while this thread records: only THIS thread's
-        # calls are checked against the capture
-        kw = {"capture_error_mode": "thread_local"} if grouped else {}
         if mode == "one":
             try:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, **kw):
-                    self._eager_step()
-                self.graph, self.graph_mode, self._g_update = g, "one", None
+                self.graph, self.graph_mode, self._g_update = self._record(self._eager_step), "one", None
             except RuntimeError as e:
                 if not grouped:
                     raise
@@ -323,15 +368,10 @@ class C4TrainStep:
                 self.opt.zero_grad()
                 mode = "split"
         if mode == "split":
-            g1 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g1, **kw):
-                loss = self.forward_backward(exchange=False)
-                self.loss = loss.detach()
-            world = dd.get_world_size() if (dd.is_available() and dd.is_initialized()) else 1
-            g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2, **kw):
-                self._update(1.0 / world)
-            self.graph, self._g_update, self.graph_mode = g1, g2, "split"
+            def fwd_bwd():
+                self.loss = self.forward_backward(exchange=False).detach()
+            g1 = self._record(fwd_bwd)
+            self.graph, self._g_update, self.graph_mode = g1, self._record_update(), "split"       # (two graphs, two pools)
         # host-side caches now carry the version stamps of a step whose kernels only run on replay: make them stale again for
         # any eager use of the modules after this point
         torch.autograd.graph.increment_version(self.params)
@@ -398,8 +438,10 @@ class C4SelectTrainStep(C4TrainStep):
         self.clip_of_pad = torch.arange(batch, device=dev).repeat_interleave(self.budget)
         self.s_flat, self.s_tgt, self.s_mask, self.s_inv = [], [], [], []
         self.h_flat, self.h_tgt, self.h_mask, self.h_inv = [], [], [], []
+        self.pad = []                                            # per step [B, Tl, 4]: the clip's first initial tube, a valid box for the padded slots' ROIAlign
         for i in range(1, a.max_iter + 1):
-            Tl = a.NUM_CHUNKS[i] * a.T
+            Tl = a.NUM_CHUNKS[i] * a.T                           # (the last step's tubes are 3 chunks long)
+            self.pad.append(np.stack([np.tile(np.asarray(t[0], np.float32), (Tl // t.shape[1] + 1, 1))[:Tl] for t in self.init_tubes]))
             for dst, host, shape in ((self.s_flat, self.h_flat, (K, Tl, 5)), (self.s_tgt, self.h_tgt, (K, 3, 6 + a.num_classes)),
                                      (self.s_mask, self.h_mask, (K, 1)), (self.s_inv, self.h_inv, (1,))):
                 dst.append(torch.zeros(shape, device=dev) if selection == "host" else None)     # (device: the selector's own buffers, below)
@@ -414,11 +456,9 @@ class C4SelectTrainStep(C4TrainStep):
             self.d_clip_start = torch.as_tensor(np.concatenate(([0], np.cumsum(self.nums0))).astype(np.int32), device=dev)
             self.d_pad = []
             for i in range(1, a.max_iter + 1):
-                Tl = a.NUM_CHUNKS[i] * a.T
-                fill = np.stack([np.tile(np.asarray(t[0], np.float32), (Tl // t.shape[1] + 1, 1))[:Tl] for t in self.init_tubes])
-                self.d_pad.append(torch.from_numpy(fill).to(dev))
+                self.d_pad.append(torch.from_numpy(self.pad[i - 1]).to(dev))
                 self.s_flat[i - 1], self.s_tgt[i - 1], self.s_mask[i - 1], self.s_inv[i - 1] = self.selector.out[i][:4]
-        self._gF = self._gB = self._gU = None
+        self._gF = self._gB = None
         self._front = None
 
     @property
@@ -465,13 +505,7 @@ class C4SelectTrainStep(C4TrainStep):
             pooled = pooled.reshape(flat.shape[0], Tl, *pooled.shape[1:])
             o = self.heads[i - 1](pooled, context_feat=cx[clip_of][:, :, t0:t0 + Tl], tubes=flat, targets=targets)
             loss = loss + o[4].mean() + a.lambda_reg * o[5].mean() + a.lambda_neighbor * o[6].mean()
-        self.reducer.begin()
-        with wgrad_into_grad():
-            loss.backward()
-        scale = self.reducer.finish()
-        self._update(scale)
-        self.loss = loss.detach()
-        return self.loss
+        return self._finish(self._backward(loss, True))
 
     # ---- the padded iteration in its three parts
     def _front_part(self):
@@ -500,35 +534,15 @@ class C4SelectTrainStep(C4TrainStep):
             return
         self.selected = []
         self.selection_ran = "host"
-        B, Bu = self.batch, self.budget
         for i in range(1, a.max_iter + 1):
-            Tl = a.NUM_CHUNKS[i] * a.T
             sel, tgt = train_select(i, history[i - 2] if i > 1 else None, self.gt, self.init_tubes, a)
             self.selected.append([len(s_) for s_ in sel])
-            hf, ht, hm = self.h_flat[i - 1].numpy(), self.h_tgt[i - 1].numpy(), self.h_mask[i - 1].numpy()
-            ht[...] = 0
-            hm[...] = 0
-            n_real = 0
-            for b in range(B):
-                n = len(sel[b])
-                if n > Bu:
-                    raise RuntimeError("C4SelectTrainStep: %d tubes selected for one clip, budget %d" % (n, Bu))
-                rows = slice(b * Bu, b * Bu + n)
-                pad = slice(b * Bu + n, (b + 1) * Bu)
-                hf[rows, :, 1:] = sel[b]
-                fill = np.asarray(self.init_tubes[b][0], np.float32)                  # a valid box for the padded slots' ROIAlign
-                if fill.shape[0] != Tl:                                               # (the last step's tubes are 3 chunks long)
-                    fill = np.tile(fill, (Tl // fill.shape[0] + 1, 1))[:Tl]
-                hf[pad, :, 1:] = fill
-                hf[b * Bu:(b + 1) * Bu, :, 0] = b * Tl + np.arange(Tl, dtype=np.float32)   # frame index inside cf[:, t0:t0+Tl] flattened over clips
-                ht[rows] = tgt[b]
-                hm[rows] = 1
-                n_real += n
-            self.h_inv[i - 1][0] = 1.0 / (max(n_real, 1) * a.num_classes)
-            self.s_flat[i - 1].copy_(self.h_flat[i - 1], non_blocking=True)
-            self.s_tgt[i - 1].copy_(self.h_tgt[i - 1], non_blocking=True)
-            self.s_mask[i - 1].copy_(self.h_mask[i - 1], non_blocking=True)
-            self.s_inv[i - 1].copy_(self.h_inv[i - 1], non_blocking=True)
+            # ONE set of pinned blocks: from step 2 on train_select reads the front's outputs on the host, a copy that is stream-ordered behind
+            # every earlier copy out of these blocks (step 1's block was copied ahead of that read in the iteration before)
+            blocks = (self.h_flat[i - 1], self.h_tgt[i - 1], self.h_mask[i - 1], self.h_inv[i - 1])
+            write_padded_slots(*(h.numpy() for h in blocks), sel, tgt, self.pad[i - 1], self.budget, a.num_classes, "C4SelectTrainStep")
+            for dst, src in zip((self.s_flat[i - 1], self.s_tgt[i - 1], self.s_mask[i - 1], self.s_inv[i - 1]), blocks):
+                dst.copy_(src, non_blocking=True)
 
     def _loss_part(self, cf, cx):
         a = self.args
@@ -549,14 +563,9 @@ class C4SelectTrainStep(C4TrainStep):
 
     def _back_part(self, cf, cx, update=True):
         loss = self._loss_part(cf, cx)
-        exchange = update                                        # (split form: the exchange is eager, between the graphs)
-        if exchange:
-            self.reducer.begin()
-        with wgrad_into_grad():
-            loss.backward()
+        self._backward(loss, update)                             # (split form: the exchange is eager, between the graphs)
         if update:
-            scale = self.reducer.finish()
-            self._update(scale)
+            return self._finish(loss)
         self.loss = loss.detach()
         return self.loss
 
@@ -574,60 +583,36 @@ class C4SelectTrainStep(C4TrainStep):
         if not self.opt.capturable:
             raise RuntimeError("C4SelectTrainStep.capture: build the workload with capturable=True")
         import gc
-        dd = torch.distributed
         grouped = self.reducer.active
         gc.collect()
+        self._warm(max(int(warmup), 2))
         dev = self.x.device
-        cur = torch.cuda.current_stream(dev)
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(cur)
-        with torch.cuda.stream(s):
-            for _ in range(max(int(warmup), 2)):
-                self.step_padded()
-        cur.wait_stream(s)
-        torch.cuda.synchronize(dev)
-        kw = {"capture_error_mode": "thread_local"} if grouped else {}
         if self.selection == "device":
             # nothing between the iteration's first launch and its last needs the host: front, selection and back are ONE recording
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, **kw):
-                cf, cx, hist = self._front_part()
-                self._select_part(hist)
-                self._back_part(cf, cx, update=not grouped)
-            gU = None
-            if grouped:
-                world = dd.get_world_size() if (dd.is_available() and dd.is_initialized()) else 1
-                gU = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gU, pool=g.pool(), **kw):
-                    self._update(1.0 / world)
-            self._gF, self._gB, self._gU = g, None, gU
-            self.graph, self.graph_mode = g, ("select-one-split" if grouped else "select-one")
-            torch.autograd.graph.increment_version(self.params)
-            return self
-        gF = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gF, **kw):
-            self._front = self._front_part()
-        pool = gF.pool()
-        cf, cx, hist = self._front
-        gF.replay()                                              # (a capture records, it does not run: give the selection real predictions to read)
-        torch.cuda.synchronize(dev)
-        import random
-        rs_py, rs_np = random.getstate(), np.random.get_state()  # this selection trains nothing: it must not consume draws of the reference's RNG streams
-        self._select_part(hist)
-        random.setstate(rs_py)
-        np.random.set_state(rs_np)
-        torch.cuda.synchronize(dev)
-        gB = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gB, pool=pool, **kw):
-            self._back_part(cf, cx, update=not grouped)
-        gU = None
-        if grouped:
-            world = dd.get_world_size() if (dd.is_available() and dd.is_initialized()) else 1
-            gU = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gU, pool=pool, **kw):
-                self._update(1.0 / world)
-        self._gF, self._gB, self._gU = gF, gB, gU
-        self.graph, self.graph_mode = gF, ("select-split" if grouped else "select")
+            front = []                                           # (the front's outputs stay alive while the update is recorded into the same pool)
+
+            def whole():
+                front[:] = self._front_part()
+                self._select_part(front[2])
+                self._back_part(front[0], front[1], update=not grouped)
+            gF, gB, form = self._record(whole), None, "select-one"
+        else:
+            def front_part():
+                self._front = self._front_part()
+            gF, form = self._record(front_part), "select"
+            cf, cx, hist = self._front
+            gF.replay()                                          # (a capture records, it does not run: give the selection real predictions to read)
+            torch.cuda.synchronize(dev)
+            import random
+            rs_py, rs_np = random.getstate(), np.random.get_state()  # this selection trains nothing: it must not consume draws of the reference's RNG streams
+            self._select_part(hist)
+            random.setstate(rs_py)
+            np.random.set_state(rs_np)
+            torch.cuda.synchronize(dev)
+            gB = self._record(lambda: self._back_part(cf, cx, update=not grouped), gF.pool())
+        gU = self._record_update(gF.pool()) if grouped else None     # (the select forms share the front graph's pool)
+        self._gF, self._gB, self._g_update = gF, gB, gU
+        self.graph, self.graph_mode = gF, form + ("-split" if grouped else "")
         torch.autograd.graph.increment_version(self.params)
         return self
 
@@ -637,11 +622,7 @@ class C4SelectTrainStep(C4TrainStep):
         if self._gB is not None:                                 # (device selection: the one graph holds all three parts)
             self._select_part(self._front[2])                    # host: reads the inference's static outputs (one small copy per step)
             self._gB.replay()
-        if self._gU is not None:
-            sdist.allreduce_flat(self.opt.flat_grad, wire=self.wire, single_rank=self.force_exchange)
-            self._gU.replay()
-        torch.autograd.graph.increment_version(self.params)
-        return self.loss
+        return self._replay_tail()
 
 
 class C4ClsTrainStep(C4TrainStep):
@@ -744,24 +725,12 @@ class C4ClsTrainStep(C4TrainStep):
         """the host selection into the pinned blocks, then four stream-ordered copies into the static buffers"""
         a = self.args
         sel, tgt = self._host_selection()
-        Bu = self.budget
         k = self._turn
         self._turn = 1 - k
         if self._pinned_free[k] is not None:
             self._pinned_free[k].synchronize()
         blocks = self._pinned[k]
-        hf, ht, hm = blocks[0].numpy(), blocks[1].numpy(), blocks[2].numpy()
-        ht[...] = 0
-        hm[...] = 0
-        for b in range(self.batch):
-            n = len(sel[b])
-            if n > Bu:
-                raise RuntimeError("C4ClsTrainStep: %d tubes selected for one clip, budget %d" % (n, Bu))
-            hf[b * Bu:b * Bu + n, :, 1:] = sel[b]
-            hf[b * Bu + n:(b + 1) * Bu, :, 1:] = self.pad[b]
-            ht[b * Bu:b * Bu + n] = tgt[b]
-            hm[b * Bu:b * Bu + n] = 1
-        blocks[3][0] = 1.0 / (max(sum(self._selected), 1) * a.num_classes)
+        write_padded_slots(*(h.numpy() for h in blocks), sel, tgt, self.pad, self.budget, a.num_classes, "C4ClsTrainStep")
         for dst, src in zip((self.s_flat, self.s_tgt, self.s_mask, self.s_inv), blocks):
             dst.copy_(src, non_blocking=True)
         if self.s_flat.is_cuda:
@@ -784,13 +753,7 @@ class C4ClsTrainStep(C4TrainStep):
         pooled = pooled.reshape(flat.shape[0], self.Tl, *pooled.shape[1:])
         o = self.heads[0](pooled, context_feat=cx[clip_of], tubes=flat, targets=targets)
         loss = o[4].mean()                                       # train_cls.py:311
-        self.reducer.begin()
-        with wgrad_into_grad():
-            loss.backward()
-        scale = self.reducer.finish()
-        self._update(scale)
-        self.loss = loss.detach()
-        return self.loss
+        return self._finish(self._backward(loss, True))
 
     # ---- the padded iteration: C4TrainStep's eager step, exchange, update and capture around this forward / backward
     def forward_backward(self, exchange=False):
@@ -805,12 +768,7 @@ class C4ClsTrainStep(C4TrainStep):
         pooled = pooled.reshape(K, self.Tl, *pooled.shape[1:])
         o = self.heads[0](pooled, context_feat=self._ctx_per_tube(cx, self.budget), tubes=self.s_flat, targets=self.s_tgt)
         loss = (o[4].view(K, -1) * self.s_mask).sum() * self.s_inv[0]      # the reference's .mean() runs over the REAL rows only
-        if exchange:
-            self.reducer.begin()
-        with wgrad_into_grad():
-            loss.backward()
-        self.scale = self.reducer.finish() if exchange else 1.0
-        return loss
+        return self._backward(loss, exchange)
 
     def _eager_step(self):
         # (the host's selection is drawn outside a recording: capture() records this step, step() draws before each replay)

@@ -52,7 +52,7 @@ def _run(mode, dropout, steps=4, warm=2):
 
     if mode == "graph":
         w.capture(warmup=warm)
-        assert w.graph_mode == "select-one" and w.graph is not None and w._gB is None and w._gU is None
+        assert w.graph_mode == "select-one" and w.graph is not None and w._gB is None and w._g_update is None
         assert w.rng.offset() == warm * (3 + (9 if dropout else 0))              # the recording itself draws nothing
         for _ in range(steps - warm):
             note(w.step())

@@ -229,3 +229,61 @@ def test_bench_rank_of_an_eight_gpu_launch_parses_its_arguments_and_environment(
     env["WORLD_SIZE"] = "4"
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode != 0 and "--gpus 8 but WORLD_SIZE=4" in (r.stderr + r.stdout), r.stderr[-800:]
+
+
+def test_write_padded_slots_fills_every_element():
+    """step_amd.workloads.write_padded_slots, the host writer behind both padded training workloads: B = 2 clips, budget 4, tubes of 3 frames,
+    5 classes.  Clip 0 selects nothing and clip 1 fills its budget; then 1 and 2 rows go into the SAME blocks (rows of the first call must not
+    survive); then nothing at all (the factor divides by one row, not by zero).  Every element of the four blocks against a table written
+    out here: rows, padding box, frame-index column b * Tl + t, targets, row mask, 1 / (rows * classes).  Five rows in one clip raise."""
+    from step_amd.workloads import write_padded_slots
+
+    flat, tgt = np.full((8, 3, 5), 7, np.float32), np.full((8, 3, 11), 7, np.float32)
+    mask, inv = np.full((8, 1), 7, np.float32), np.full((1,), 7, np.float32)
+    pad = np.array([[[-100, -101, -102, -103], [-110, -111, -112, -113], [-120, -121, -122, -123]],
+                    [[-200, -201, -202, -203], [-210, -211, -212, -213], [-220, -221, -222, -223]]], np.float32)
+
+    def row(r):                                        # selected tube r: box r * 100 + frame * 10 + coordinate; target rows r * 10 + frame
+        box = np.array([[r * 100 + t * 10 + c for c in range(4)] for t in range(3)], np.float32)
+        return box, np.array([[r * 10 + t] * 11 for t in range(3)], np.float32)
+
+    def clips(*rows_per_clip):
+        sel = [np.stack([row(r)[0] for r in rs]) if rs else np.zeros((0, 3, 4), np.float32) for rs in rows_per_clip]
+        tgts = [np.stack([row(r)[1] for r in rs]) if rs else np.zeros((0, 3, 11), np.float32) for rs in rows_per_clip]
+        return sel, tgts
+
+    def write(*rows_per_clip):
+        write_padded_slots(flat, tgt, mask, inv, *clips(*rows_per_clip), pad, 4, 5, "Workload")
+
+    P0 = [[0, -100, -101, -102, -103], [1, -110, -111, -112, -113], [2, -120, -121, -122, -123]]      # a padded slot of clip 0: frames 0..2
+    P1 = [[3, -200, -201, -202, -203], [4, -210, -211, -212, -213], [5, -220, -221, -222, -223]]      # ... of clip 1: frames 3..5
+    Z = [[0] * 11] * 3
+
+    write((), (1, 2, 3, 4))
+    assert np.array_equal(flat, np.array([
+        P0, P0, P0, P0,
+        [[3, 100, 101, 102, 103], [4, 110, 111, 112, 113], [5, 120, 121, 122, 123]],
+        [[3, 200, 201, 202, 203], [4, 210, 211, 212, 213], [5, 220, 221, 222, 223]],
+        [[3, 300, 301, 302, 303], [4, 310, 311, 312, 313], [5, 320, 321, 322, 323]],
+        [[3, 400, 401, 402, 403], [4, 410, 411, 412, 413], [5, 420, 421, 422, 423]]], np.float32))
+    assert np.array_equal(tgt, np.array([Z, Z, Z, Z, [[10] * 11, [11] * 11, [12] * 11], [[20] * 11, [21] * 11, [22] * 11],
+                                         [[30] * 11, [31] * 11, [32] * 11], [[40] * 11, [41] * 11, [42] * 11]], np.float32))
+    assert np.array_equal(mask, np.array([[0], [0], [0], [0], [1], [1], [1], [1]], np.float32))
+    assert np.array_equal(inv, np.array([1.0 / 20], np.float32))
+
+    write((5,), (6, 7))
+    assert np.array_equal(flat, np.array([
+        [[0, 500, 501, 502, 503], [1, 510, 511, 512, 513], [2, 520, 521, 522, 523]], P0, P0, P0,
+        [[3, 600, 601, 602, 603], [4, 610, 611, 612, 613], [5, 620, 621, 622, 623]],
+        [[3, 700, 701, 702, 703], [4, 710, 711, 712, 713], [5, 720, 721, 722, 723]], P1, P1], np.float32))
+    assert np.array_equal(tgt, np.array([[[50] * 11, [51] * 11, [52] * 11], Z, Z, Z,
+                                         [[60] * 11, [61] * 11, [62] * 11], [[70] * 11, [71] * 11, [72] * 11], Z, Z], np.float32))
+    assert np.array_equal(mask, np.array([[1], [0], [0], [0], [1], [1], [0], [0]], np.float32))
+    assert np.array_equal(inv, np.array([1.0 / 15], np.float32))
+
+    write((), ())
+    assert np.array_equal(flat, np.array([P0, P0, P0, P0, P1, P1, P1, P1], np.float32))
+    assert not tgt.any() and not mask.any() and np.array_equal(inv, np.array([1.0 / 5], np.float32))
+
+    with pytest.raises(RuntimeError, match="Workload: 5 tubes selected for one clip, budget 4"):
+        write((1,), (1, 2, 3, 4, 5))
