@@ -1027,6 +1027,85 @@ STEP_API int step_anchor_sample(const float* gt, const int32_t* gt_count, int B,
                                 int T, int pos_num, int neg_ratio, float pos_thresh, float neg_thresh, int mode,
                                 unsigned long long* rng_state, float* tubes, int32_t* clip_start, int32_t* counts, step_stream_t stream);
 
+/* The augmentation's DECISIONS on the device: what TubeAugmentation.plan (step_amd/augment.py; data/augmentations.py:172-586) draws per clip
+ * on the host -- photometric parameters, crop, mirror, erase rectangles -- plus the erase noise and the transformed ground truths, with the
+ * draws taken from the device-side generator of step_dropout_forward.  Same rule as the host form, NOT its decisions under numpy's seeds (the
+ * host form reproduces the reference's draws): the relation step_select_train has to train_select.  The output is the plan block
+ * step_clip_augment_u8 reads and the gt / gt_count step_select_train reads, as they lie; nothing but the uint8 frames crosses the bus.
+ *
+ * Launches: (a) the planner, one wavefront per clip; (b) the noise fill.  No host synchronisation.  The call owns offsets `offset`
+ * (decisions) and `offset + 1` (noise); thread 0 of (b) advances the state by 2, also for N == 0.  A refused call writes nothing and leaves
+ * the offset alone.
+ *
+ * Inputs (device memory).  src [N] uint64 addresses of the clips' [T,Hs,Ws,3] frames (copied into the block, never dereferenced here);
+ * dims [N,2] int32 (Hs, Ws), clips may differ (values below 1 are read as 1); gt_in [N,Gmax,F,4+NC] fp32 boxes in percent coordinates +
+ * labels, an all-zero box is a padding frame of a tube; gt_count [N] int32 (clamped to [0, Gmax]); rng_state {seed, offset}.  switches: the
+ * STEP_AUGP_* bits; scale 0 / 1 / 2: the noise range [0,255] / [0,1] / [-1,1]; (Wn, Hn) the network resolution; max_hw: the largest
+ * Hs * Ws the block was sized for.
+ *
+ * The plan block (16-byte aligned, step_augment_plan_bytes(N, Gmax, max_hw, &cap_words) bytes), a STATIC layout in 4-byte words so that a
+ * captured graph can own it:
+ *   [0, 16 N)                               step_aug_clip[N]; clip n has rect_off = 16 N + 6 Gmax n
+ *   16 N + 6 Gmax n + 6 k                   step_aug_rect k of clip n (slots k >= n_rects are zero)
+ *   rec = 16 N + 6 Gmax N                   the call record: offset_lo, offset_hi of the call that wrote the block, 0, 0
+ *   rec + 4 + (n Gmax + k) * cap_words      the patch of rectangle k of clip n (only its (y2-y1)(x2-x1)3 first words are written)
+ * cap_words.  get_region accepts a rectangle of real size We x He inside its box with We He = Se <= sh S, sh = 0.2, S <= A = max Hs Ws the
+ * box's area; We = sqrt(Se / re) <= sqrt(sh A / r1), He = sqrt(Se re) <= sqrt(sh A r2), r1 = 0.3, r2 = 10/3, both = sqrt(2 A / 3).  The
+ * integer rectangle is int(xe + We) - int(xe) <= We + 1 by int(ye + He) - int(ye) <= He + 1 (the +1 of the two truncations), so its pixels
+ * are at most (We + 1)(He + 1) = Se + We + He + 1 <= 0.2 A + 2 sqrt(2 A / 3) + 1.  cap_words = 3 (floor(that) + 2), the 2 covering the
+ * fp32 roundings of S, Se, We and He.  The planner drops a rectangle that exceeds cap_words or leaves its crop; for boxes inside their frame
+ * the bound says that never happens.  cap_words > 2^22, N Gmax > 65535 or a block above 2^31 words -> STEP_E_UNSUPPORTED.
+ *
+ * Outputs besides the block.  gt_out [N,Gmax,F,4+NC]: what the loader hands the training loop (data/ava.py:361): the tubes the crop kept,
+ * compacted in index order, labels copied, boxes = scale_tubes_abs(percent of the cropped frame, Wn, Hn); the other rows zero.
+ * gt_count_out [N].
+ *
+ * The rule, per clip n (W = Ws, H = Hs, G = gt_count[n], mid = F / 2), in the order and the TYPES of TubeAugmentation.plan under NumPy 2's
+ * promotion: draws and crop rectangles in double, tubes in fp32, every operation rounded on its own (no contraction).
+ *   Draws.  u(phase, k) = step_select_train's draw (n, phase, k): Philox block (n << 20) | (phase << 16) | k at the call's offset,
+ *     u = ((w0 << 21) | (w1 >> 11)) * 2^-53; randint(m) = min(floor(u m), m - 1); uniform(a, b) = a + (b - a) u; uniform(a) = a + (1 - a) u.
+ *   1 Photometric (STEP_AUGP_PHOTOMETRIC), phase 0, one FIXED slot k per draw of the host rule, consumed or not: 0 brightness coin, 1
+ *     uniform(-32, 32); 2 contrast-first coin; 3 coin, 4 uniform(0.5, 1.5) of the contrast when it comes first; 5 coin, 6 uniform(0.5, 1.5)
+ *     saturation; 7 coin, 8 uniform(-18, 18) hue; 9 coin, 10 uniform(0.5, 1.5) of the contrast when it comes last; 11 coin, 12 randint(6) the
+ *     channel permutation ((0,1,2), (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0)).  Parameters are rounded to fp32.
+ *   2 Tubes to pixels: box * (W, H, W, H) in fp32.
+ *   3 Crop (STEP_AUGP_CROP), phase 1.  Round r = 0..15: mode = randint(7) at k = 3200 + r; mode 0 keeps the whole frame; else min_iou =
+ *     0.1, 0.3, 0.5, 0.7, 0.9, -inf and trials t = 0..49 with k = (50 r + t) 4 + slot: w = uniform(0.3 W, W) [0], h = uniform(0.3 H, H) [1];
+ *     rejected when h / w < 0.5 or h / w > 2; left = uniform(W - w) [2], top = uniform(H - h) [3]; rect = (int(left), int(top),
+ *     int(left + w), int(top + h)); over the G middle-frame boxes b (padding boxes included): sides = max(min(b.hi, rect.hi) - max(b.lo,
+ *     rect.lo), 0) in double, inter their product, overlap = inter / ((double(area_b) + area_rect) - inter) with area_b in fp32; rejected
+ *     when the minimum overlap < min_iou (no box: nothing to undercut; a NaN overlap rejects nothing); a box is KEPT when rect.lo < its
+ *     centre ((lo + hi) / 2 in fp32) < rect.hi in x and y; rejected when no box is kept -- always, therefore, when G = 0 -- or when the
+ *     rectangle is empty or leaves the frame (cannot happen from W, H >= 4).  The first accepted trial of the first round that has one is
+ *     the crop: kept tubes, all frames, box = max(clamp(box, rect) - rect.lo, 0) in fp32; (width, height) = the crop's size.
+ *   4 Mirror (STEP_AUGP_FLIP), phase 2 k = 0: a coin; boxes with ((x1 + y1) + x2) + y2 > 0: (x1, x2) = (width - x2, width - x1) in fp32.
+ *   5 Erase (STEP_AUGP_ERASE), phase 2 k = 1: a coin; then per kept tube j in order, its middle-frame box (x1, y1, x2, y2), fp32 S =
+ *     (x2 - x1)(y2 - y1), phase 3, trials t = 0..63 with k = (64 j + t) 4 + slot: Se = fp32(uniform(0.02, 0.2) [0]) S, re = fp32(uniform(0.3,
+ *     10/3) [1]), He = sqrt(Se re), We = sqrt(Se / re) in fp32 (IEEE); xe = uniform(x1, x2 - We) [2], ye = uniform(y1, y2 - He) [3] in
+ *     double; accepted when fp32(xe) + We <= x2 and fp32(ye) + He <= y2; rectangle (int(xe), int(ye), int(fp32(xe) + We), int(fp32(ye) + He)).
+ *     The first accepted trial gives the tube's rectangle; accepted rectangles are numbered k = 0.. in tube order (later ones win).
+ *     Noise element e of patch (n, k): word e & 3 of Philox block ((n Gmax + k) << 20) | (e >> 2) at offset + 1, value lo + (hi - lo) *
+ *     ((word >> 8) * 2^-24) in double, rounded to fp32.
+ *   6 Percent: box / (width, height, width, height) in fp32; gt_out = min(max(., 0), 1) * (Wn, Hn, Wn, Hn) in fp32.
+ * Deviations from the host form.  (1) Other draws: the stream above, not numpy's.  (2) Bounded loops: the crop gives up after 16 rounds and
+ * keeps the whole frame; get_region gives up after 64 trials and erases nothing for that box (the reference loops `while True`).  With
+ * addressed draws the trials of a round are evaluated side by side and the first accepted one is taken, which is the sequential rule's
+ * result.  (3) Proposals are not transformed: the device form serves the anchor-grid recipe.
+ *
+ * Errors: negative N / Gmax / NC, F < 1, Wn / Hn / max_hw < 1, scale outside 0..2, unknown switch bits -> STEP_E_SHAPE; Gmax > 64 ->
+ * STEP_E_UNSUPPORTED (step_select_train's limit for the same buffers); rng_state NULL, or with N > 0 any other pointer NULL -> STEP_E_NULL;
+ * rng_state not 8-byte or the block not 16-byte aligned -> STEP_E_ALIGN.
+ * The planner itself guarantees what step_clip_augment_u8 trusts its caller for: every crop inside its frame, every rectangle inside its
+ * crop, every offset inside the block. */
+#define STEP_AUGP_FLIP        1       /* switches: TubeAugmentation's do_flip, do_crop, do_photometric, do_erase */
+#define STEP_AUGP_CROP        2
+#define STEP_AUGP_PHOTOMETRIC 4
+#define STEP_AUGP_ERASE       8
+STEP_API size_t step_augment_plan_bytes(int N, int Gmax, long long max_hw, int* cap_words);      /* 0 for bad arguments */
+STEP_API int step_augment_plan(const unsigned long long* src, const int32_t* dims, const float* gt_in, const int32_t* gt_count, int N,
+                               int Gmax, int F, int NC, int switches, int scale, int Wn, int Hn, long long max_hw,
+                               unsigned long long* rng_state, void* plan_block, float* gt_out, int32_t* gt_count_out, step_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

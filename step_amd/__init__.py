@@ -10,11 +10,11 @@ from .optim import DeviceWarmupCosineLR, DeviceWarmupStepLR, FlatAdam, FlatSGD, 
 from . import evaluate  # noqa: F401
 from .evaluate import FrameMAP, ava_evaluation  # noqa: F401
 from . import augment  # noqa: F401
-from .augment import BaseTransform, TubeAugmentation  # noqa: F401
+from .augment import BaseTransform, DeviceTubeAugmentation, TubeAugmentation  # noqa: F401
 from . import video  # noqa: F401
 from .video import FrameRing, VideoClips, clip_frame_indices, detect_video  # noqa: F401
 
 __all__ = ["BaseNet", "ROINet", "TwoBranchNet", "ContextNet", "I3D", "I3D_head", "FrameMAP", "ava_evaluation",
-           "TubeAugmentation", "BaseTransform", "Dropout", "DeviceRNG", "manual_seed", "FrameRing", "VideoClips", "clip_frame_indices",
+           "TubeAugmentation", "DeviceTubeAugmentation", "BaseTransform", "Dropout", "DeviceRNG", "manual_seed", "FrameRing", "VideoClips", "clip_frame_indices",
            "detect_video"]
 __version__ = "0.1.0"

@@ -19,7 +19,7 @@ import torch
 
 from . import _capi, _lib
 
-__all__ = ["AugPlan", "TubeAugmentation", "BaseTransform"]
+__all__ = ["AugPlan", "TubeAugmentation", "BaseTransform", "DeviceTubeAugmentation"]
 
 F_MIRROR, F_PHOTOMETRIC, F_BRIGHTNESS, F_CONTRAST, F_CONTRAST_FIRST, F_SATURATION, F_HUE = 1, 2, 4, 8, 16, 32, 64    # include/step_amd.h
 _PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
@@ -310,3 +310,94 @@ class TubeAugmentation(_Transform):
             ye = rnd.uniform(y1, y2 - He)
             if xe + We <= x2 and ye + He <= y2:
                 return int(xe), int(ye), int(xe + We), int(ye + He)
+
+
+class DeviceTubeAugmentation(_Transform):
+    """TubeAugmentation with the DECISIONS made on the device too (include/step_amd.h: step_augment_plan): the constructor arguments of
+    TubeAugmentation plus `rng`, a step_amd.DeviceRNG.  `.apply()` is the planner, the noise fill and step_clip_augment_u8 on the current
+    stream -- three launches, two offsets of `rng`, no copy and no host synchronisation, so the calls can be recorded in a graph and every
+    replay draws anew.  Besides the clip it writes the transformed ground truths, the `gt` / `gt_count` step_select_train reads.  Same
+    rule as TubeAugmentation.plan, other draws (the device generator's, not numpy's); proposals are not transformed."""
+
+    def __init__(self, size=300, mean=(0, 0, 0), stds=(1, 1, 1), do_flip=False, do_crop=False, do_photometric=False, do_erase=False, scale=1,
+                 rng=None):
+        super().__init__(size, mean, stds, scale)
+        self.rng = rng                                       # (None: bound later by the workload whose generator it shares)
+        self.do_flip, self.do_crop, self.do_photometric, self.do_erase = bool(do_flip), bool(do_crop), bool(do_photometric), bool(do_erase)
+        self.switches = (1 if self.do_flip else 0) | (2 if self.do_crop else 0) | (4 if self.do_photometric else 0) | (8 if self.do_erase else 0)
+        self._static = None                                  # (key, block, max_hw): one block per (N, Gmax, largest frame)
+        self._frames = None                                  # (key, src [N] int64, dims [N,2] int32) of the frame buffers last seen
+
+    def _block(self, N, Gmax, max_hw, dev):
+        key = (N, Gmax, max_hw, dev)
+        if self._static is None or self._static[0] != key:
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("step_amd: DeviceTubeAugmentation builds its plan block on the first apply() of a batch shape; run apply() once before capturing")
+            nbytes = _lib.lib().step_augment_plan_bytes(N, Gmax, max_hw, None)
+            if nbytes == 0:
+                raise RuntimeError("step_amd: no plan block for N=%d, Gmax=%d, frames of %d pixels" % (N, Gmax, max_hw))
+            self._static = (key, torch.zeros(nbytes, dtype=torch.uint8, device=dev))
+        return self._static[1]
+
+    def _sources(self, clips, dev):
+        """the clips' addresses and sizes ON THE DEVICE: uploaded when other frame buffers are handed in than the last time (the stage
+        buffer of a captured step never changes), so not inside a capture"""
+        key = tuple((c.data_ptr(), c.shape[1], c.shape[2]) for c in clips)
+        if self._frames is None or self._frames[0] != key:
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("step_amd: DeviceTubeAugmentation cannot take new frame buffers inside a graph capture (run apply() on them once before)")
+            src = np.array([k[0] for k in key], np.uint64).view(np.int64)
+            dims = np.array([[k[1], k[2]] for k in key], np.int32)
+            self._frames = (key, torch.from_numpy(src).to(dev), torch.from_numpy(dims).to(dev))
+        return self._frames[1], self._frames[2]
+
+    def apply(self, frames, gt, gt_count, out=None, gt_out=None, gt_count_out=None, dtype=torch.bfloat16, rgb=True):
+        """frames: one device uint8 tensor [N,T,Hs,Ws,3] or a list of N per-clip [T,Hs_i,Ws_i,3] device tensors (BGR); gt [N,Gmax,F,4+NC]
+        float32 percent boxes + labels (an all-zero box pads a tube) and gt_count [N] int32, on the device.  Returns (clip [N,T,3,Ho,Wo],
+        gt_out [N,Gmax,F,4+NC] in pixels of the network's resolution, kept tubes first, gt_count_out [N]); `out`, `gt_out`,
+        `gt_count_out` are filled when given (out's dtype wins)."""
+        L = _lib.lib()
+        clips = list(frames.unbind(0)) if torch.is_tensor(frames) else list(frames)
+        N = len(clips)
+        if N == 0:
+            raise RuntimeError("step_amd: apply() wants at least one clip")
+        T, dev = clips[0].shape[0], clips[0].device
+        for c in clips:
+            if c.dtype != torch.uint8 or c.dim() != 4 or c.shape[-1] != 3 or not c.is_contiguous() or c.device != dev or c.shape[0] != T:
+                raise RuntimeError("step_amd: apply() expects contiguous uint8 clips [T,H,W,3] of one length on one device")
+        if gt.dim() != 4 or gt.shape[0] != N or gt.shape[3] < 4 or gt.dtype != torch.float32 or not gt.is_contiguous() or gt.device != dev:
+            raise RuntimeError("step_amd: apply() wants gt as a contiguous float32 [N,Gmax,F,4+NC] tensor on the frames' device")
+        if tuple(gt_count.shape) != (N,) or gt_count.dtype != torch.int32 or gt_count.device != dev:
+            raise RuntimeError("step_amd: apply() wants gt_count as an int32 [N] tensor on the frames' device")
+        if self.rng is None:
+            raise RuntimeError("step_amd: DeviceTubeAugmentation needs rng, a step_amd.DeviceRNG")
+        if self.rng.device.type != dev.type or self.rng.device.index not in (None, dev.index):
+            raise RuntimeError("step_amd: the generator lives on %s, the frames on %s" % (self.rng.device, dev))
+        Gmax, F, NC = gt.shape[1], gt.shape[2], gt.shape[3] - 4
+        Wo, Ho = self.size
+        if out is None:
+            out = torch.empty((N, T, 3, Ho, Wo), dtype=dtype, device=dev)
+        elif tuple(out.shape) != (N, T, 3, Ho, Wo) or not out.is_contiguous() or out.device != dev:
+            raise RuntimeError("step_amd: apply(out=...) wants a contiguous [N,T,3,%d,%d] tensor on the frames' device" % (Ho, Wo))
+        if gt_out is None:
+            gt_out = torch.empty_like(gt)
+        elif gt_out.shape != gt.shape or gt_out.dtype != torch.float32 or not gt_out.is_contiguous() or gt_out.device != dev:
+            raise RuntimeError("step_amd: apply(gt_out=...) wants a contiguous float32 tensor of gt's shape on the frames' device")
+        if gt_count_out is None:
+            gt_count_out = torch.empty_like(gt_count)
+        elif tuple(gt_count_out.shape) != (N,) or gt_count_out.dtype != torch.int32 or gt_count_out.device != dev:
+            raise RuntimeError("step_amd: apply(gt_count_out=...) wants an int32 [N] tensor on the frames' device")
+        max_hw = max(c.shape[1] * c.shape[2] for c in clips)
+        block = self._block(N, Gmax, max_hw, dev)
+        src, dims = self._sources(clips, dev)
+        _capi.check(L.step_augment_plan(_lib.dptr(src), _lib.dptr(dims), _lib.dptr(gt), _lib.dptr(gt_count), N, Gmax, F, NC, self.switches,
+                                        self.scale, Wo, Ho, max_hw, _lib.dptr(self.rng.state), _lib.dptr(block), _lib.dptr(gt_out),
+                                        _lib.dptr(gt_count_out), _lib.stream_ptr(dev)), "step_augment_plan")
+        self.launch(block, N, T, out, rgb)
+        return out, gt_out, gt_count_out
+
+    def last_block(self):
+        """the plan block of the last apply() (a uint8 device tensor in the layout of include/step_amd.h), for inspection"""
+        if self._static is None:
+            raise RuntimeError("step_amd: no apply() yet")
+        return self._static[1]

@@ -571,9 +571,297 @@ __global__ __launch_bounds__(64 * ANC_MAX_WAVES) void anchor_sample_kernel(Ancho
     for (size_t i = (size_t)rows * rowlen + tid; i < end; i += blockDim.x) p.tubes[i] = 0.0f;
 }
 
+// ---- the augmentation's decisions on the device (step_augment_plan; include/step_amd.h has the rule) ---------------------------------------
+// What TubeAugmentation.plan (step_amd/augment.py) draws per clip on the host: one wavefront per clip writes the clip's step_aug_clip, its
+// erase rectangles and the transformed ground truths.  A trial of the crop or of get_region depends on its own draws only, so the 50 (64)
+// trials of a round are evaluated with lane = trial and the first accepted one is taken by ballot: the sequential rule's result.  The tubes
+// are never stored: every stage after the crop is element-wise given (rectangle, kept set, mirror), so a box is recomputed where it is used.
+constexpr int AUGP_CROP_ROUNDS = 16, AUGP_CROP_TRIALS = 50, AUGP_ERASE_TRIALS = 64, AUGP_MODE_K = AUGP_CROP_ROUNDS * AUGP_CROP_TRIALS * 4;
+
+struct AugPlanParams {
+    const unsigned long long* src; const int32_t* dims; const float* gt_in; const int32_t* gt_count; const unsigned long long* rng;
+    unsigned char* block; float* gt_out; int32_t* gt_count_out;
+    int N, Gmax, F, NC, switches, scale, Wn, Hn, cap_words;
+};
+
+__device__ __forceinline__ float augp_div(float a, float b) { return (float)((double)a / (double)b); }     // IEEE fp32 quotient and root, whatever
+__device__ __forceinline__ float augp_sqrt(float a) { return (float)sqrt((double)a); }                    // the build's fast-math settings
+
+struct AugpState { int W, H, cropped, r0, r1, r2, r3, mirror, width, height; };
+
+// box (g, f) of clip n in pixels of the cropped, mirrored frame: _scale_xy, _shift_into + the clamp at 0, the mirror
+__device__ __forceinline__ void augp_box(const AugPlanParams& p, const AugpState& s, int n, int g, int f, float (&b)[4]) {
+    const float* q = p.gt_in + (((size_t)n * p.Gmax + g) * p.F + f) * (4 + p.NC);
+    b[0] = q[0] * (float)s.W; b[1] = q[1] * (float)s.H; b[2] = q[2] * (float)s.W; b[3] = q[3] * (float)s.H;
+    if (s.cropped) {
+        const float x0 = (float)s.r0, y0 = (float)s.r1, x1 = (float)s.r2, y1 = (float)s.r3;
+        b[0] = fmaxf((b[0] > x0 ? b[0] : x0) - x0, 0.0f);
+        b[1] = fmaxf((b[1] > y0 ? b[1] : y0) - y0, 0.0f);
+        b[2] = fmaxf((b[2] < x1 ? b[2] : x1) - x0, 0.0f);
+        b[3] = fmaxf((b[3] < y1 ? b[3] : y1) - y0, 0.0f);
+    }
+    if (s.mirror && (((b[0] + b[1]) + b[2]) + b[3]) > 0.0f) {                 // (zero-padded boxes stay where they are)
+        const float l = (float)s.width - b[2], r = (float)s.width - b[0];
+        b[0] = l; b[2] = r;
+    }
+}
+
+__global__ __launch_bounds__(64) void augment_plan_kernel(AugPlanParams p) {
+    __shared__ int s_rect[4];
+    __shared__ int s_fits;
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const unsigned long long seed = p.rng[0], off = p.rng[1];
+    int32_t* words = (int32_t*)p.block;
+    const int rect_base = 16 * p.N + 6 * p.Gmax * n;
+    const int rec_at = 16 * p.N + 6 * p.Gmax * p.N;                           // the call record, then the patches
+    const int patch_base = rec_at + 4;
+    AugpState s;
+    s.H = p.dims[2 * n]; s.W = p.dims[2 * n + 1];
+    s.H = s.H < 1 ? 1 : s.H; s.W = s.W < 1 ? 1 : s.W;
+    s.cropped = 0; s.r0 = 0; s.r1 = 0; s.r2 = s.W; s.r3 = s.H; s.mirror = 0; s.width = s.W; s.height = s.H;
+    int G = p.gt_count[n];
+    G = G < 0 ? 0 : G > p.Gmax ? p.Gmax : G;
+    const int mid = p.F / 2;
+
+    // photometric coins and parameters: phase 0, one fixed slot per draw of the host rule
+    int flags = 0, perm = 0x24;
+    float par[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (p.switches & STEP_AUGP_PHOTOMETRIC) {
+        flags |= STEP_AUG_PHOTOMETRIC;
+        if (sel_floor(sel_draw(seed, off, n, 0, 0), 2)) { flags |= STEP_AUG_BRIGHTNESS; par[0] = (float)anc_uniform(-32.0, 32.0, sel_draw(seed, off, n, 0, 1)); }
+        const int first = sel_floor(sel_draw(seed, off, n, 0, 2), 2);
+        if (first) {
+            flags |= STEP_AUG_CONTRAST_FIRST;
+            if (sel_floor(sel_draw(seed, off, n, 0, 3), 2)) { flags |= STEP_AUG_CONTRAST; par[1] = (float)anc_uniform(0.5, 1.5, sel_draw(seed, off, n, 0, 4)); }
+        }
+        if (sel_floor(sel_draw(seed, off, n, 0, 5), 2)) { flags |= STEP_AUG_SATURATION; par[2] = (float)anc_uniform(0.5, 1.5, sel_draw(seed, off, n, 0, 6)); }
+        if (sel_floor(sel_draw(seed, off, n, 0, 7), 2)) { flags |= STEP_AUG_HUE; par[3] = (float)anc_uniform(-18.0, 18.0, sel_draw(seed, off, n, 0, 8)); }
+        if (!first && sel_floor(sel_draw(seed, off, n, 0, 9), 2)) { flags |= STEP_AUG_CONTRAST; par[1] = (float)anc_uniform(0.5, 1.5, sel_draw(seed, off, n, 0, 10)); }
+        if (sel_floor(sel_draw(seed, off, n, 0, 11), 2)) {
+            const int k = sel_floor(sel_draw(seed, off, n, 0, 12), 6);        // _PERMS[k], packed 2 bits per channel
+            perm = k == 0 ? 0x24 : k == 1 ? 0x18 : k == 2 ? 0x21 : k == 3 ? 0x09 : k == 4 ? 0x12 : 0x06;
+        }
+    }
+
+    // RandomSampleCrop: phase 1
+    unsigned long long keep = G >= 64 ? ~0ull : (1ull << G) - 1ull;
+    if (p.switches & STEP_AUGP_CROP) {
+        const double Wd = (double)s.W, Hd = (double)s.H;
+        for (int round = 0; round < AUGP_CROP_ROUNDS; ++round) {
+            const int mode = sel_floor(sel_draw(seed, off, n, 1, AUGP_MODE_K + round), 7);
+            if (mode == 0) break;                                             // None: the whole frame
+            const double thr = mode == 1 ? 0.1 : mode == 2 ? 0.3 : mode == 3 ? 0.5 : mode == 4 ? 0.7 : mode == 5 ? 0.9 : -INFINITY;
+            const bool trial = lane < AUGP_CROP_TRIALS;
+            const int kb = (round * AUGP_CROP_TRIALS + (trial ? lane : 0)) * 4;
+            const double w = anc_uniform(0.3 * Wd, Wd, sel_draw(seed, off, n, 1, kb + 0));
+            const double h = anc_uniform(0.3 * Hd, Hd, sel_draw(seed, off, n, 1, kb + 1));
+            bool ok = trial && !(h / w < 0.5 || h / w > 2.0);
+            int r[4] = {0, 0, 0, 0};
+            unsigned long long kept = 0;
+            if (ok) {
+                const double lw = Wd - w, lh = Hd - h;
+                const double left = lw + (1.0 - lw) * sel_draw(seed, off, n, 1, kb + 2);
+                const double top = lh + (1.0 - lh) * sel_draw(seed, off, n, 1, kb + 3);
+                r[0] = (int)left; r[1] = (int)top; r[2] = (int)(left + w); r[3] = (int)(top + h);
+                // (a rectangle that is empty or leaves the frame is no crop: step_clip_augment_u8 trusts the block)
+                ok = r[0] >= 0 && r[1] >= 0 && r[2] > r[0] && r[3] > r[1] && r[2] <= s.W && r[3] <= s.H;
+            }
+            if (ok) {
+                const double area_r = (double)((long long)(r[2] - r[0]) * (long long)(r[3] - r[1]));
+                double m = INFINITY;
+                bool nan = false;
+                for (int g = 0; g < G; ++g) {
+                    float b[4];
+                    augp_box(p, s, n, g, mid, b);                             // (s is still the uncropped, unmirrored state)
+                    const double hx = (double)b[2] < (double)r[2] ? (double)b[2] : (double)r[2], hy = (double)b[3] < (double)r[3] ? (double)b[3] : (double)r[3];
+                    const double lx = (double)b[0] > (double)r[0] ? (double)b[0] : (double)r[0], ly = (double)b[1] > (double)r[1] ? (double)b[1] : (double)r[1];
+                    double sx = hx - lx, sy = hy - ly;
+                    sx = sx < 0.0 ? 0.0 : sx; sy = sy < 0.0 ? 0.0 : sy;
+                    const double inter = sx * sy;
+                    const float area_b = (b[2] - b[0]) * (b[3] - b[1]);
+                    const double ov = inter / (((double)area_b + area_r) - inter);
+                    if (ov != ov) nan = true;
+                    m = ov < m ? ov : m;
+                    const float cx = (b[0] + b[2]) / 2.0f, cy = (b[1] + b[3]) / 2.0f;
+                    if ((double)r[0] < (double)cx && (double)r[1] < (double)cy && (double)r[2] > (double)cx && (double)r[3] > (double)cy) kept |= 1ull << g;
+                }
+                if (!nan && m < thr) ok = false;                              // (numpy's min() hands a NaN on, and NaN < x is false)
+                if (kept == 0) ok = false;
+            }
+            const unsigned long long acc = __ballot(ok);
+            if (acc) {
+                const int win = __builtin_ctzll(acc);
+                if (lane == win) { s_rect[0] = r[0]; s_rect[1] = r[1]; s_rect[2] = r[2]; s_rect[3] = r[3]; }
+                keep = __shfl(kept, win);
+                __syncthreads();
+                s.cropped = 1; s.r0 = s_rect[0]; s.r1 = s_rect[1]; s.r2 = s_rect[2]; s.r3 = s_rect[3];
+                s.width = s.r2 - s.r0; s.height = s.r3 - s.r1;
+                break;
+            }
+        }
+    }
+    const int K = __builtin_popcountll(keep);
+
+    // mirror and the erase coin: phase 2
+    if ((p.switches & STEP_AUGP_FLIP) && sel_floor(sel_draw(seed, off, n, 2, 0), 2)) { s.mirror = 1; flags |= STEP_AUG_MIRROR; }
+    const bool erase = (p.switches & STEP_AUGP_ERASE) && sel_floor(sel_draw(seed, off, n, 2, 1), 2);
+
+    // RandomErase.get_region per kept box, in order: phase 3
+    int n_rects = 0;
+    if (erase) {
+        unsigned long long rest = keep;
+        for (int j = 0; j < K; ++j) {
+            const int g = __builtin_ctzll(rest);
+            rest &= rest - 1ull;
+            float b[4];
+            augp_box(p, s, n, g, mid, b);
+            const float S = (b[2] - b[0]) * (b[3] - b[1]);
+            const int kb = (j * AUGP_ERASE_TRIALS + lane) * 4;
+            const float Se = (float)anc_uniform(0.02, 0.2, sel_draw(seed, off, n, 3, kb + 0)) * S;
+            const float re = (float)anc_uniform(0.3, 10.0 / 3.0, sel_draw(seed, off, n, 3, kb + 1));
+            const float He = augp_sqrt(Se * re), We = augp_sqrt(augp_div(Se, re));
+            const double xe = anc_uniform((double)b[0], (double)(b[2] - We), sel_draw(seed, off, n, 3, kb + 2));
+            const double ye = anc_uniform((double)b[1], (double)(b[3] - He), sel_draw(seed, off, n, 3, kb + 3));
+            const float xr = (float)xe + We, yr = (float)ye + He;
+            const bool ok = xr <= b[2] && yr <= b[3];
+            const unsigned long long acc = __ballot(ok);
+            if (!acc) continue;                                               // 64 trials rejected: nothing erased for this box
+            const int win = __builtin_ctzll(acc);
+            if (lane == win) {
+                const int x1 = (int)xe, y1 = (int)ye, x2 = (int)xr, y2 = (int)yr;
+                // a rectangle outside its crop or larger than a patch slot is dropped (the bound of the header rules the second out)
+                const bool fits = x1 >= 0 && y1 >= 0 && x1 <= x2 && y1 <= y2 && x2 <= s.width && y2 <= s.height &&
+                                  (long long)(x2 - x1) * (long long)(y2 - y1) * 3 <= (long long)p.cap_words;
+                s_fits = fits; s_rect[0] = x1; s_rect[1] = y1; s_rect[2] = x2; s_rect[3] = y2;
+            }
+            __syncthreads();
+            const int fits = s_fits, x1 = s_rect[0], y1 = s_rect[1], x2 = s_rect[2], y2 = s_rect[3];
+            __syncthreads();
+            if (!fits) continue;
+            if (lane == 0) {
+                int32_t* rc = words + rect_base + 6 * n_rects;
+                rc[0] = x1; rc[1] = y1; rc[2] = x2; rc[3] = y2;
+                rc[4] = patch_base + (n * p.Gmax + n_rects) * p.cap_words; rc[5] = 0;
+            }
+            ++n_rects;
+        }
+    }
+    for (int i = 6 * n_rects + lane; i < 6 * p.Gmax; i += 64) words[rect_base + i] = 0;
+
+    if (lane == 0) {
+        int32_t* c = words + 16 * n;
+        *(unsigned long long*)c = p.src[n];
+        c[2] = s.H; c[3] = s.W; c[4] = s.r0; c[5] = s.r1; c[6] = s.width; c[7] = s.height; c[8] = flags; c[9] = perm;
+        float* cf = (float*)c;
+        cf[10] = par[0]; cf[11] = par[1]; cf[12] = par[2]; cf[13] = par[3];
+        c[14] = n_rects; c[15] = rect_base;
+        p.gt_count_out[n] = K;
+        if (n == 0) { words[rec_at] = (int32_t)(unsigned)off; words[rec_at + 1] = (int32_t)(unsigned)(off >> 32); words[rec_at + 2] = 0; words[rec_at + 3] = 0; }
+    }
+
+    // the ground truths the loader hands on: kept tubes compacted in index order, percent of the crop, scale_tubes_abs to (Wn, Hn)
+    const int E = 4 + p.NC, per = p.F * E;
+    float* out = p.gt_out + (size_t)n * p.Gmax * per;
+    for (int i = lane; i < p.Gmax * per; i += 64) {
+        const int j = i / per, f = (i % per) / E, c = i % E;
+        float v = 0.0f;
+        if (j < K) {
+            unsigned long long m = keep;
+            for (int t = 0; t < j; ++t) m &= m - 1ull;
+            const int g = __builtin_ctzll(m);
+            if (c >= 4) {
+                v = p.gt_in[(((size_t)n * p.Gmax + g) * p.F + f) * E + c];
+            } else {
+                float b[4];
+                augp_box(p, s, n, g, f, b);
+                const float bc = c == 0 ? b[0] : c == 1 ? b[1] : c == 2 ? b[2] : b[3];
+                const float pc = augp_div(bc, (float)((c & 1) ? s.height : s.width));
+                const float cl = fminf(fmaxf(pc, 0.0f), 1.0f);
+                v = cl * (float)((c & 1) ? p.Hn : p.Wn);
+            }
+        }
+        out[i] = v;
+    }
+}
+
+// the erase patches of the rectangles the planner accepted: element e of patch (n, k) is word e & 3 of block ((n Gmax + k) << 20) | (e >> 2)
+// at the planner's offset + 1, which every thread takes from the call record in the block; thread (0, 0) advances the generator by the call's
+// 2 (the planner has finished, and nothing here reads the state's offset)
+constexpr int AUGP_NOISE_RUN = 8;                                             // Philox blocks per thread
+__global__ __launch_bounds__(64) void augment_noise_kernel(unsigned char* block, int N, int Gmax, int cap_words, double lo, double hi,
+                                                           unsigned long long* rng) {
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) rng[1] += 2ull;
+    if (N * Gmax == 0) return;
+    const int32_t* words = (const int32_t*)block;
+    const int slot = blockIdx.y, n = slot / Gmax, k = slot % Gmax;
+    if (k >= words[16 * n + 14]) return;
+    const int rec_at = 16 * N + 6 * Gmax * N;
+    const int32_t* rc = words + 16 * N + 6 * Gmax * n + 6 * k;
+    long long used = (long long)(rc[2] - rc[0]) * (rc[3] - rc[1]) * 3;
+    used = used < cap_words ? used : cap_words;                                // (the planner dropped what would not fit: belt and braces)
+    const unsigned long long seed = rng[0];
+    const unsigned long long off = (((unsigned long long)(unsigned)words[rec_at + 1] << 32) | (unsigned long long)(unsigned)words[rec_at]) + 1ull;
+    float* dst = (float*)block + rc[4];
+    for (int i = 0; i < AUGP_NOISE_RUN; ++i) {
+        const long long q = ((long long)blockIdx.x * AUGP_NOISE_RUN + i) * 64 + threadIdx.x, e0 = 4 * q;
+        if (e0 >= used) return;
+        const unsigned long long blk = ((unsigned long long)slot << 20) | (unsigned long long)q;
+        unsigned w[4];
+        philox4x32_10((unsigned)blk, (unsigned)(blk >> 32), (unsigned)off, (unsigned)(off >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
+        const float v0 = (float)(lo + (hi - lo) * ((double)(w[0] >> 8) * (1.0 / 16777216.0))), v1 = (float)(lo + (hi - lo) * ((double)(w[1] >> 8) * (1.0 / 16777216.0)));
+        const float v2 = (float)(lo + (hi - lo) * ((double)(w[2] >> 8) * (1.0 / 16777216.0))), v3 = (float)(lo + (hi - lo) * ((double)(w[3] >> 8) * (1.0 / 16777216.0)));
+        dst[e0] = v0;
+        if (e0 + 1 < used) dst[e0 + 1] = v1;
+        if (e0 + 2 < used) dst[e0 + 2] = v2;
+        if (e0 + 3 < used) dst[e0 + 3] = v3;
+    }
+}
+
 }  // namespace step
 
 using namespace step;
+
+// the patch slot of step_augment_plan in words: 3 * (floor(0.2 A + 2 sqrt(2 A / 3) + 1) + 2), A = the largest Hs * Ws (header: derivation)
+static long long augp_cap_words(long long max_hw) {
+    const double A = (double)max_hw;
+    return 3 * ((long long)(0.2 * A + 2.0 * sqrt(2.0 * A / 3.0) + 1.0) + 2);
+}
+
+extern "C" size_t step_augment_plan_bytes(int N, int Gmax, long long max_hw, int* cap_words) {
+    if (N < 0 || Gmax < 0 || max_hw < 1) return 0;
+    const long long cap = augp_cap_words(max_hw);
+    if (cap_words) *cap_words = cap > 0x7fffffffLL ? 0 : (int)cap;
+    const long long words = 16ll * N + 6ll * Gmax * N + 4 + (long long)N * Gmax * cap;
+    return (size_t)(4 * ((words + 3) / 4 * 4));
+}
+
+extern "C" int step_augment_plan(const unsigned long long* src, const int32_t* dims, const float* gt_in, const int32_t* gt_count, int N, int Gmax,
+                                 int F, int NC, int switches, int scale, int Wn, int Hn, long long max_hw, unsigned long long* rng_state,
+                                 void* plan_block, float* gt_out, int32_t* gt_count_out, step_stream_t stream) {
+    if (N < 0 || Gmax < 0 || F <= 0 || NC < 0 || Wn < 1 || Hn < 1 || max_hw < 1) return STEP_E_SHAPE;
+    if (scale < 0 || scale > 2 || (switches & ~15)) return STEP_E_SHAPE;
+    if (Gmax > SEL_MAX_GT) return STEP_E_UNSUPPORTED;
+    const long long cap = augp_cap_words(max_hw);
+    if (cap > (1ll << 22)) return STEP_E_UNSUPPORTED;                          // (a patch's elements are addressed by 20 bits of Philox block)
+    if (16ll * N + 6ll * Gmax * N + 4 + (long long)N * Gmax * cap > 0x7fffffffLL || (long long)N * Gmax > 65535) return STEP_E_UNSUPPORTED;
+    if (!rng_state) return STEP_E_NULL;
+    if ((uintptr_t)rng_state & 7) return STEP_E_ALIGN;
+    if (N > 0) {
+        if (!src || !dims || !gt_count || !plan_block || !gt_count_out || (Gmax && (!gt_in || !gt_out))) return STEP_E_NULL;
+        if ((uintptr_t)plan_block & 15) return STEP_E_ALIGN;
+        AugPlanParams p;
+        p.src = src; p.dims = dims; p.gt_in = gt_in; p.gt_count = gt_count; p.rng = rng_state;
+        p.block = (unsigned char*)plan_block; p.gt_out = gt_out; p.gt_count_out = gt_count_out;
+        p.N = N; p.Gmax = Gmax; p.F = F; p.NC = NC; p.switches = switches; p.scale = scale; p.Wn = Wn; p.Hn = Hn; p.cap_words = (int)cap;
+        STEP_LAUNCH(augment_plan_kernel, dim3((unsigned)N), dim3(64), stream, p);
+    }
+    const double lo = scale == 2 ? -1.0 : 0.0, hi = scale == 0 ? 255.0 : 1.0;
+    const long long slots = (long long)N * Gmax;
+    const unsigned gx = slots > 0 ? (unsigned)((cap + 4 * 64 * AUGP_NOISE_RUN - 1) / (4 * 64 * AUGP_NOISE_RUN)) : 1u;
+    STEP_LAUNCH(augment_noise_kernel, dim3(gx, (unsigned)(slots > 0 ? slots : 1)), dim3(64), stream, (unsigned char*)plan_block, N, Gmax,
+                (int)cap, lo, hi, rng_state);                                  // (also for N == 0: the call counts)
+    return STEP_LAUNCH_CHECK();
+}
 
 extern "C" int step_anchor_sample(const float* gt, const int32_t* gt_count, int B, int Gmax, int F, int NC, int mid, float width, float height,
                                   int T, int pos_num, int neg_ratio, float pos_thresh, float neg_thresh, int mode, unsigned long long* rng_state,

@@ -278,7 +278,7 @@ class DeviceSelector:
     current stream, into static buffers -- nothing is copied to the host, nothing waits, so the calls can be recorded in a graph and the
     draws (step_amd.rng.DeviceRNG: one offset per select()) change from replay to replay.  temporal_mode "predict" only."""
 
-    def __init__(self, args, batch, budget, device, rng):
+    def __init__(self, args, batch, budget, device, rng, dynamic_gt=False):
         import torch
         if args.temporal_mode != "predict":
             raise NotImplementedError("DeviceSelector: temporal_mode %r stays on the host path (selection.train_select)" % (args.temporal_mode,))
@@ -290,6 +290,9 @@ class DeviceSelector:
         K, nc = self.batch * self.budget, args.num_classes
         self._layout = None                                      # (key, clip_of, most tubes of one clip) of the clip_start last seen
         self._gt_mid = None                                      # (key, the ground truths' middle-frame boxes, dense)
+        # dynamic_gt: the ground truths change UNDER the selector -- a kernel writes them through a raw pointer (step_augment_plan's gt_out),
+        # which bumps no tensor version -- so the middle-frame gather is issued on every select() (and recorded with it in a graph)
+        self.dynamic_gt = bool(dynamic_gt)
         self.out = {}
         for i in range(1, args.max_iter + 1):
             Tl = args.NUM_CHUNKS[i] * args.T
@@ -317,6 +320,8 @@ class DeviceSelector:
 
     def _gt_mid_boxes(self, gt, mid):
         """gt[:, :, mid, :4] as the dense tensor step_select_prepare reads; made again only when gt was replaced or written to"""
+        if self.dynamic_gt:
+            return gt[:, :, mid, :4].contiguous()
         key = self._key(gt) + (mid,)
         if self._gt_mid is None or self._gt_mid[0] != key:
             self._gt_mid = (key, gt[:, :, mid, :4].contiguous())

@@ -404,13 +404,21 @@ class C4SelectTrainStep(C4TrainStep):
     back as ONE graph ("select-one"; with a process group one graph up to the backward, the eager flat all-reduce, the update graph:
     "select-one-split").  The ragged step() keeps the host selection -- before capture(), step() of a selection="device" workload is
     therefore the HOST form; `selection_ran` names the selection of the last iteration, and a caller that wants the device selection
-    uncaptured calls step_padded() (train_step_amd.py --select-device --no-graph does)."""
+    uncaptured calls step_padded() (train_step_amd.py --select-device --no-graph does).
+
+    augment=<step_amd.DeviceTubeAugmentation> (opt-in, selection="device" only): the padded forms start from uint8 frames.  `stage`
+    [B,T,Hs,Ws,3] (src_size) is the iteration's input -- the captured one -- and the front begins with the planner, the noise fill and
+    step_clip_augment_u8, which write the clip `x` AND the ground truths the selector reads (`d_gt`, `d_gt_count`: the tubes the crop kept,
+    in pixels of the network's resolution), both from the same draws; `d_gt_in` / `d_gt_count_in` hold the loader's percent boxes.  Two
+    more offsets of the generator per iteration.  An augmentation built with rng=None draws from the workload's generator."""
 
     def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, tubes_per_clip=34, capturable=False, force_exchange=False, budget=None,
                  optimizer="adam", dropout=0.0, rng_seed=0, selection="host", grad_wire="fp32", wire_feedback=True, max_grad_norm=None,
-                 lr_schedule=None):
+                 lr_schedule=None, augment=None, src_size=(256, 340)):
         if selection not in ("host", "device"):
             raise ValueError("C4SelectTrainStep: selection is 'host' or 'device', got %r" % (selection,))
+        if augment is not None and selection != "device":
+            raise ValueError("C4SelectTrainStep: augment= needs selection='device' (the host selection reads ground truths the device cannot hand it)")
         super().__init__(dev, batch=batch, tubes_per_clip=5, seed=seed, max_iter=3, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
                          optimizer=optimizer, dropout=dropout, rng_seed=rng_seed, grad_wire=grad_wire, wire_feedback=wire_feedback,
                          max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
@@ -449,7 +457,7 @@ class C4SelectTrainStep(C4TrainStep):
                     host.append(torch.zeros(shape).pin_memory())
         if selection == "device":
             # everything the selection reads is resident: ground truths, the initial tubes (step 1's candidates), the padded slots' box
-            self.selector = DeviceSelector(a, batch, self.budget, dev, self.rng)
+            self.selector = DeviceSelector(a, batch, self.budget, dev, self.rng, dynamic_gt=augment is not None)
             self.d_gt = torch.from_numpy(np.stack(self.gt)).to(dev)
             self.d_gt_count = torch.full((batch,), self.gt[0].shape[0], dtype=torch.int32, device=dev)
             self.d_init = self.flat0[:, :, 1:].float().contiguous()
@@ -458,6 +466,20 @@ class C4SelectTrainStep(C4TrainStep):
             for i in range(1, a.max_iter + 1):
                 self.d_pad.append(torch.from_numpy(self.pad[i - 1]).to(dev))
                 self.s_flat[i - 1], self.s_tgt[i - 1], self.s_mask[i - 1], self.s_inv[i - 1] = self.selector.out[i][:4]
+        self.augment = augment
+        if augment is not None:
+            _, T, _, H, W = self.x.shape
+            if tuple(augment.size) != (W, H):
+                raise ValueError("C4SelectTrainStep: the augmentation resizes to %r, the clips are %r" % (tuple(augment.size), (W, H)))
+            if augment.rng is None:
+                augment.rng = self.rng
+            Hs, Ws = (int(v) for v in src_size)
+            g_ = torch.Generator().manual_seed(seed + 7)
+            self.stage = torch.randint(0, 256, (batch, T, Hs, Ws, 3), dtype=torch.uint8, generator=g_).to(dev)
+            whwh = torch.tensor([a.image_size[0], a.image_size[1]] * 2, dtype=torch.float32, device=dev)
+            self.d_gt_in = self.d_gt.clone()                     # what the loader reads: percent boxes (data/ava.py:283-296)
+            self.d_gt_in[..., :4] = (self.d_gt[..., :4] / whwh).clamp_(0.0, 1.0)
+            self.d_gt_count_in = self.d_gt_count.clone()
         self._gF = self._gB = None
         self._front = None
 
@@ -480,6 +502,8 @@ class C4SelectTrainStep(C4TrainStep):
     def step(self):
         if self._gF is not None:
             return self._replay()
+        if self.augment is not None:
+            raise RuntimeError("C4SelectTrainStep: the ragged step() selects on the host and knows no augmentation; use step_padded() or capture()")
         a = self.args
         cf = self.base(self.x)
         cx = self.ctx(cf)
@@ -511,6 +535,8 @@ class C4SelectTrainStep(C4TrainStep):
     def _front_part(self):
         """backbone + ContextNet (with gradients) and the no-grad, eval-mode inference over the first max_iter - 1 steps (train.py:266-272)"""
         a = self.args
+        if self.augment is not None:                            # decisions, noise, pixels and boxes of this iteration, from the same two offsets
+            self.augment.apply(self.stage, self.d_gt_in, self.d_gt_count_in, out=self.x, gt_out=self.d_gt, gt_count_out=self.d_gt_count)
         cf = self.base(self.x)
         cx = self.ctx(cf)
         for m in self.mods:

@@ -10,7 +10,13 @@ device events after a warm-up, the forms alternated round by round, the spread (
     is not installed here);
   * --train-runs K: train_step_amd.py --feed u8 against --feed u8 --augment as child processes, alternated, K runs each.
 
+--device-plan runs another leg INSTEAD: the decisions of the same batch made on the device (step_augment_plan: planner + noise fill, timed
+between device events) beside the host form (`.plan` per clip + pack + the copy of the block, wall time up to the copy's completion), rounds
+alternated; and with --train-runs K, train_step_amd.py --feed u8 --augment --select-device against --feed u8 --augment-device
+--select-device at 1 and 8 clips per GPU, child processes alternated, K runs each, each form's own spread beside its median.
+
     python tools/augment_bench.py [--out profiles/clip_augment_timing.txt] [--train-runs 3]
+    python tools/augment_bench.py --device-plan --train-runs 3 --out profiles/augment_plan_timing.txt
 """
 import argparse
 import ctypes
@@ -33,6 +39,7 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--train-runs", type=int, default=0)
 ap.add_argument("--train-iters", type=int, default=60)
 ap.add_argument("--np-clips", type=int, default=2, help="clips the numpy restatement is timed on")
+ap.add_argument("--device-plan", action="store_true", help="the step_augment_plan leg instead of the kernel forms (see above)")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "tools/augment_bench.py needs a ROCm device"
 dev = torch.device("cuda:0")
@@ -52,6 +59,99 @@ frames = torch.from_numpy(frames_np).to(dev)
 centre, half = rs.uniform(0.35, 0.65, (N, 2, 1, 2)), rs.uniform(0.1, 0.25, (N, 2, 1, 2))
 tubes = np.tile(np.concatenate([centre - half, centre + half], 3), (1, 1, T, 1)).astype(np.float32)
 out = torch.empty((N, T, 3, Ho, Wo), dtype=torch.bfloat16, device=dev)
+
+
+def timed(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def train_children(forms, extra, what):
+    """the launcher as child processes, the forms alternated run by run -> {form: [ms per iteration]}"""
+    runs = {f: [] for f in forms}
+    for r in range(a.train_runs):
+        for form in runs:
+            cmd = [sys.executable, os.path.join(ROOT, "train_step_amd.py"), "--iters", str(a.train_iters), "--log-every", "0"] + form.split() + extra
+            p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=400)
+            if p.returncode != 0:
+                say("train_step_amd.py %s failed (%d): %s" % (form, p.returncode, (p.stdout + p.stderr)[-800:]))
+                raise SystemExit(1)                                            # (nothing more is started after a failed child)
+            s = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{") and "summary" in l][-1]
+            runs[form].append(s["ms_per_iter"])
+    say("train_step_amd.py, %s, %d iterations per run, child processes alternated:" % (what, a.train_iters))
+    for form, v in runs.items():
+        say("  %-45s ms per iteration: %s  (median %.3f, spread %.3f)" % (form, ", ".join("%.3f" % x for x in v), float(np.median(v)), max(v) - min(v)))
+    return runs
+
+
+if a.device_plan:
+    from step_amd import DeviceRNG, DeviceTubeAugmentation
+    NC = 60
+    gt = np.zeros((N, 2, T, 4 + NC), np.float32)
+    gt[..., :4] = tubes
+    gt[..., 4 + 7] = 1
+    d_gt, d_cnt = torch.from_numpy(gt).to(dev), torch.full((N,), 2, dtype=torch.int32, device=dev)
+    host_aug = TubeAugmentation((Wo, Ho), do_flip=True, do_crop=True, do_photometric=True, do_erase=True, scale=2)
+    dev_aug = DeviceTubeAugmentation((Wo, Ho), do_flip=True, do_crop=True, do_photometric=True, do_erase=True, scale=2, rng=DeviceRNG(dev, seed=11))
+    g_out, c_out = torch.empty_like(d_gt), torch.empty_like(d_cnt)
+    clips = list(frames.unbind(0))
+    src, dims = None, None
+    np.random.seed(11)
+
+    def host_form():
+        """what `--augment` does per batch ahead of the one launch: plan per clip, pack, the copy of the block (waited for here)"""
+        t0 = time.perf_counter()
+        plans = [host_aug.plan((T, Hs, Ws), tubes[n])[0] for n in range(N)]
+        t1 = time.perf_counter()
+        _, block = host_aug.pack(frames, plans)
+        torch.cuda.synchronize()
+        return (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3, block.numel()
+
+    dev_aug.apply(frames, d_gt, d_cnt, out=out, gt_out=g_out, gt_count_out=c_out)          # builds the static block, uploads the frame addresses
+    block = dev_aug.last_block()
+    src, dims = dev_aug._frames[1], dev_aug._frames[2]
+
+    def plan_only():
+        _capi.check(L.step_augment_plan(_lib.dptr(src), _lib.dptr(dims), _lib.dptr(d_gt), _lib.dptr(d_cnt), N, 2, T, NC, 15, 2, Wo, Ho, Hs * Ws,
+                                        _lib.dptr(dev_aug.rng.state), _lib.dptr(block), _lib.dptr(g_out), _lib.dptr(c_out), _lib.stream_ptr(dev)),
+                    "step_augment_plan")
+
+    say("the augmentation's decisions for %d clips x %d frames of %dx%d, 2 tubes per clip, all four switches; %d rounds, alternated" % (N, T, Hs, Ws, a.rounds))
+    timed(plan_only, 10)
+    host_form()
+    dev_ms, host_plan, host_copy, blk_bytes = [], [], [], []
+    for _ in range(a.rounds):
+        dev_ms.append(timed(plan_only, a.launches))
+        hp = [host_form() for _ in range(5)]
+        host_plan.append(float(np.median([h[0] for h in hp])))
+        host_copy.append(float(np.median([h[1] for h in hp])))
+        blk_bytes.append(int(np.median([h[2] for h in hp])))
+    say("  device: step_augment_plan (planner + noise fill), median %.4f ms per batch (min %.4f .. max %.4f); static block %d bytes"
+        % (float(np.median(dev_ms)), min(dev_ms), max(dev_ms), block.numel()))
+    say("  host:   .plan x %d, median %.3f ms per batch (min %.3f .. max %.3f); pack + copy of the block, %.3f ms (min %.3f .. max %.3f; ~%d bytes)"
+        % (N, float(np.median(host_plan)), min(host_plan), max(host_plan), float(np.median(host_copy)), min(host_copy), max(host_copy), int(np.median(blk_bytes))))
+    res = {"device_plan_ms": dev_ms, "host_plan_ms": host_plan, "host_pack_copy_ms": host_copy}
+    if a.train_runs:
+        del frames, out
+        torch.cuda.empty_cache()
+        forms = ("--feed u8 --augment --select-device", "--feed u8 --augment-device --select-device")
+        for clips_per_gpu in (1, 8):
+            runs = train_children(forms, ["--global-batch", str(clips_per_gpu)], "%d clip(s) per GPU" % clips_per_gpu)
+            h, d = runs[forms[0]], runs[forms[1]]
+            say("  device-plan - host-plan = %+.3f ms per iteration; the host-plan form's own spread is %.3f ms"
+                % (float(np.median(d) - np.median(h)), max(h) - min(h)))
+            res["train_%d" % clips_per_gpu] = runs
+    say(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    raise SystemExit(0)
+
 forms = {
     "BaseTransform (resize only)": BaseTransform((Wo, Ho), scale=2),
     "geometry only (crop, mirror, erase)": TubeAugmentation((Wo, Ho), do_flip=True, do_crop=True, do_erase=True, scale=2),
@@ -80,16 +180,6 @@ nbytes = 1 << 30
 src, dst = torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.empty(nbytes, dtype=torch.uint8, device=dev)
 cus = torch.cuda.get_device_properties(dev).multi_processor_count
 stream = _lib.stream_ptr(dev)
-
-
-def timed(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
 
 
 def probe():

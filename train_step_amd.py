@@ -37,7 +37,10 @@ host -> device every iteration on a copy stream (`step_clip_from_u8` writes the 
 k + 1 runs under the replay of iteration k.  --feed u8 --augment keeps the frames at the SOURCE size (--src-size, default 256x340) and runs the
 reference's training transform on the device instead (`step_amd.TubeAugmentation`: a host plan per clip over synthetic tubes, drawn in
 the reference's RNG order, then one `step_clip_augment_u8` launch -- photometric distortion, crop, mirror, erase, resize to the
-network's resolution -- writes the captured step's input where `step_clip_from_u8` does without the flag).
+network's resolution -- writes the captured step's input where `step_clip_from_u8` does without the flag).  --feed u8 --augment-device
+--select-device makes the decisions on the device as well (`step_amd.DeviceTubeAugmentation`: `step_augment_plan` inside the captured
+iteration): the uint8 frames are the graph's input, the selection trains on the boxes that belong to the augmented pixels, and an
+iteration is the frame copy and one replay.
 """
 import argparse
 import json
@@ -102,7 +105,10 @@ def main():
     ap.add_argument("--augment", action="store_true",
                     help="--feed u8 only: uint8 frames at --src-size, the reference's TubeAugmentation (all four switches on, scripts/train_step.sh:55-58) "
                          "applied on the device by step_clip_augment_u8")
-    ap.add_argument("--src-size", default="256x340", help="--augment: HxW of the decoded source frames")
+    ap.add_argument("--augment-device", action="store_true",
+                    help="--feed u8 --select-device only: the augmentation's decisions, erase noise and transformed ground truths are made on the device "
+                         "too (step_augment_plan, draws from the generator of --rng-seed, not numpy's), inside the captured iteration")
+    ap.add_argument("--src-size", default="256x340", help="--augment / --augment-device: HxW of the decoded source frames")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
                     help="process-group backend (default: nccl = RCCL; gloo only to exercise the multi-rank program with ranks SHARING one GPU, "
@@ -116,6 +122,9 @@ def main():
         raise SystemExit("train_step_amd.py: --momentum must be positive (the workload's momentum buffer is allocated at construction)")
     if a.augment and a.feed != "u8":
         raise SystemExit("train_step_amd.py: --augment needs --feed u8 (the augmentation reads the uint8 frames)")
+    if a.augment_device and (a.feed != "u8" or not a.select_device or a.cls or a.augment):
+        raise SystemExit("train_step_amd.py: --augment-device needs --feed u8 --select-device (the device selection reads the boxes the planner "
+                         "writes), without --cls and --augment")
     if a.scheduler and a.lr_decay_every:
         raise SystemExit("train_step_amd.py: --scheduler and --lr-decay-every both write the learning rate; pick one")
     if a.clip_grad_norm is not None and not a.clip_grad_norm > 0:
@@ -162,6 +171,9 @@ def main():
         import numpy as np
         random.seed(1000 + rank)                                 # (the selection draws from the reference's two host RNG streams)
         np.random.seed(1000 + rank)
+        if a.augment_device:                                     # (400 x 400: the workload's clips; the generator is the workload's)
+            extra.update(augment=step_amd.DeviceTubeAugmentation((400, 400), do_flip=True, do_crop=True, do_photometric=True, do_erase=True, scale=2),
+                         src_size=tuple(int(v) for v in a.src_size.lower().split("x")))
         w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=capturable, optimizer=a.optimizer,
                                         dropout=a.dropout, rng_seed=a.rng_seed + rank, selection="device" if a.select_device else "host",
                                         grad_wire=a.grad_wire, wire_feedback=not a.no_wire_feedback, **extra)
@@ -185,7 +197,29 @@ def main():
             run()
 
     feed = None
-    if a.feed == "u8":
+    if a.augment_device:
+        # the uint8 frames are the captured iteration's input.  Host -> device on a copy stream into one of two landing buffers, under the
+        # replay of the iteration before (the prefetch of --feed u8 below); then ONE device copy into the workload's stage buffer and the
+        # replay, which plans, augments, selects and trains without the host
+        g_ = torch.Generator().manual_seed(999 + rank)
+        host = [torch.randint(0, 256, tuple(w.stage.shape), dtype=torch.uint8, generator=g_).pin_memory() for _ in range(2)]
+        landed = [torch.empty_like(w.stage) for _ in range(2)]
+        copy_stream = torch.cuda.Stream()
+        copied = [torch.cuda.Event() for _ in range(2)]
+        main_stream = torch.cuda.current_stream()
+
+        def prefetch(k):
+            with torch.cuda.stream(copy_stream):
+                landed[k % 2].copy_(host[k % 2], non_blocking=True)
+                copied[k % 2].record(copy_stream)
+
+        def feed(k):
+            main_stream.wait_event(copied[k % 2])
+            w.stage.copy_(landed[k % 2])
+            copy_stream.wait_stream(main_stream)
+            prefetch(k + 1)
+        prefetch(0)
+    elif a.feed == "u8":
         N, T, _, H, W = w.x.shape
         g_ = torch.Generator().manual_seed(999 + rank)
         Hs, Ws = (int(v) for v in a.src_size.lower().split("x")) if a.augment else (H, W)
@@ -260,7 +294,8 @@ def main():
                           "launch": ("hipGraph replay (%s)" % w.graph_mode) if w.graph is not None else "eager",
                           "gradient_exchange": _exchange_label(w, world),
                           "grad_wire": a.grad_wire, "exchange_bytes_per_step": w.opt.numel * (2 if a.grad_wire == "bf16" else 4), "param_checksum": checksum,
-                          "feed": a.feed + ("+augment" if a.augment else ""), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
+                          "feed": a.feed + ("+augment" if a.augment else "+augment-device" if a.augment_device else ""),
+                          **({"gt_kept": int(w.d_gt_count.sum().item())} if a.augment_device else {}), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
                           "dropout": a.dropout, "rng_offset": w.rng.offset(), **({"selection": w.selection_ran} if (a.select or a.cls) else {}),
                           **({"workload": "cls"} if a.cls else {}),
                           **({"clip_grad_norm": a.clip_grad_norm, "grad_norm": round(float(w.opt.grad_norm[0]), 6)} if a.clip_grad_norm is not None else {}),
