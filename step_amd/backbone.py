@@ -24,7 +24,8 @@ import weakref
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, wgrad
+from .wgrad import STATE as WGRAD, wgrad_into_grad, wgrad_sync    # (the public names of the weight-gradient path live here too)
 
 BN_EPS = 1e-5
 
@@ -83,53 +84,32 @@ class _ConvUnitFn(torch.autograd.Function):
             # 16-bit activations: the weight gradient runs on the 16-bit matrix instructions too (step_conv_wgrad16: 16x the
             # fp32 instruction's rate), reading the SAME 16-bit activation gradient as the data-gradient conv -- what
             # mixed-precision training back-propagates; no fp32 copy of the gradient is written
-            w16 = WGRAD16 and need_w and x.dtype != torch.float32 and y.dtype == x.dtype
+            w16 = need_w and WGRAD.use16(x, y.dtype)
             fused = ops.act_grad(y, gy, scale, ctx.relu, want_f32=need_w and not w16, want_act=need_x or need_res or w16) \
                 if (need_x or need_w or need_res) else (None, None)
             if fused is not None:
                 g32, gact = fused
-                if w16:
-                    g32 = gact
-
-                    def wgrad(x_, g_, cout_, k_, into=None):
-                        return ops.conv_wgrad16(x_, g_, cout_, k_, into=into)
-                else:
-                    wgrad = ops.conv_wgrad
-                target = _wgrad_target(ctx.unit, w_eff) if (need_w and WGRAD_INTO_GRAD and x.is_cuda and ops.PROFILE is None) else None
-                if target is not None:
-                    # opt-in (wgrad_into_grad()): the weight gradient is ACCUMULATED straight into the parameter's .grad (the
-                    # FlatAdam arena) on a side stream that nobody waits for until wgrad_sync() -- no clear, no autograd add, and the
-                    # latency-bound weight-gradient launches overlap the rest of the backward pass instead of sitting in its
-                    # critical path.  The fixed-order sums of the partial tiles queue up and run eight layers per launch
-                    # (_PEND_Q; the parameters are announced to the gradient exchange when their sum has been launched).
-                    _unit_wgrad(ctx.unit, w_eff, x, g32, k, _PEND_Q)
-                    if len(_PEND_Q) >= 8:
-                        _flush_wgrads(_PEND_Q, x.device)
-                    if need_res and g32 is gact:
-                        # the side stream is still READING this buffer while it is handed to autograd as the residual's
-                        # gradient: with a use count of one autograd would accumulate the other branch's gradient into it
-                        # IN PLACE on the main stream (input_buffer.cpp) -- a write/read race that perturbed the Bottleneck
-                        # conv3 weight gradients by ~1 % (found by tests/test_gpu_ddp.py).  A second reference makes autograd
-                        # add out of place; the list is dropped in wgrad_sync().
-                        _KEEP.append(gact)
-                    gx = _ConvUnitFn._dgrad(gact, w_eff, x.dtype, k, ctx.unit) if need_x else None
-                    return gx, None, None, None, (gact if need_res else None), None, None, None
-                if need_x and need_w and WGRAD_SIDE_STREAM and x.is_cuda and x.dtype == torch.float32 and ops.PROFILE is None:
-                    # the two gradients are independent: the weight gradient (many of them latency-bound launches that fill a
-                    # fraction of the chip) runs on a side stream beside the data-gradient conv.  Measured on the C4 step:
-                    # fp32 69.3 -> 65.0 ms; with 16-bit activations the data-gradient convs are too short to hide anything
-                    # and the extra stream bookkeeping costs 2 % (46.1 -> 47.2 ms), so 16-bit stays on one stream
-                    main = torch.cuda.current_stream(x.device)
-                    side = _side_streams(x.device)[0]
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        gw = wgrad(x, g32, w_eff.shape[0], k).to(w_eff.dtype)
+                g32 = gact if w16 else g32
+                route = WGRAD.route(ctx.unit, w_eff, x, beside=need_x) if need_w else None
+                if route is wgrad.BESIDE:
+                    gw = WGRAD.unit_wgrad(ctx.unit, w_eff, x, g32, k, route=route)
                     gx = _ConvUnitFn._dgrad(gact, w_eff, x.dtype, k, ctx.unit)
-                    main.wait_stream(side)
-                    gw.record_stream(main)
-                    return gx, gw, None, None, (gact if need_res else None), None, None, None
-                gx = _ConvUnitFn._dgrad(gact, w_eff, x.dtype, k, ctx.unit) if need_x else None
-                gw = wgrad(x, g32, w_eff.shape[0], k).to(w_eff.dtype) if need_w else None
+                    WGRAD.join(gw)
+                elif route is not None:
+                    # opt-in (wgrad_into_grad()): ACCUMULATED straight into the parameter's .grad on the side stream -- no clear, no autograd add,
+                    # off the critical path; the fixed-order sums of the partial tiles queue up and run eight layers per launch
+                    gw = WGRAD.unit_wgrad(ctx.unit, w_eff, x, g32, k, WGRAD.queue, route)
+                    if len(WGRAD.queue) >= 8:
+                        WGRAD.flush()
+                    if need_res and g32 is gact:
+                        # the side stream is still READING this buffer while it is handed to autograd as the residual's gradient: with a use count
+                        # of one autograd would accumulate the other branch's gradient into it IN PLACE on the main stream (input_buffer.cpp) -- a race
+                        # that perturbed conv3's weight gradients by ~1 % (tests/test_gpu_ddp.py).  A second reference (dropped in wgrad_sync()) prevents it
+                        WGRAD.keep.append(gact)
+                    gx = _ConvUnitFn._dgrad(gact, w_eff, x.dtype, k, ctx.unit) if need_x else None
+                else:
+                    gx = _ConvUnitFn._dgrad(gact, w_eff, x.dtype, k, ctx.unit) if need_x else None
+                    gw = WGRAD.unit_wgrad(ctx.unit, w_eff, x, g32, k) if need_w else None
                 return gx, gw, None, None, (gact if need_res else None), None, None, None
         g = gy.float()
         if ctx.relu:
@@ -211,7 +191,7 @@ def _repack_all(dtype, device):
     -- every side stream forks from the main one (wait_stream) after this point, so a launch on the main stream is."""
     if device.type == "cuda":
         cur = torch.cuda.current_stream(device)
-        if any(cur == s for s in _SIDE.get((device.type, device.index if device.index is not None else torch.cuda.current_device()), ())):
+        if any(cur == s for s in WGRAD.streams.get((device.type, device.index if device.index is not None else torch.cuda.current_device()), ())):
             return False
     entries, owners = [], []
     for u in list(_UNITS):
@@ -567,13 +547,13 @@ class _StemFn(torch.autograd.Function):
         if not ctx.relu and scale is None:                             # the raw conv (batch-statistics BN follows): gy IS the conv's gradient
             gw = None
             if ctx.needs_input_grad[1]:
-                if WGRAD16 and x.dtype != torch.float32 and gy.dtype == x.dtype:
+                if wgrad.WGRAD16 and x.dtype != torch.float32 and gy.dtype == x.dtype:
                     gw = ops.stem_wgrad16(x, gy.contiguous(), w.shape[0])
                 if gw is None:
                     gw = ops.stem_wgrad(x.contiguous(), gy.float(), w.shape[0])
                 gw = gw.to(w.dtype)
             return None, gw, None, None, None, None, None
-        if WGRAD16 and ctx.needs_input_grad[1] and not (ctx.needs_input_grad[2] or ctx.needs_input_grad[3]) and y.dtype != torch.float32 \
+        if wgrad.WGRAD16 and ctx.needs_input_grad[1] and not (ctx.needs_input_grad[2] or ctx.needs_input_grad[3]) and y.dtype != torch.float32 \
                 and x.dtype == y.dtype:
             # frozen affine, 16-bit activations: ReLU mask x scale in ONE HIP pass (16-bit result), then the weight gradient on the
             # 16-bit matrix instructions reading clip and gradient once (step_stem_wgrad16) -- as the other units' step_conv_wgrad16
@@ -668,69 +648,6 @@ class _FusedPointwise:
         return None
 
 
-def _unit_wgrad(unit, w_eff, x, g, k, pend=None):
-    """Weight gradient of one conv unit from its input x and the gradient g of its conv output (both channels-last, g possibly a channel
-    slice): inside wgrad_into_grad() accumulated straight into the parameter's .grad on the side stream (returns None), else returned.
-    pend (a list): the fixed-order sum of the partial tiles is deferred and described there -- _flush_wgrads() runs the sums of a whole
-    block as one launch (and only then announces the parameters to the gradient exchange)."""
-    w16 = WGRAD16 and x.dtype != torch.float32 and g.dtype == x.dtype
-    if not w16 and g.dtype != torch.float32:
-        g = g.float()
-    fn = ops.conv_wgrad16 if w16 else ops.conv_wgrad
-    cout = w_eff.shape[0]
-    target = _wgrad_target(unit, w_eff) if (WGRAD_INTO_GRAD and x.is_cuda and ops.PROFILE is None) else None
-    defer = pend is not None and ops.PROFILE is None and (ops.WGRAD16_WS if w16 else ops.WGRAD_WS)
-    if target is None:
-        if defer:
-            dw, item, ws = ops.conv_wgrad_partial(x, g, cout, k)
-            pend.append((item, ws, None, None, x.device))
-            assert dw.dtype == w_eff.dtype                       # (fp32 master weights: a cast here would read the gradient before its sum has run)
-            return dw
-        return fn(x, g, cout, k).to(w_eff.dtype)
-    main = torch.cuda.current_stream(x.device)
-    side = _side_streams(x.device)[0]
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        if defer:
-            _, item, ws = ops.conv_wgrad_partial(x, g, cout, k, into=target)
-            pend.append((item, ws, unit, side, x.device))
-            if GRAD_DEFER is not None:
-                GRAD_DEFER(unit.weight_fn())
-        else:
-            fn(x, g, cout, k, into=target)
-    x.record_stream(side)
-    g.record_stream(side)
-    _PENDING[0] = True
-    if GRAD_READY is not None and not defer:                     # this parameter bypasses autograd's accumulate hook
-        GRAD_READY(unit.weight_fn(), side)
-    return None
-
-
-def _flush_wgrads(pend, device):
-    """The deferred sums collected by _unit_wgrad(pend=...), one launch (per eight layers), on the stream their partial tiles were
-    written on; then the gradient exchange hears about the parameters."""
-    if not pend:
-        return
-    # One launch PER STREAM the partial tiles were written on (None = the current stream, whose dw autograd reads next: its sum must be
-    # ordered on that stream, not on the side stream of a neighbour that happens to have a dense fp32 .grad).
-    parts = {}
-    for e in pend:
-        parts.setdefault((e[4], e[3]), []).append(e)
-    for (dev, side), es in parts.items():
-        items = [e[0] for e in es]
-        if side is None:
-            ops.wgrad_reduce_group(items, dev if dev is not None else device)
-            continue
-        with torch.cuda.stream(side):
-            ops.wgrad_reduce_group(items, dev if dev is not None else device)
-        for _, ws, unit, _, _ in es:
-            if ws is not None:
-                ws.record_stream(side)
-            if GRAD_READY is not None and unit is not None:
-                GRAD_READY(unit.weight_fn(), side)
-    del pend[:]
-
-
 class _MixedTrainFn(torch.autograd.Function):
     """One autograd node for a whole Inception block in training (eval-mode BN with a frozen affine: every shipped configuration).
     Forward: the block's six units write channel slices of one output buffer and one bottleneck buffer (no torch.cat), the two 3x3x3
@@ -772,13 +689,13 @@ class _MixedTrainFn(torch.autograd.Function):
         gws = [None] * 6
         pend = []                                                # the six fixed-order sums of partial tiles run as ONE launch at the end
         if need_w[0]:
-            gws[0] = _unit_wgrad(u0, w0, x, g0, (1, 1, 1), pend)
+            gws[0] = WGRAD.unit_wgrad(u0, w0, x, g0, (1, 1, 1), pend)
         if need_w[2]:
-            gws[2] = _unit_wgrad(u1b, w1b, t[..., :oc[1]], g1, (3, 3, 3), pend)
+            gws[2] = WGRAD.unit_wgrad(u1b, w1b, t[..., :oc[1]], g1, (3, 3, 3), pend)
         if need_w[4]:
-            gws[4] = _unit_wgrad(u2b, w2b, t[..., oc[1]:], g2, (3, 3, 3), pend)
+            gws[4] = WGRAD.unit_wgrad(u2b, w2b, t[..., oc[1]:], g2, (3, 3, 3), pend)
         if need_w[5]:
-            gws[5] = _unit_wgrad(u3, w3, p, g3, (1, 1, 1), pend)
+            gws[5] = WGRAD.unit_wgrad(u3, w3, p, g3, (1, 1, 1), pend)
         # 2. the two 3x3x3 data gradients into one bottleneck-gradient buffer (one grouped launch where the library merges them)
         gt = torch.empty(t.shape, dtype=t.dtype, device=t.device)
         dt_ = out.dtype
@@ -788,10 +705,10 @@ class _MixedTrainFn(torch.autograd.Function):
         # 3. through the two bottleneck ReLUs / BN scales in one pass
         _, gta = ops.act_grad(t, gt, m._train_scales(out.device)[1], True, want_f32=False, want_act=True)
         if need_w[1]:
-            gws[1] = _unit_wgrad(u1a, w1a, x, gta[..., :oc[1]], (1, 1, 1), pend)
+            gws[1] = WGRAD.unit_wgrad(u1a, w1a, x, gta[..., :oc[1]], (1, 1, 1), pend)
         if need_w[3]:
-            gws[3] = _unit_wgrad(u2a, w2a, x, gta[..., oc[1]:], (1, 1, 1), pend)
-        _flush_wgrads(pend, x.device)
+            gws[3] = WGRAD.unit_wgrad(u2a, w2a, x, gta[..., oc[1]:], (1, 1, 1), pend)
+        WGRAD.flush(pend)
         gx = None
         if need_x:
             cin = x.shape[-1]
@@ -924,7 +841,7 @@ class Mixed(nn.Module):
         # hipGraph capture these become parallel graph branches).  Most of these launches do not fill
         # 256 CUs on the 28x28 / 14x14 maps, so they overlap instead of queueing behind each other.
         main = torch.cuda.current_stream(x.device)
-        s1, s2 = _side_streams(x.device)
+        s1, s2 = WGRAD.side_streams(x.device)
         if BRANCH_STREAMS == 1:
             s1 = s2                                        # both side branches on ONE side stream (one fork, one join)
         s2.wait_stream(main)
@@ -951,67 +868,6 @@ class Mixed(nn.Module):
         p = pool(x)
         unit(p, out=out)
         return p
-
-
-WGRAD16 = True           # 16-bit activations: weight gradients on the 16-bit MFMA (step_conv_wgrad16)
-WGRAD_INTO_GRAD = False        # see wgrad_into_grad()
-GRAD_READY = None              # step_amd.dist.BucketedReducer.ready while a backward pass is being overlapped with the exchange
-GRAD_DEFER = None              # ... its defer(): this parameter's gradient will be announced by _flush_wgrads, not by autograd's hook
-_PENDING = [False]
-_PEND_Q = []                   # deferred weight-gradient sums of the per-unit nodes (flushed eight at a time and in wgrad_sync())
-_KEEP = []                     # tensors the side stream reads that autograd must not modify in place (until wgrad_sync())
-
-
-def _wgrad_target(unit, w_eff):
-    """The dense fp32 .grad of the unit's weight parameter when the effective weight IS that parameter (no channel slice /
-    permutation) and a gradient buffer exists; else None (the caller returns the gradient through autograd)."""
-    if unit.cin_slice is not None or unit.perm is not None:
-        return None
-    w = unit.weight_fn()
-    g = w.grad
-    if g is None or g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != w_eff.numel() or not w.requires_grad:
-        return None
-    return g
-
-
-class wgrad_into_grad:
-    """Context manager for a training step whose optimizer owns persistent gradient buffers (step_amd.optim.FlatAdam):
-    inside it the conv units add their weight gradients into `weight.grad` directly, asynchronously on a side stream.
-    Leaving the context (or calling wgrad_sync()) makes the current stream wait for them.  Not for torch.autograd.grad()
-    or double backward: the weight gradient bypasses autograd."""
-
-    def __enter__(self):
-        global WGRAD_INTO_GRAD
-        if not WGRAD_INTO_GRAD:
-            wgrad_sync()                                         # nothing of an earlier backward may ride into this step's sums
-        self.prev, WGRAD_INTO_GRAD = WGRAD_INTO_GRAD, True
-        return self
-
-    def __exit__(self, *exc):
-        global WGRAD_INTO_GRAD
-        WGRAD_INTO_GRAD = self.prev
-        if exc and exc[0] is not None:
-            # backward raised mid-way: the queued partial sums describe a gradient nobody will use -- drop them instead of adding them
-            # to the arena at the next flush (their workspaces die with the list); the side stream is still joined.  The gradients of
-            # this step are UNDEFINED after a failed backward (some weight gradients are in the arena, the dropped ones are not): the
-            # announcement hooks are cleared so that a BucketedReducer armed for this step does not wait for parameters that will never
-            # report (its next begin() re-arms it), and the caller must zero the arena (opt.zero_grad()) before the next backward.
-            global GRAD_READY, GRAD_DEFER
-            del _PEND_Q[:]
-            GRAD_READY = GRAD_DEFER = None
-        wgrad_sync()
-        return False
-
-
-def wgrad_sync():
-    """Order every weight gradient launched on the side stream before what the current stream does next."""
-    if _PEND_Q:
-        _flush_wgrads(_PEND_Q, _PEND_Q[0][4])
-    if _PENDING[0] and torch.cuda.is_available():
-        for dev_key, streams in list(_SIDE.items()):
-            torch.cuda.current_stream(torch.device(dev_key[0], dev_key[1])).wait_stream(streams[0])
-        _PENDING[0] = False
-    del _KEEP[:]
 
 
 POOL_WITH_POINTWISE = True     # inference: an Inception block's max pool and its fused 1x1x1 triple as one launch where the library has the form
@@ -1075,15 +931,6 @@ def _pointwise_then_3x3x3(a, b, x, pool=None):
 
 
 BRANCH_STREAMS = 0       # Inception blocks (inference path): 0 = one stream + the grouped 3x3x3 launch (default since round 3, see Mixed.forward); 1 / 2 = side branches on 1 / 2 side streams
-WGRAD_SIDE_STREAM = True # training: weight gradient beside the data gradient
-_SIDE = {}
-
-
-def _side_streams(device):
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-    if key not in _SIDE:
-        _SIDE[key] = (torch.cuda.Stream(device), torch.cuda.Stream(device))
-    return _SIDE[key]
 
 
 def build_base_i3d(kinetics_pretrain=None, freeze_affine=True):

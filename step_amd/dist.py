@@ -21,7 +21,7 @@ import time
 import torch
 import torch.distributed as dist
 
-from . import _capi, _lib
+from . import _capi, _lib, wgrad
 
 
 def init(backend=None):
@@ -233,14 +233,10 @@ class BucketedReducer:
         for h in self._hooks:
             h.remove()
         self._hooks = []
-        from . import backbone
-        if backbone.GRAD_READY is self.ready:
-            backbone.GRAD_READY = None
-            backbone.GRAD_DEFER = None
+        wgrad.STATE.disarm(self.ready)
 
     def begin(self, weight=None):
         """Arm for one backward pass.  weight: optional per-rank scalar as in allreduce_flat()."""
-        from . import backbone
         self.pending = [c for _, _, c in self.buckets]
         self.seen = set()
         self.deferred = set()                                    # parameters whose gradient a conv unit will announce itself, later (see defer())
@@ -259,8 +255,7 @@ class BucketedReducer:
                 dist.all_reduce(wsum)
                 self.weight = float(weight)
                 self.factor = 1.0 / float(wsum.item())
-        backbone.GRAD_READY = self.ready
-        backbone.GRAD_DEFER = self.defer
+        wgrad.STATE.arm(self.ready, self.defer)
         self._armed = True
 
     def _autograd_ready(self, p):
@@ -282,7 +277,7 @@ class BucketedReducer:
 
     def defer(self, p):
         """A conv unit accumulates `p`'s gradient itself and its last kernel (the grouped fixed-order sum of partial tiles,
-        backbone._flush_wgrads) is launched LATER than the unit's autograd node returns: autograd's hook, which fires for the leaf even
+        wgrad.STATE.flush) is launched LATER than the unit's autograd node returns: autograd's hook, which fires for the leaf even
         though no gradient arrives through it, must not count the parameter -- the unit calls ready() when the sum has been launched."""
         if self._armed:
             self.deferred.add(id(p))
@@ -338,14 +333,12 @@ class BucketedReducer:
     def finish(self):
         """Issue the buckets backward did not complete (same order on every rank), wait for all of them, return the
         factor that turns the sums into the average (for FlatAdam.step(grad_scale=...))."""
-        from . import backbone
         if self.cuda:
             # queued weight-gradient sums are launched (and announce their parameters: buckets may still leave here); late
             # side-stream accumulations are ordered before the main stream
-            backbone.wgrad_sync()
+            wgrad.STATE.sync()
         self._armed = False
-        backbone.GRAD_READY = None
-        backbone.GRAD_DEFER = None
+        wgrad.STATE.disarm()
         while self.next >= 0:
             self._issue(self.next)
             self.next -= 1

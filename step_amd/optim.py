@@ -18,7 +18,7 @@ Both share the arena layer `_FlatOptimizer`, which is all that step_amd.dist and
 """
 import torch
 
-from . import _capi, _lib
+from . import _capi, _lib, wgrad
 
 _ALIGN = 64          # elements (256 B): every tensor starts on its own cache line; segment ends stay multiples of 4
 
@@ -206,8 +206,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        from .backbone import wgrad_sync
-        wgrad_sync()                                             # weight gradients still in flight on the side stream
+        wgrad.STATE.sync()                                       # weight gradients still in flight on the side stream
         self._gather_stray_grads()
         self._refresh_tables()
         if scaler is not None and not self.capturable:

@@ -8,7 +8,7 @@ import torch
 
 from . import BaseNet, ContextNet, ROINet, TwoBranchNet
 from . import rng as srng
-from . import dist as sdist
+from . import dist as sdist, wgrad
 from .driver import GraphedInference, inference, inference_flat, postprocess
 from .backbone import wgrad_into_grad
 from .optim import FlatAdam, FlatSGD
@@ -362,9 +362,8 @@ class C4TrainStep:
                 warnings.warn("C4TrainStep.capture: recording the gradient exchange failed (%s); falling back to the split form" % (str(e).splitlines()[0],))
                 torch.cuda.synchronize(dev)
                 self.reducer._armed = False
-                from . import backbone as _bb
-                _bb.GRAD_READY = _bb.GRAD_DEFER = None
-                _bb.wgrad_sync()
+                wgrad.STATE.disarm()
+                wgrad.STATE.sync()
                 self.opt.zero_grad()
                 mode = "split"
         if mode == "split":

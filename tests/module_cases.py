@@ -976,8 +976,8 @@ def case_flat_adam_matches_torch(dev, golden):
 
 def case_wgrad_into_and_targets(dev, golden):
     """ops.conv_wgrad(into=...) adds to what the buffer holds (the kernel's accumulate mode) and refuses buffers of the wrong
-    kind; backbone._wgrad_target only offers a parameter's .grad when the effective weight IS the parameter."""
-    from step_amd import backbone, ops
+    kind; wgrad.STATE.target only offers a parameter's .grad when the effective weight IS the parameter."""
+    from step_amd import backbone, ops, wgrad
     torch.manual_seed(2)
     x = torch.randn(1, 2, 5, 6, 8).to(dev)
     gy = torch.randn(1, 2, 5, 6, 16).to(dev)
@@ -995,19 +995,19 @@ def case_wgrad_into_and_targets(dev, golden):
     conv = torch.nn.Conv3d(8, 16, (1, 3, 3), bias=False).to(dev)
     plain = backbone.ConvUnit(conv, lambda m: m.weight, (1, 3, 3))
     sliced = backbone.ConvUnit(conv, lambda m: m.weight, (1, 3, 3), cin_slice=(0, 4))
-    assert backbone._wgrad_target(plain, plain.effective_weight()) is None          # no gradient buffer yet
+    assert wgrad.STATE.target(plain, plain.effective_weight()) is None          # no gradient buffer yet
     conv.weight.grad = torch.zeros_like(conv.weight)
-    assert backbone._wgrad_target(plain, plain.effective_weight()) is conv.weight.grad
-    assert backbone._wgrad_target(sliced, sliced.effective_weight()) is None        # a channel slice goes through autograd
+    assert wgrad.STATE.target(plain, plain.effective_weight()) is conv.weight.grad
+    assert wgrad.STATE.target(sliced, sliced.effective_weight()) is None        # a channel slice goes through autograd
     conv.weight.requires_grad_(False)
-    assert backbone._wgrad_target(plain, plain.effective_weight()) is None
+    assert wgrad.STATE.target(plain, plain.effective_weight()) is None
 
 
 def case_wgrad_into_grad_matches_autograd(dev, golden):
     """backbone.wgrad_into_grad(): weight gradients accumulated straight into .grad on a side stream equal the ones autograd
     delivers (same kernels, same operands; only the fp32 atomics' order differs), they ADD to what .grad already holds, and
     parameters the shortcut does not cover (biases, permuted / sliced weights) still arrive through autograd."""
-    from step_amd import backbone
+    from step_amd import backbone, wgrad
     g = golden("head_golden")
     net = fill(step_amd.TwoBranchNet(cfg()), "det0.").to(dev)
     net.set_device(dev)
@@ -1034,7 +1034,34 @@ def case_wgrad_into_grad_matches_autograd(dev, golden):
         a, b = np_(p.grad).astype(np.float64) - 1.0, np_(ref[k]).astype(np.float64)
         e = float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
         assert e < 1e-4, (k, e)
-    assert not backbone._PENDING[0] and not backbone.WGRAD_INTO_GRAD
+    assert not wgrad.STATE.in_flight and not wgrad.STATE.into_grad
+
+
+def case_wgrad_side_stream_bit_identical(dev, golden):
+    """The fp32 per-unit node with its weight gradient on the side stream beside the data gradient (wgrad.WGRAD_SIDE_STREAM, the
+    default on a GPU) against both on one stream: the same kernels on the same operands, the partial tiles summed in a fixed order
+    (ops.WGRAD_WS) -- bit-identical gradients.  The route is taken exactly where it exists (never on the interpreter)."""
+    from step_amd import backbone, wgrad
+    torch.manual_seed(3)
+    conv = torch.nn.Conv3d(8, 16, (3, 3, 3), bias=False).to(dev)
+    unit = backbone.ConvUnit(conv, lambda m: m.weight, (3, 3, 3))
+    x0, gy = torch.randn(1, 2, 6, 6, 8).to(dev), torch.randn(1, 2, 6, 6, 16).to(dev)
+    got, joins = {}, []
+    keep, join = wgrad.WGRAD_SIDE_STREAM, wgrad.STATE.join
+    wgrad.STATE.join = lambda gw: (joins.append(wgrad.WGRAD_SIDE_STREAM), join(gw))
+    try:
+        for side in (True, False):
+            wgrad.WGRAD_SIDE_STREAM = side
+            x = x0.clone().requires_grad_(True)
+            conv.weight.grad = None
+            unit(x).backward(gy)
+            got[side] = (x.grad, conv.weight.grad)
+    finally:
+        wgrad.WGRAD_SIDE_STREAM = keep
+        del wgrad.STATE.join
+    assert joins == ([True] if x0.is_cuda else []), joins
+    for a, b in zip(got[True], got[False]):
+        assert a.dtype == torch.float32 and bool(a.abs().sum() > 0) and torch.equal(a, b)
 
 
 def case_train_select_device_front_end(dev, golden):
@@ -1315,7 +1342,7 @@ def case_stem_backward_16bit(dev, golden):
     only difference is the bf16 rounding of the activation gradient (< 5e-3); both follow the fp32 run to the bf16 forward's own
     error (quantized clip, ReLU decisions: a few per cent).  A clip width outside the 16-bit kernel's contract (W % 8) takes the
     fp32-MFMA kernel."""
-    from step_amd import backbone, ops
+    from step_amd import ops, wgrad
     for shape in ((2, 6, 3, 24, 40), (1, 5, 3, 18, 20)):
         grads = {}
         for tag, dt, w16 in (("f32", torch.float32, True), ("new", torch.bfloat16, True), ("old", torch.bfloat16, False)):
@@ -1325,19 +1352,19 @@ def case_stem_backward_16bit(dev, golden):
             assert not stem.batch3d.weight.requires_grad
             x = R.fill_tensor("golden.stem16.images", shape, "image").to(dev).to(dt)
             used = []
-            orig, keep = ops.stem_wgrad16, backbone.WGRAD16
+            orig, keep = ops.stem_wgrad16, wgrad.WGRAD16
 
             def spy(*a, **k):
                 r = orig(*a, **k)
                 used.append(r is not None)
                 return r
-            ops.stem_wgrad16, backbone.WGRAD16 = spy, w16
+            ops.stem_wgrad16, wgrad.WGRAD16 = spy, w16
             try:
                 y = stem(x)
                 wgt = R.fill_tensor("golden.stem16.w", tuple(y.shape), "feat").to(dev)
                 (y.float() * wgt).sum().backward()
             finally:
-                ops.stem_wgrad16, backbone.WGRAD16 = orig, keep
+                ops.stem_wgrad16, wgrad.WGRAD16 = orig, keep
             assert used == ([shape[-1] % 8 == 0] if tag == "new" else []), (shape, tag, used)
             grads[tag] = np_(stem.conv3d.weight.grad).astype(np.float64)
         b = grads["f32"]
@@ -1679,7 +1706,7 @@ def case_fused_forms_refused_fall_back(dev, golden):
 CPU_CASES = ["case_state_dict_contract", "case_mixed_golden", "case_basenet_c1_golden", "case_context_golden",
              "case_twobranch_T3_and_losses_golden", "case_roinet_layouts", "case_training_step_matches_torch_autograd",
              "case_training_step_generic_weights",
-             "case_flat_adam_matches_torch", "case_wgrad_into_and_targets", "case_twobranch_variants_golden",
+             "case_flat_adam_matches_torch", "case_wgrad_into_and_targets", "case_wgrad_side_stream_bit_identical", "case_twobranch_variants_golden",
              "case_reg_unit_pack_follows_weight_updates", "case_basenet_backward_matches_oracle_autograd",
              "case_contextnet_backward_matches_oracle_autograd", "case_basenet_batch_statistics_bn_golden", "case_postprocess_golden",
              "case_batched_repack_follows_weight_updates", "case_stem_backward_16bit",

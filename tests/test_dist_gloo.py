@@ -26,7 +26,7 @@ def _model():
 
 class _DirectLinear(torch.autograd.Function):
     """Mimics the conv units under backbone.wgrad_into_grad(): the weight gradient is ADDED to weight.grad by the op itself,
-    announced through backbone.GRAD_READY, and autograd gets None for it (its post-accumulate hook still fires for that
+    announced through wgrad.STATE.ready, and autograd gets None for it (its post-accumulate hook still fires for that
     parameter -- with an undefined gradient -- which the reducer must not count as a second gradient)."""
 
     @staticmethod
@@ -36,11 +36,11 @@ class _DirectLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from step_amd import backbone
+        from step_amd import wgrad
         x, w = ctx.saved_tensors
         w.grad.add_(g.t() @ x)
-        if backbone.GRAD_READY is not None:
-            backbone.GRAD_READY(w, None)
+        if wgrad.STATE.ready is not None:
+            wgrad.STATE.ready(w, None)
         return g @ w, None
 
 

@@ -287,3 +287,49 @@ def test_write_padded_slots_fills_every_element():
 
     with pytest.raises(RuntimeError, match="Workload: 5 tubes selected for one clip, budget 4"):
         write((1,), (1, 2, 3, 4, 5))
+
+
+# ---------------------------------------------------------------- the weight-gradient state's protocol (step_amd.wgrad)
+def test_wgrad_disarm_only_clears_the_named_exchange():
+    from step_amd.wgrad import STATE
+    r1, d1, r2 = (lambda p, s=None: None), (lambda p: None), (lambda p, s=None: None)
+    try:
+        STATE.arm(r1, d1)
+        STATE.disarm(r2)                               # another reducer's close() leaves the armed one alone
+        assert STATE.ready is r1 and STATE.defer is d1
+        STATE.disarm(r1)
+        assert STATE.ready is None and STATE.defer is None
+        STATE.arm(r1, d1)
+        STATE.disarm()
+        assert STATE.ready is None and STATE.defer is None
+    finally:
+        STATE.disarm()
+
+
+def test_wgrad_into_grad_nests_and_restores():
+    from step_amd.backbone import wgrad_into_grad
+    from step_amd.wgrad import STATE
+    assert not STATE.into_grad
+    with wgrad_into_grad():
+        assert STATE.into_grad
+        with wgrad_into_grad():
+            assert STATE.into_grad
+        assert STATE.into_grad                         # the inner exit restores the OUTER value
+    assert not STATE.into_grad and not STATE.in_flight
+
+
+def test_wgrad_into_grad_failed_backward_drops_queue_and_disarms():
+    from step_amd.backbone import wgrad_into_grad
+    from step_amd.wgrad import STATE, Pending
+    r1, d1 = (lambda p, s=None: None), (lambda p: None)
+    try:
+        with pytest.raises(ZeroDivisionError):
+            with wgrad_into_grad():
+                STATE.arm(r1, d1)
+                STATE.queue.append(Pending(item=None, ws=None, unit=None, stream=None, device=None))
+                1 / 0
+        assert STATE.queue == [] and STATE.ready is None and STATE.defer is None
+        assert not STATE.into_grad and not STATE.in_flight
+    finally:
+        del STATE.queue[:]
+        STATE.disarm()
