@@ -977,6 +977,20 @@ STEP_API int step_select_train(const float* cand, const float* cand_first, const
                                int sampling, int budget, float* sel, float* tgt, float* mask, float* inv, int32_t* counts,
                                step_stream_t stream);
 
+/* step_select_train over PADDED clips: step_select_train's arguments plus clip_count [B] int32 (device memory, before the stream).  Clip b
+ * owns the rows from clip_start[b], of length min(max(clip_count[b], 0), clip_start[b+1] - clip_start[b], Amax): the first clip_count[b]
+ * slots of its segment are real tubes, the others padding that no step of the rule sees.  Draw indices, the offset and every output are
+ * those of step_select_train on the compacted inputs (the real rows alone, clip_start their running sum), bit for bit; clip_count == NULL
+ * IS step_select_train.  step_select_prepare keeps running over all slots: nobody reads what it computes for a padded one.  The slot
+ * convention (a clip owns K slots, the first count[b] real, the others the whole frame (0, 0, W, H), count never read by the host) is
+ * step_augment_plan_tubes' and step_detect_nms' tube_count's. */
+STEP_API int step_select_train_counted(const float* cand, const float* cand_first, const float* cand_last, const float* score,
+                                       const float* iou, int N, int Tc, int Tw, int NC, const int32_t* clip_start, int B, int Amax,
+                                       const float* gt, const int32_t* gt_count, int Gmax, int F, const float* pad_tubes,
+                                       unsigned long long* rng_state, int mid, int before, int after, int topk, float cls_thresh,
+                                       float reg_thresh, int max_pos_num, int neg_ratio, int sampling, int budget, float* sel, float* tgt,
+                                       float* mask, float* inv, int32_t* counts, const int32_t* clip_count, step_stream_t stream);
+
 /* Classification pre-training (train_cls.py, stage 1 of the two-stage recipe): the boxes the loader samples around every ground-truth box,
  * data/ava_cls.py:200-261 sample_anchors inside __getitem__ -- up to 100 sequential trials per box, each a jaccard_numpy call -- for all
  * clips of a batch in ONE launch, with the draws taken from the device-side generator of step_dropout_forward.  Same rule as the reference,
@@ -1090,7 +1104,7 @@ STEP_API int step_anchor_sample(const float* gt, const int32_t* gt_count, int B,
  * Deviations from the host form.  (1) Other draws: the stream above, not numpy's.  (2) Bounded loops: the crop gives up after 16 rounds and
  * keeps the whole frame; get_region gives up after 64 trials and erases nothing for that box (the reference loops `while True`).  With
  * addressed draws the trials of a round are evaluated side by side and the first accepted one is taken, which is the sequential rule's
- * result.  (3) Proposals are not transformed: the device form serves the anchor-grid recipe.
+ * result.  (Proposals: step_augment_plan_tubes below.)
  *
  * Errors: negative N / Gmax / NC, F < 1, Wn / Hn / max_hw < 1, scale outside 0..2, unknown switch bits -> STEP_E_SHAPE; Gmax > 64 ->
  * STEP_E_UNSUPPORTED (step_select_train's limit for the same buffers); rng_state NULL, or with N > 0 any other pointer NULL -> STEP_E_NULL;
@@ -1105,6 +1119,37 @@ STEP_API size_t step_augment_plan_bytes(int N, int Gmax, long long max_hw, int* 
 STEP_API int step_augment_plan(const unsigned long long* src, const int32_t* dims, const float* gt_in, const int32_t* gt_count, int N,
                                int Gmax, int F, int NC, int switches, int scale, int Wn, int Hn, long long max_hw,
                                unsigned long long* rng_state, void* plan_block, float* gt_out, int32_t* gt_count_out, step_stream_t stream);
+
+/* step_augment_plan that also transforms the clip's detector PROPOSALS (data/augmentations.py:412-423,463-483 with data/ava.py:342-362):
+ * step_augment_plan's arguments, then (before the stream) tubes_in [N,Pmax,Tp,4] fp32 percent boxes, tube_count [N] int32, Pmax, Tp, fill
+ * [n_fill,4] fp32 percent boxes (may be NULL), n_fill, tubes_out [N,Pmax,Tp,4] fp32, tube_count_out [N] int32.  The same two launches and
+ * the same two offsets: the plan block, gt_out, gt_count_out and the offset's advance are step_augment_plan's at the same state, and
+ * tubes_in == NULL IS step_augment_plan.  The planner's wavefront for clip n transforms the proposals once crop and mirror are decided,
+ * while the accepted trial's drawn w, h (doubles, not in the block) are at hand.
+ *
+ * Slots.  A clip owns Pmax slots; the first tube_count_out[n] are real, the others hold the whole frame (0, 0, Wn, Hn) on every frame -- a
+ * valid box for ROIAlign, and what valid_tubes makes of a degenerate one.  The count stays on the device (step_select_train_counted's
+ * clip_count, step_detect_nms' tube_count).
+ *
+ * The rule, per clip (TubeAugmentation.plan's for float64 proposals): double on the fp32 inputs widened, every operation rounded on its own.
+ *   P = clamp(tube_count[n], 0, Pmax).
+ *   1 P == 0 and fill != NULL: the rows are fill[0 .. min(n_fill, Pmax)), repeated over the Tp frames, NOT transformed (the reference
+ *     builds the anchor grid behind the transform); the count is min(n_fill, Pmax); on to 6.
+ *   2 Pixels: box * (W, H, W, H).
+ *   3 Crop accepted (rect, drawn w, h): every proposal, every frame, no centre test, nothing dropped: lo = max(lo, rect.lo) - rect.lo, hi =
+ *     min(hi, rect.hi) - rect.lo; then valid_tubes(width = w, height = h): x1 = max(0, x1), y1 = max(0, y1), x2 = min(w, x2), y2 =
+ *     min(h, y2), and unless x1 < x2 - 2 && y1 < y2 - 2 the box becomes (0, 0, w, h).
+ *   4 Mirror: (x1, x2) = (width - x2, width - x1) for EVERY box (no zero-box exemption), width the crop's integer width, or W.
+ *   5 Percent: box / (width, height, width, height).
+ *   6 tubes_out = fp32(min(max(., 0), 1) * (Wn, Hn, Wn, Hn)), one rounding; rows from the count on are (0, 0, Wn, Hn).
+ *
+ * Errors, with tubes_in given: Pmax < 0, Tp < 1, n_fill < 0 -> STEP_E_SHAPE; Pmax > 1024 or N Pmax Tp >= 2^29 -> STEP_E_UNSUPPORTED;
+ * tube_count, tubes_out or tube_count_out NULL -> STEP_E_NULL.  A refused call writes nothing and leaves the offset alone. */
+STEP_API int step_augment_plan_tubes(const unsigned long long* src, const int32_t* dims, const float* gt_in, const int32_t* gt_count, int N,
+                                     int Gmax, int F, int NC, int switches, int scale, int Wn, int Hn, long long max_hw,
+                                     unsigned long long* rng_state, void* plan_block, float* gt_out, int32_t* gt_count_out,
+                                     const float* tubes_in, const int32_t* tube_count, int Pmax, int Tp, const float* fill, int n_fill,
+                                     float* tubes_out, int32_t* tube_count_out, step_stream_t stream);
 
 #ifdef __cplusplus
 }

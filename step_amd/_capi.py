@@ -5,7 +5,7 @@ import ctypes as C
 F32, BF16, F16 = 0, 1, 2
 NCHW, NHWC = 0, 1
 ROI_BWD_GATHER, ROI_BWD_ATOMIC = 0, 1
-ABI_VERSION = 47
+ABI_VERSION = 48
 
 vp, fp, ip, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # raw device addresses
 i, f, ll, sz = C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -126,9 +126,11 @@ SIGNATURES = {
     "step_tube_update": (i, [fp, i, i, fp, fp, fp, i, i, i, ip, i, f, f, fp, fp, fp, fp, vp]),
     "step_select_prepare": (i, [fp, fp, fp, fp, i, i, i, i, ip, fp, ip, i, f, f, fp, fp, fp, fp, fp, vp]),
     "step_select_train": (i, [fp, fp, fp, fp, fp, i, i, i, i, ip, i, i, fp, ip, i, i, fp, vp, i, i, i, i, f, f, i, i, i, i, fp, fp, fp, fp, ip, vp]),
+    "step_select_train_counted": (i, [fp, fp, fp, fp, fp, i, i, i, i, ip, i, i, fp, ip, i, i, fp, vp, i, i, i, i, f, f, i, i, i, i, fp, fp, fp, fp, ip, ip, vp]),
     "step_anchor_sample": (i, [fp, ip, i, i, i, i, i, f, f, i, i, i, f, f, i, vp, fp, ip, ip, vp]),
     "step_augment_plan_bytes": (sz, [i, i, ll, C.POINTER(C.c_int)]),
     "step_augment_plan": (i, [vp, ip, fp, ip, i, i, i, i, i, i, i, i, ll, vp, vp, fp, ip, vp]),
+    "step_augment_plan_tubes": (i, [vp, ip, fp, ip, i, i, i, i, i, i, i, i, ll, vp, vp, fp, ip, fp, ip, i, i, fp, i, fp, ip, vp]),
     "step_adam_flat": (i, [fp, fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, C.c_double, i, f, i, vp]),
     "step_adam_flat_dev": (i, [fp, fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, C.c_double, vp, fp, f, i, vp]),
     "step_adam_flat_amp": (i, [fp, fp, fp, fp, ll, vp, fp, fp, i, C.c_double, C.c_double, C.c_double, vp, fp, f, i, fp, f, f, i, vp]),

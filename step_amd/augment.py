@@ -317,7 +317,8 @@ class DeviceTubeAugmentation(_Transform):
     TubeAugmentation plus `rng`, a step_amd.DeviceRNG.  `.apply()` is the planner, the noise fill and step_clip_augment_u8 on the current
     stream -- three launches, two offsets of `rng`, no copy and no host synchronisation, so the calls can be recorded in a graph and every
     replay draws anew.  Besides the clip it writes the transformed ground truths, the `gt` / `gt_count` step_select_train reads.  Same
-    rule as TubeAugmentation.plan, other draws (the device generator's, not numpy's); proposals are not transformed."""
+    rule as TubeAugmentation.plan, other draws (the device generator's, not numpy's).  With `tubes=` the planner transforms the clips'
+    detector proposals as well (step_augment_plan_tubes: the same launches and offsets) into padded slots with a device-side count."""
 
     def __init__(self, size=300, mean=(0, 0, 0), stds=(1, 1, 1), do_flip=False, do_crop=False, do_photometric=False, do_erase=False, scale=1,
                  rng=None):
@@ -351,11 +352,16 @@ class DeviceTubeAugmentation(_Transform):
             self._frames = (key, torch.from_numpy(src).to(dev), torch.from_numpy(dims).to(dev))
         return self._frames[1], self._frames[2]
 
-    def apply(self, frames, gt, gt_count, out=None, gt_out=None, gt_count_out=None, dtype=torch.bfloat16, rgb=True):
+    def apply(self, frames, gt, gt_count, out=None, gt_out=None, gt_count_out=None, dtype=torch.bfloat16, rgb=True, tubes=None, tube_count=None,
+              fill=None, tubes_out=None, tube_count_out=None):
         """frames: one device uint8 tensor [N,T,Hs,Ws,3] or a list of N per-clip [T,Hs_i,Ws_i,3] device tensors (BGR); gt [N,Gmax,F,4+NC]
         float32 percent boxes + labels (an all-zero box pads a tube) and gt_count [N] int32, on the device.  Returns (clip [N,T,3,Ho,Wo],
         gt_out [N,Gmax,F,4+NC] in pixels of the network's resolution, kept tubes first, gt_count_out [N]); `out`, `gt_out`,
-        `gt_count_out` are filled when given (out's dtype wins)."""
+        `gt_count_out` are filled when given (out's dtype wins).
+        tubes [N,Pmax,Tp,4] float32 percent boxes with tube_count [N] int32: the clips' proposals, transformed with the frames; fill [n,4]
+        float32 percent boxes stands in, untransformed, for a clip without any (the anchor grid).  The call then returns two more tensors:
+        tubes_out [N,Pmax,Tp,4] in pixels of the network's resolution -- the first tube_count_out[n] slots of a clip real, the others the
+        whole frame -- and tube_count_out [N] int32 (both filled when given)."""
         L = _lib.lib()
         clips = list(frames.unbind(0)) if torch.is_tensor(frames) else list(frames)
         N = len(clips)
@@ -387,13 +393,35 @@ class DeviceTubeAugmentation(_Transform):
             gt_count_out = torch.empty_like(gt_count)
         elif tuple(gt_count_out.shape) != (N,) or gt_count_out.dtype != torch.int32 or gt_count_out.device != dev:
             raise RuntimeError("step_amd: apply(gt_count_out=...) wants an int32 [N] tensor on the frames' device")
+        Pmax = Tp = n_fill = 0
+        if tubes is not None:
+            if tubes.dim() != 4 or tubes.shape[0] != N or tubes.shape[3] != 4 or tubes.dtype != torch.float32 or not tubes.is_contiguous() or tubes.device != dev:
+                raise RuntimeError("step_amd: apply() wants tubes as a contiguous float32 [N,Pmax,Tp,4] tensor on the frames' device")
+            if tube_count is None or tuple(tube_count.shape) != (N,) or tube_count.dtype != torch.int32 or tube_count.device != dev:
+                raise RuntimeError("step_amd: apply() wants tube_count as an int32 [N] tensor on the frames' device")
+            if fill is not None and (fill.dim() != 2 or fill.shape[1] != 4 or fill.dtype != torch.float32 or not fill.is_contiguous() or fill.device != dev):
+                raise RuntimeError("step_amd: apply() wants fill as a contiguous float32 [n,4] tensor on the frames' device")
+            Pmax, Tp, n_fill = tubes.shape[1], tubes.shape[2], (0 if fill is None else fill.shape[0])
+            if tubes_out is None:
+                tubes_out = torch.empty_like(tubes)
+            elif tubes_out.shape != tubes.shape or tubes_out.dtype != torch.float32 or not tubes_out.is_contiguous() or tubes_out.device != dev:
+                raise RuntimeError("step_amd: apply(tubes_out=...) wants a contiguous float32 tensor of tubes' shape on the frames' device")
+            if tube_count_out is None:
+                tube_count_out = torch.empty_like(tube_count)
+            elif tuple(tube_count_out.shape) != (N,) or tube_count_out.dtype != torch.int32 or tube_count_out.device != dev:
+                raise RuntimeError("step_amd: apply(tube_count_out=...) wants an int32 [N] tensor on the frames' device")
+        elif tube_count is not None or fill is not None or tubes_out is not None or tube_count_out is not None:
+            raise RuntimeError("step_amd: apply() takes tube_count, fill, tubes_out and tube_count_out only with tubes")
         max_hw = max(c.shape[1] * c.shape[2] for c in clips)
         block = self._block(N, Gmax, max_hw, dev)
         src, dims = self._sources(clips, dev)
-        _capi.check(L.step_augment_plan(_lib.dptr(src), _lib.dptr(dims), _lib.dptr(gt), _lib.dptr(gt_count), N, Gmax, F, NC, self.switches,
-                                        self.scale, Wo, Ho, max_hw, _lib.dptr(self.rng.state), _lib.dptr(block), _lib.dptr(gt_out),
-                                        _lib.dptr(gt_count_out), _lib.stream_ptr(dev)), "step_augment_plan")
+        _capi.check(L.step_augment_plan_tubes(_lib.dptr(src), _lib.dptr(dims), _lib.dptr(gt), _lib.dptr(gt_count), N, Gmax, F, NC, self.switches,
+                                              self.scale, Wo, Ho, max_hw, _lib.dptr(self.rng.state), _lib.dptr(block), _lib.dptr(gt_out),
+                                              _lib.dptr(gt_count_out), _lib.dptr(tubes), _lib.dptr(tube_count), Pmax, Tp, _lib.dptr(fill), n_fill,
+                                              _lib.dptr(tubes_out), _lib.dptr(tube_count_out), _lib.stream_ptr(dev)), "step_augment_plan_tubes")
         self.launch(block, N, T, out, rgb)
+        if tubes is not None:
+            return out, gt_out, gt_count_out, tubes_out, tube_count_out
         return out, gt_out, gt_count_out
 
     def last_block(self):

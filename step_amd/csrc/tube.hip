@@ -129,6 +129,7 @@ constexpr int SEL_MAX_GT = 64;
 
 struct SelTrainParams {
     const float* cand; const float* cfirst; const float* clast; const float* score; const float* iou; const int32_t* clip_start;
+    const int32_t* clip_count;                                  // NULL: a clip owns its whole segment (step_select_train)
     const float* gt; const int32_t* gt_count; const float* pad; const unsigned long long* rng;
     float* sel; float* tgt; float* mask; int32_t* counts;
     int N, B, Tc, Tw, NC, Gmax, F, Amax, mid, before, after, topk, max_pos, neg_ratio, sampling, budget;
@@ -186,6 +187,11 @@ __global__ __launch_bounds__(256) void select_train_kernel(SelTrainParams p) {
     int A = p.clip_start[b + 1] - start;
     if (A > p.Amax) A = p.Amax;
     if (start < 0 || A < 0 || (long long)start + A > p.N) A = 0;           // (a table that does not describe [0, N): select nothing)
+    if (p.clip_count) {                                                     // the segment's first clip_count[b] slots are real, the others padding
+        int c = p.clip_count[b];
+        c = c < 0 ? 0 : c;
+        A = c < A ? c : A;
+    }
     int G = p.gt_count[b];
     G = G < 0 ? 0 : G > p.Gmax ? p.Gmax : G;
     if (A == 0) G = 0;
@@ -582,6 +588,8 @@ struct AugPlanParams {
     const unsigned long long* src; const int32_t* dims; const float* gt_in; const int32_t* gt_count; const unsigned long long* rng;
     unsigned char* block; float* gt_out; int32_t* gt_count_out;
     int N, Gmax, F, NC, switches, scale, Wn, Hn, cap_words;
+    const float* tubes_in; const int32_t* tube_count; const float* fill; float* tubes_out; int32_t* tube_count_out;      // step_augment_plan_tubes
+    int Pmax, Tp, n_fill;
 };
 
 __device__ __forceinline__ float augp_div(float a, float b) { return (float)((double)a / (double)b); }     // IEEE fp32 quotient and root, whatever
@@ -645,6 +653,7 @@ __global__ __launch_bounds__(64) void augment_plan_kernel(AugPlanParams p) {
 
     // RandomSampleCrop: phase 1
     unsigned long long keep = G >= 64 ? ~0ull : (1ull << G) - 1ull;
+    double crop_w = 0.0, crop_h = 0.0;                                        // the accepted trial's drawn sizes: valid_tubes' window for the proposals
     if (p.switches & STEP_AUGP_CROP) {
         const double Wd = (double)s.W, Hd = (double)s.H;
         for (int round = 0; round < AUGP_CROP_ROUNDS; ++round) {
@@ -693,6 +702,7 @@ __global__ __launch_bounds__(64) void augment_plan_kernel(AugPlanParams p) {
                 const int win = __builtin_ctzll(acc);
                 if (lane == win) { s_rect[0] = r[0]; s_rect[1] = r[1]; s_rect[2] = r[2]; s_rect[3] = r[3]; }
                 keep = __shfl(kept, win);
+                crop_w = __shfl(w, win); crop_h = __shfl(h, win);
                 __syncthreads();
                 s.cropped = 1; s.r0 = s_rect[0]; s.r1 = s_rect[1]; s.r2 = s_rect[2]; s.r3 = s_rect[3];
                 s.width = s.r2 - s.r0; s.height = s.r3 - s.r1;
@@ -705,6 +715,45 @@ __global__ __launch_bounds__(64) void augment_plan_kernel(AugPlanParams p) {
     // mirror and the erase coin: phase 2
     if ((p.switches & STEP_AUGP_FLIP) && sel_floor(sel_draw(seed, off, n, 2, 0), 2)) { s.mirror = 1; flags |= STEP_AUG_MIRROR; }
     const bool erase = (p.switches & STEP_AUGP_ERASE) && sel_floor(sel_draw(seed, off, n, 2, 1), 2);
+
+    // the proposals (step_augment_plan_tubes): a clip owns Pmax slots, the first `cnt` real -- its own, transformed in double on the fp32
+    // inputs as TubeAugmentation.plan does with float64 proposals, or the fill rows when it has none -- the others the whole frame
+    if (p.tubes_out) {
+        int P = p.tube_count[n];
+        P = P < 0 ? 0 : P > p.Pmax ? p.Pmax : P;
+        const bool filled = P == 0 && p.fill;
+        const int cnt = filled ? (p.n_fill < p.Pmax ? p.n_fill : p.Pmax) : P;
+        const size_t base = (size_t)n * p.Pmax * p.Tp;
+        for (int i = lane; i < p.Pmax * p.Tp; i += 64) {
+            const int j = i / p.Tp;
+            double b[4] = {0.0, 0.0, 1.0, 1.0};
+            if (j < cnt) {
+                if (filled) {                                                 // (the reference builds the anchors behind the transform)
+                    const float* q = p.fill + (size_t)j * 4;
+                    b[0] = (double)q[0]; b[1] = (double)q[1]; b[2] = (double)q[2]; b[3] = (double)q[3];
+                } else {
+                    const float* q = p.tubes_in + (base + i) * 4;
+                    b[0] = (double)q[0] * (double)s.W; b[1] = (double)q[1] * (double)s.H; b[2] = (double)q[2] * (double)s.W; b[3] = (double)q[3] * (double)s.H;
+                    if (s.cropped) {                                          // _shift_into, then valid_tubes(width = w, height = h)
+                        const double x0 = (double)s.r0, y0 = (double)s.r1, x1 = (double)s.r2, y1 = (double)s.r3;
+                        b[0] = anc_max(b[0], x0) - x0; b[1] = anc_max(b[1], y0) - y0;
+                        b[2] = anc_min(b[2], x1) - x0; b[3] = anc_min(b[3], y1) - y0;
+                        b[0] = anc_max(b[0], 0.0); b[1] = anc_max(b[1], 0.0); b[2] = anc_min(b[2], crop_w); b[3] = anc_min(b[3], crop_h);
+                        if (!(b[0] < b[2] - 2.0 && b[1] < b[3] - 2.0)) { b[0] = 0.0; b[1] = 0.0; b[2] = crop_w; b[3] = crop_h; }
+                    }
+                    if (s.mirror) {                                           // (every box: no zero-box exemption for proposals)
+                        const double l = (double)s.width - b[2], r = (double)s.width - b[0];
+                        b[0] = l; b[2] = r;
+                    }
+                    b[0] = b[0] / (double)s.width; b[1] = b[1] / (double)s.height; b[2] = b[2] / (double)s.width; b[3] = b[3] / (double)s.height;
+                }
+                for (int c = 0; c < 4; ++c) b[c] = anc_min(anc_max(b[c], 0.0), 1.0);
+            }
+            float* o = p.tubes_out + (base + i) * 4;
+            o[0] = (float)(b[0] * (double)p.Wn); o[1] = (float)(b[1] * (double)p.Hn); o[2] = (float)(b[2] * (double)p.Wn); o[3] = (float)(b[3] * (double)p.Hn);
+        }
+        if (lane == 0) p.tube_count_out[n] = cnt;
+    }
 
     // RandomErase.get_region per kept box, in order: phase 3
     int n_rects = 0;
@@ -835,17 +884,22 @@ extern "C" size_t step_augment_plan_bytes(int N, int Gmax, long long max_hw, int
     return (size_t)(4 * ((words + 3) / 4 * 4));
 }
 
-extern "C" int step_augment_plan(const unsigned long long* src, const int32_t* dims, const float* gt_in, const int32_t* gt_count, int N, int Gmax,
-                                 int F, int NC, int switches, int scale, int Wn, int Hn, long long max_hw, unsigned long long* rng_state,
-                                 void* plan_block, float* gt_out, int32_t* gt_count_out, step_stream_t stream) {
+extern "C" int step_augment_plan_tubes(const unsigned long long* src, const int32_t* dims, const float* gt_in, const int32_t* gt_count, int N, int Gmax,
+                                       int F, int NC, int switches, int scale, int Wn, int Hn, long long max_hw, unsigned long long* rng_state,
+                                       void* plan_block, float* gt_out, int32_t* gt_count_out, const float* tubes_in, const int32_t* tube_count,
+                                       int Pmax, int Tp, const float* fill, int n_fill, float* tubes_out, int32_t* tube_count_out,
+                                       step_stream_t stream) {
     if (N < 0 || Gmax < 0 || F <= 0 || NC < 0 || Wn < 1 || Hn < 1 || max_hw < 1) return STEP_E_SHAPE;
     if (scale < 0 || scale > 2 || (switches & ~15)) return STEP_E_SHAPE;
-    if (Gmax > SEL_MAX_GT) return STEP_E_UNSUPPORTED;
+    if (tubes_in && (Pmax < 0 || Tp < 1 || n_fill < 0)) return STEP_E_SHAPE;
+    if (Gmax > SEL_MAX_GT || (tubes_in && Pmax > SEL_MAX_TUBES)) return STEP_E_UNSUPPORTED;
+    if (tubes_in && (long long)N * Pmax * Tp > 0x1fffffffLL) return STEP_E_UNSUPPORTED;
     const long long cap = augp_cap_words(max_hw);
     if (cap > (1ll << 22)) return STEP_E_UNSUPPORTED;                          // (a patch's elements are addressed by 20 bits of Philox block)
     if (16ll * N + 6ll * Gmax * N + 4 + (long long)N * Gmax * cap > 0x7fffffffLL || (long long)N * Gmax > 65535) return STEP_E_UNSUPPORTED;
     if (!rng_state) return STEP_E_NULL;
     if ((uintptr_t)rng_state & 7) return STEP_E_ALIGN;
+    if (tubes_in && (!tube_count || !tubes_out || !tube_count_out)) return STEP_E_NULL;
     if (N > 0) {
         if (!src || !dims || !gt_count || !plan_block || !gt_count_out || (Gmax && (!gt_in || !gt_out))) return STEP_E_NULL;
         if ((uintptr_t)plan_block & 15) return STEP_E_ALIGN;
@@ -853,6 +907,8 @@ extern "C" int step_augment_plan(const unsigned long long* src, const int32_t* d
         p.src = src; p.dims = dims; p.gt_in = gt_in; p.gt_count = gt_count; p.rng = rng_state;
         p.block = (unsigned char*)plan_block; p.gt_out = gt_out; p.gt_count_out = gt_count_out;
         p.N = N; p.Gmax = Gmax; p.F = F; p.NC = NC; p.switches = switches; p.scale = scale; p.Wn = Wn; p.Hn = Hn; p.cap_words = (int)cap;
+        p.tubes_in = tubes_in; p.tube_count = tube_count; p.fill = n_fill > 0 ? fill : nullptr; p.tubes_out = tubes_in ? tubes_out : nullptr;
+        p.tube_count_out = tube_count_out; p.Pmax = Pmax; p.Tp = Tp; p.n_fill = n_fill;
         STEP_LAUNCH(augment_plan_kernel, dim3((unsigned)N), dim3(64), stream, p);
     }
     const double lo = scale == 2 ? -1.0 : 0.0, hi = scale == 0 ? 255.0 : 1.0;
@@ -861,6 +917,13 @@ extern "C" int step_augment_plan(const unsigned long long* src, const int32_t* d
     STEP_LAUNCH(augment_noise_kernel, dim3(gx, (unsigned)(slots > 0 ? slots : 1)), dim3(64), stream, (unsigned char*)plan_block, N, Gmax,
                 (int)cap, lo, hi, rng_state);                                  // (also for N == 0: the call counts)
     return STEP_LAUNCH_CHECK();
+}
+
+extern "C" int step_augment_plan(const unsigned long long* src, const int32_t* dims, const float* gt_in, const int32_t* gt_count, int N, int Gmax,
+                                 int F, int NC, int switches, int scale, int Wn, int Hn, long long max_hw, unsigned long long* rng_state,
+                                 void* plan_block, float* gt_out, int32_t* gt_count_out, step_stream_t stream) {
+    return step_augment_plan_tubes(src, dims, gt_in, gt_count, N, Gmax, F, NC, switches, scale, Wn, Hn, max_hw, rng_state, plan_block, gt_out,
+                                   gt_count_out, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int step_anchor_sample(const float* gt, const int32_t* gt_count, int B, int Gmax, int F, int NC, int mid, float width, float height,
@@ -899,12 +962,12 @@ extern "C" int step_select_prepare(const float* prob, const float* loc, const fl
     return STEP_LAUNCH_CHECK();
 }
 
-extern "C" int step_select_train(const float* cand, const float* cand_first, const float* cand_last, const float* score, const float* iou,
-                                 int N, int Tc, int Tw, int NC, const int32_t* clip_start, int B, int Amax, const float* gt,
-                                 const int32_t* gt_count, int Gmax, int F, const float* pad_tubes, unsigned long long* rng_state, int mid,
-                                 int before, int after, int topk, float cls_thresh, float reg_thresh, int max_pos_num, int neg_ratio,
-                                 int sampling, int budget, float* sel, float* tgt, float* mask, float* inv, int32_t* counts,
-                                 step_stream_t stream) {
+extern "C" int step_select_train_counted(const float* cand, const float* cand_first, const float* cand_last, const float* score, const float* iou,
+                                         int N, int Tc, int Tw, int NC, const int32_t* clip_start, int B, int Amax, const float* gt,
+                                         const int32_t* gt_count, int Gmax, int F, const float* pad_tubes, unsigned long long* rng_state, int mid,
+                                         int before, int after, int topk, float cls_thresh, float reg_thresh, int max_pos_num, int neg_ratio,
+                                         int sampling, int budget, float* sel, float* tgt, float* mask, float* inv, int32_t* counts,
+                                         const int32_t* clip_count, step_stream_t stream) {
     if (N < 0 || B < 0 || Tc <= 0 || Tw < 0 || NC <= 0 || Gmax < 0 || F <= 0 || Amax < 0 || budget <= 0) return STEP_E_SHAPE;
     if (mid < 0 || mid >= F || (before < 0) != (after < 0) || before >= F || after >= F) return STEP_E_SHAPE;
     if (max_pos_num < 0 || neg_ratio < 0 || sampling < 0 || sampling > 2) return STEP_E_SHAPE;
@@ -919,7 +982,7 @@ extern "C" int step_select_train(const float* cand, const float* cand_first, con
         if ((cand_first != nullptr) != (cand_last != nullptr) || (cand_first && Tw <= 0)) return STEP_E_NULL;
         SelTrainParams p;
         p.cand = cand; p.cfirst = cand_first; p.clast = cand_last; p.score = score; p.iou = iou; p.clip_start = clip_start;
-        p.gt = gt; p.gt_count = gt_count; p.pad = pad_tubes; p.rng = rng_state;
+        p.gt = gt; p.gt_count = gt_count; p.pad = pad_tubes; p.rng = rng_state; p.clip_count = clip_count;
         p.sel = sel; p.tgt = tgt; p.mask = mask; p.counts = counts;
         p.N = N; p.B = B; p.Tc = Tc; p.Tw = Tw; p.NC = NC; p.Gmax = Gmax; p.F = F; p.Amax = Amax; p.mid = mid; p.before = before; p.after = after;
         p.topk = topk; p.max_pos = max_pos_num; p.neg_ratio = neg_ratio; p.sampling = sampling; p.budget = budget;
@@ -929,6 +992,17 @@ extern "C" int step_select_train(const float* cand, const float* cand_first, con
     }
     STEP_LAUNCH(select_finish_kernel, dim3(1), dim3(64), stream, (const int32_t*)counts, B, NC, inv, rng_state);      // (also for B == 0: the call counts)
     return STEP_LAUNCH_CHECK();
+}
+
+extern "C" int step_select_train(const float* cand, const float* cand_first, const float* cand_last, const float* score, const float* iou,
+                                 int N, int Tc, int Tw, int NC, const int32_t* clip_start, int B, int Amax, const float* gt,
+                                 const int32_t* gt_count, int Gmax, int F, const float* pad_tubes, unsigned long long* rng_state, int mid,
+                                 int before, int after, int topk, float cls_thresh, float reg_thresh, int max_pos_num, int neg_ratio,
+                                 int sampling, int budget, float* sel, float* tgt, float* mask, float* inv, int32_t* counts,
+                                 step_stream_t stream) {
+    return step_select_train_counted(cand, cand_first, cand_last, score, iou, N, Tc, Tw, NC, clip_start, B, Amax, gt, gt_count, Gmax, F, pad_tubes,
+                                     rng_state, mid, before, after, topk, cls_thresh, reg_thresh, max_pos_num, neg_ratio, sampling, budget, sel, tgt,
+                                     mask, inv, counts, nullptr, stream);
 }
 
 extern "C" int step_tube_update(const float* tubes, int N, int T, const float* local_loc, const float* first_loc, const float* last_loc,

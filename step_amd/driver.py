@@ -49,6 +49,29 @@ def _flat_tubes(tubes_list, device, dtype=torch.float32):
     return torch.cat(rows, dim=0), nums
 
 
+def pad_tubes(tubes_list, capacity, device, width, height):
+    """list (one per clip) of [n_i, T, 4] tensors/arrays, n_i <= capacity (zero included) -> (flat [B*K,T,5] with the frame index, count
+    int32 [B]), K = capacity: the padded form of _flat_tubes.  A clip owns K slots, the first count[b] hold its tubes, the others the whole
+    frame (0, 0, width, height) on every frame -- a valid box for ROIAlign, what valid_tubes makes of a degenerate one.  inference_flat(...,
+    counts=count) carries the count to postprocess, which hands it to step_detect_nms."""
+    K, B = int(capacity), len(tubes_list)
+    arrs = [np.asarray(t.detach().cpu() if torch.is_tensor(t) else t, np.float32) for t in tubes_list]
+    T = next((a.shape[1] for a in arrs if a.ndim == 3), None)
+    if T is None:
+        raise ValueError("step_amd: pad_tubes wants [n,T,4] arrays (an empty clip is a [0,T,4] array)")
+    arrs = [a.reshape(-1, T, 4) for a in arrs]
+    host = np.empty((B, K, T, 5), np.float32)
+    host[..., 1:] = (0.0, 0.0, float(width), float(height))
+    host[..., 0] = (np.arange(B, dtype=np.float32)[:, None, None] * T + np.arange(T, dtype=np.float32)[None, None, :])
+    count = np.zeros(B, np.int32)
+    for b, a in enumerate(arrs):
+        if a.shape[0] > K:
+            raise ValueError("step_amd: clip %d has %d tubes, the capacity is %d" % (b, a.shape[0], K))
+        host[b, :a.shape[0], :, 1:] = a
+        count[b] = a.shape[0]
+    return torch.from_numpy(host.reshape(B * K, T, 5)).to(device), torch.from_numpy(count).to(device)
+
+
 def inference(args, conv_feat, context_feat, nets, exec_iter, tubes):
     """args: Namespace with T, NUM_CHUNKS, max_iter, num_classes, image_size, no_context, temporal_mode
     conv_feat [B,T_all,C,H,W] (BaseNet output), context_feat [B,1024,T_all,1,1] or None,
@@ -72,11 +95,13 @@ def inference(args, conv_feat, context_feat, nets, exec_iter, tubes):
     return history, trajectory
 
 
-def inference_flat(args, conv_feat, context_feat, nets, exec_iter, flat, nums, clip_of, want_classes=True):
+def inference_flat(args, conv_feat, context_feat, nets, exec_iter, flat, nums, clip_of, want_classes=True, counts=None):
     """The device-resident core of `inference`: flat [N,T,5] tubes (col 0 = frame index), nums = tubes per
     clip, clip_of [N] = clip index of every tube.  Pure tensor ops with static shapes and no host
     synchronisation, so the whole multi-step pipeline can be captured in a hipGraph (GraphedInference).
-    want_classes=False: the trajectory's class index (an argmax per step that only `inference` hands on) is None."""
+    want_classes=False: the trajectory's class index (an argmax per step that only `inference` hands on) is None.
+    counts: int32 [B] on the device for PADDED clips (pad_tubes: nums = [K] * B slots, the first counts[b] of a clip real) -- every
+    history dict then carries it as "tubes_count" beside "tubes_nums"; the arithmetic runs over all slots."""
     dev = conv_feat.device
     history, trajectory = [], []
     clip32 = None
@@ -106,6 +131,8 @@ def inference_flat(args, conv_feat, context_feat, nets, exec_iter, flat, nums, c
                 args.image_size[0], args.image_size[1])
             history.append({"pred_prob": pred_prob.detach(), "pred_loc": pred_loc, "pred_first_loc": pred_first,
                             "pred_last_loc": pred_last, "tubes_nums": list(nums)})
+            if counts is not None:
+                history[-1]["tubes_count"] = counts
             trajectory.append((flat[:, :, 1:], torch.argmax(prob, dim=-1) if want_classes else None))
             continue
         flat = flat.to(local_loc)
@@ -117,6 +144,8 @@ def inference_flat(args, conv_feat, context_feat, nets, exec_iter, flat, nums, c
         history.append({"pred_prob": pred_prob.detach(), "pred_loc": pred_loc.detach(),            # utils.py:81-85 (.data)
                         "pred_first_loc": pred_first.detach() if mode == "predict" else None,
                         "pred_last_loc": pred_last.detach() if mode == "predict" else None, "tubes_nums": list(nums)})
+        if counts is not None:
+            history[-1]["tubes_count"] = counts
 
         # next step's proposals (utils.py:91-129), all clips at once
         if extend:
@@ -152,10 +181,23 @@ def _clip_groups(nums, device):
 _POST_CONST = {}
 
 
-def _detect_keep(nums, NC, dev, members, conf, thr, W, H):
+def _count32(count, B, dev):
+    if tuple(count.shape) != (B,) or count.device != dev:
+        raise RuntimeError("step_amd: a history's tubes_count wants an int32 [B=%d] tensor on %s, got %s on %s" % (B, dev, tuple(count.shape), count.device))
+    return count if count.dtype == torch.int32 and count.is_contiguous() else count.to(torch.int32).contiguous()
+
+
+def _count_key(h):
+    """histories that share a clip layout share a launch: a padded one's count tensor is part of its layout"""
+    c = h.get("tubes_count")
+    return None if c is None else (c.data_ptr(), c._version)
+
+
+def _detect_keep(nums, NC, dev, members, conf, thr, W, H, count=None):
     """The fused mask + valid_tubes + NMS launch (ops.detect_nms) of every iteration in `members` (one clip layout `nums`, <= 1024 tubes
     per clip: a wavefront per (clip, class) up to 64, a workgroup beyond) -> keep [I,B,NC,kmax], the clamped boxes and the middle-frame
-    scores per iteration, tube_start [B] int32, [W,H,W,H]."""
+    scores per iteration, tube_start [B] int32, [W,H,W,H].  count: a padded history's "tubes_count" -- `nums` are then the clips' SLOTS and the
+    launch takes its tube_count from that device tensor instead of the cached table: padded slots are never kept."""
     B, kmax, I = len(nums), max(nums), len(members)
     # per-layout constants live on the device (a host -> device copy from pageable memory per call stalls the host; the layout of a
     # serving loop never changes)
@@ -167,6 +209,8 @@ def _detect_keep(nums, NC, dev, members, conf, thr, W, H):
         if len(_POST_CONST) > 64:
             _POST_CONST.pop(next(iter(_POST_CONST)))
     n, start, whwh = hit
+    if count is not None:
+        n = _count32(count, B, dev)
     keep = torch.empty((I, B, NC, kmax), dtype=torch.uint8, device=dev)
     sc_all, bx_all = [], []
     for k, (oi, h) in enumerate(members):
@@ -208,14 +252,16 @@ def postprocess(args, history, conf_thresh=None, nms_thresh=None, evaluate_topk=
             out[oi] = [{"boxes": e.view(0, 4), "scores": e, "labels": e.long(), "tubes": e.long()} for _ in nums]
         elif max(nums) <= _fused_tubes():
             fast.append((oi, h, nums))
+        elif h.get("tubes_count") is not None:
+            raise NotImplementedError("step_amd: a padded history (tubes_count) takes the fused path: at most %d slots per clip" % _fused_tubes())
         else:
             slow.append((oi, h, nums))
     groups = {}
     for oi, h, nums in fast:
-        groups.setdefault((tuple(nums), h["pred_prob"].shape[-1], h["pred_loc"].device), []).append((oi, h))
-    for (nums, NC, dev), members in groups.items():
+        groups.setdefault((tuple(nums), h["pred_prob"].shape[-1], h["pred_loc"].device, _count_key(h)), []).append((oi, h))
+    for (nums, NC, dev, _), members in groups.items():
         B, kmax, I = len(nums), max(nums), len(members)
-        keep, bx_all, sc_all, start, whwh = _detect_keep(nums, NC, dev, members, conf, thr, W, H)
+        keep, bx_all, sc_all, start, whwh = _detect_keep(nums, NC, dev, members, conf, thr, W, H, members[0][1].get("tubes_count"))
         # rows in the reference's order: iteration, clip, class ascending, kept tube ascending == row-major order of `keep`
         if COMPACT_KERNEL and I <= 8:
             # one launch (step_detect_compact: a ballot prefix per (iteration, clip) into fixed-capacity segments) and one small copy of
@@ -399,19 +445,23 @@ def postprocess_merged(args, history, conf_thresh=None, nms_thresh=None, global_
             e = torch.zeros(0, device=h["pred_loc"].device)
             out[oi] = [{"boxes": e.view(0, 4), "cluster": e.long(), "labels": e.long(), "scores": e, "tubes": e.long()} for _ in nums]
         else:
-            groups.setdefault((tuple(nums), h["pred_prob"].shape[-1], h["pred_loc"].device), []).append((oi, h))
-    for (nums, NC, dev), members in groups.items():
+            groups.setdefault((tuple(nums), h["pred_prob"].shape[-1], h["pred_loc"].device, _count_key(h)), []).append((oi, h))
+    for (nums, NC, dev, _), members in groups.items():
         B, kmax = len(nums), max(nums)
+        count = members[0][1].get("tubes_count")
         cap = NC * kmax
         if kmax <= 64 or (kmax <= _fused_tubes() and cap <= MERGE_ROWS_MAX):
             for m0 in range(0, len(members), 8):                                                      # (STEP_DETECT_ITERS_MAX iterations per launch)
                 part = members[m0:m0 + 8]
-                keep, bx_all, sc_all, start, _ = _detect_keep(nums, NC, dev, part, conf, thr, W, H)
+                keep, bx_all, sc_all, start, _ = _detect_keep(nums, NC, dev, part, conf, thr, W, H, count)
                 rb, rs, kc, kj, cnt = ops.detect_compact(keep, bx_all, sc_all, start, W, H)
                 G = len(part) * B
                 res = _merge_segments(rb.view(G, cap, 4), rs.view(G, cap), kc.view(G, cap), kj.view(G, cap), cnt, gthr, etopk, topk)
                 for k, (oi, h) in enumerate(part):
                     out[oi] = res[k * B:(k + 1) * B]
+        elif count is not None:
+            raise NotImplementedError("step_amd: a padded history (tubes_count) takes the fused path: at most %d slots per clip and %d rows per segment"
+                                      % (_fused_tubes(), MERGE_ROWS_MAX))
         else:
             # the general path's rows come as one flat list per iteration: scatter them into the same fixed-capacity segments
             I = len(members)
@@ -451,14 +501,37 @@ class GraphedInference:
     """BaseNet -> ContextNet -> multi-step inference for a FIXED batch size / tubes-per-clip, captured once
     in a hipGraph and replayed: the ~200 small launches of the three refinement steps stop being bound by
     Python / launch latency.  `__call__(images, tubes)` copies the inputs into the captured buffers, replays
-    and returns (history, conv_feat, context_feat) -- static tensors that the next call overwrites."""
+    and returns (history, conv_feat, context_feat) -- static tensors that the next call overwrites.
 
-    def __init__(self, args, base_net, context_net, nets, images, tubes):
+    capacity=K: captured once over B * K padded slots (pad_tubes) with the tubes per clip in a device-side count.  `__call__(images, tubes)`
+    then takes ANY list with at most K tubes per clip, zero included (more raises ValueError), without recapture and without host
+    synchronisation: slots and counts travel in one non-blocking copy out of two pinned blocks used in turn, each guarded by an event.  The
+    history carries "tubes_count"; its rows are slots, a clip's real tubes first."""
+
+    def __init__(self, args, base_net, context_net, nets, images, tubes, capacity=None):
         self.args, self.base, self.ctx, self.nets = args, base_net, context_net, nets
         dev = images.device
         self.images = images.clone()
-        flat, self.nums = _flat_tubes(tubes, dev)
-        self.flat0 = flat.clone()
+        self.capacity = None if capacity is None else int(capacity)
+        self.count = None
+        if self.capacity is not None:
+            if self.capacity < 1:
+                raise ValueError("step_amd: GraphedInference wants a capacity of at least one tube per clip")
+            B, K = len(tubes), self.capacity
+            W, H = float(args.image_size[0]), float(args.image_size[1])
+            flat, count = pad_tubes(tubes, K, "cpu", W, H)
+            self._T, self._whwh = flat.shape[1], (0.0, 0.0, W, H)
+            words = flat.numel()
+            # slots and counts lie in ONE buffer (the counts' int32 bits behind the slots), so that a call is one copy
+            self._slots = torch.empty(words + B, dtype=torch.float32, device=dev)
+            self.flat0, self.count = self._slots[:words].view(B * K, self._T, 5), self._slots[words:].view(torch.int32)
+            self._stage = [[torch.empty(words + B, dtype=torch.float32).pin_memory(), torch.cuda.Event(), False] for _ in range(2)]
+            self._stage_at = 0
+            self.nums = [K] * B
+            self._write_slots(flat, count)
+        else:
+            flat, self.nums = _flat_tubes(tubes, dev)
+            self.flat0 = flat.clone()
         self.clip_of = torch.as_tensor(np.repeat(np.arange(len(self.nums)), self.nums), device=dev)
         with torch.no_grad():
             s = torch.cuda.Stream(dev)
@@ -474,8 +547,22 @@ class GraphedInference:
     def _run(self):
         cf = self.base(self.images)
         cx = self.ctx(cf) if not self.args.no_context else None
-        hist, _ = inference_flat(self.args, cf, cx, self.nets, self.args.max_iter, self.flat0, self.nums, self.clip_of, want_classes=False)
+        hist, _ = inference_flat(self.args, cf, cx, self.nets, self.args.max_iter, self.flat0, self.nums, self.clip_of, want_classes=False,
+                                 counts=self.count)
         return hist, cf, cx
+
+    def _write_slots(self, flat, count):
+        """host (flat [B*K,T,5], count [B] int32) -> the captured buffers, through the next pinned block"""
+        st = self._stage[self._stage_at % 2]
+        self._stage_at += 1
+        if st[2] and not st[1].query():                                        # the copy that last read this block: finished before it is rewritten
+            st[1].synchronize()
+        words = flat.numel()
+        st[0][:words].copy_(flat.reshape(-1))
+        st[0][words:].view(torch.int32).copy_(count)
+        self._slots.copy_(st[0], non_blocking=True)
+        st[1].record(torch.cuda.current_stream(self._slots.device))
+        st[2] = True
 
     def __call__(self, images=None, tubes=None):
         # images: a new clip batch, copied into the captured input buffer -- or None / `self.images` itself when the caller (a decoder, the
@@ -483,7 +570,12 @@ class GraphedInference:
         # read + 138 MB written per step, ~1 % of it
         if images is not None and images.data_ptr() != self.images.data_ptr():
             self.images.copy_(images)
-        if tubes is not None:
+        if tubes is not None and self.capacity is not None:
+            if len(tubes) != len(self.nums):
+                raise ValueError("step_amd: GraphedInference was captured for %d clips, got %d" % (len(self.nums), len(tubes)))
+            self._write_slots(*pad_tubes([np.zeros((0, self._T, 4), np.float32) if len(t) == 0 else t for t in tubes], self.capacity, "cpu",
+                                         self._whwh[2], self._whwh[3]))
+        elif tubes is not None:
             flat, nums = _flat_tubes(tubes, self.images.device)
             assert nums == self.nums, "GraphedInference was captured for %s tubes per clip" % (self.nums,)
             self.flat0.copy_(flat)

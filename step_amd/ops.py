@@ -1084,13 +1084,14 @@ SAMPLING = {"uniform": 0, "random": 1, "softmax": 2}
 
 
 def select_train(cand, cand_first, cand_last, score, iou, clip_start, max_tubes, gt, gt_count, pad_tubes, rng, mid, before, after, topk,
-                 cls_thresh, reg_thresh, max_pos_num, neg_ratio, sampling, budget, out=None):
+                 cls_thresh, reg_thresh, max_pos_num, neg_ratio, sampling, budget, out=None, clip_count=None):
     """step_select_train: one training step's proposal selection for all clips on the device (include/step_amd.h has the rule).
     cand [N,Tc,4], cand_first / cand_last [N,Tw,4] | None (growing tubes), score [N,NC] | None (step 1), iou [N,Gmax] | None (the kernel
     computes it), clip_start [B+1] int32, max_tubes = the most tubes any clip has (host integer), gt [B,Gmax,F,4+NC], gt_count [B] int32,
     pad_tubes [B,Tout,4], rng a step_amd.rng.DeviceRNG (its offset advances by one on the device), sampling "uniform" | "random" |
     "softmax".  -> (sel [B*budget,Tout,5], tgt [B*budget,3,6+NC], mask [B*budget,1], inv [1], counts [B,2] int32); out = such a tuple
-    writes into the caller's (static) buffers.  No host synchronisation."""
+    writes into the caller's (static) buffers.  clip_count [B] int32 | None: padded clips (step_select_train_counted) -- the first
+    clip_count[b] rows of clip b's segment are real, the others are padding the rule never sees.  No host synchronisation."""
     L = _lib.lib()
     if sampling not in SAMPLING:
         raise NotImplementedError(sampling)
@@ -1099,8 +1100,8 @@ def select_train(cand, cand_first, cand_last, score, iou, clip_start, max_tubes,
     for name, t in tensors.items():
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
             raise RuntimeError("step_amd: select_train wants %s as a contiguous float32 tensor on %s" % (name, dev))
-    for name, t in (("clip_start", clip_start), ("gt_count", gt_count)):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+    for name, t in (("clip_start", clip_start), ("gt_count", gt_count), ("clip_count", clip_count)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev):
             raise RuntimeError("step_amd: select_train wants %s as a contiguous int32 tensor on %s" % (name, dev))
     if (cand_first is None) != (cand_last is None):
         raise RuntimeError("step_amd: select_train wants cand_first and cand_last together")
@@ -1110,6 +1111,8 @@ def select_train(cand, cand_first, cand_last, score, iou, clip_start, max_tubes,
     Tout = Tc + 2 * Tw
     if gt.dim() != 4 or gt.shape[0] != B or tuple(gt_count.shape) != (B,):
         raise RuntimeError("step_amd: select_train wants gt [B=%d,Gmax,F,4+NC] and gt_count [B], got %s, %s" % (B, tuple(gt.shape), tuple(gt_count.shape)))
+    if clip_count is not None and tuple(clip_count.shape) != (B,):
+        raise RuntimeError("step_amd: select_train wants clip_count [B=%d], got %s" % (B, tuple(clip_count.shape)))
     Gmax, F, NC = gt.shape[1], gt.shape[2], gt.shape[3] - 4
     want = {"cand_first": (N, Tw, 4), "cand_last": (N, Tw, 4), "score": (N, NC), "iou": (N, Gmax), "pad_tubes": (B, Tout, 4)}
     for name, shape in want.items():
@@ -1123,11 +1126,12 @@ def select_train(cand, cand_first, cand_last, score, iou, clip_start, max_tubes,
         if tuple(t.shape) != sh or t.dtype != (torch.int32 if k == 4 else torch.float32) or not t.is_contiguous() or t.device != dev:
             raise RuntimeError("step_amd: select_train output %d wants shape %s, got %s %s" % (k, sh, tuple(t.shape), t.dtype))
     sel, tgt, mask, inv, counts = out
-    _capi.check(L.step_select_train(_lib.dptr(cand), _lib.dptr(cand_first), _lib.dptr(cand_last), _lib.dptr(score), _lib.dptr(iou), N, Tc, Tw, NC,
+    _capi.check(L.step_select_train_counted(_lib.dptr(cand), _lib.dptr(cand_first), _lib.dptr(cand_last), _lib.dptr(score), _lib.dptr(iou), N, Tc, Tw, NC,
                                     _lib.dptr(clip_start), B, int(max_tubes), _lib.dptr(gt), _lib.dptr(gt_count), Gmax, F, _lib.dptr(pad_tubes),
                                     _lib.dptr(rng.state), int(mid), int(before), int(after), int(topk), float(cls_thresh), float(reg_thresh),
                                     int(max_pos_num), int(neg_ratio), SAMPLING[sampling], int(budget), _lib.dptr(sel), _lib.dptr(tgt),
-                                    _lib.dptr(mask), _lib.dptr(inv), _lib.dptr(counts), _lib.stream_ptr(dev)), "step_select_train")
+                                    _lib.dptr(mask), _lib.dptr(inv), _lib.dptr(counts), _lib.dptr(clip_count), _lib.stream_ptr(dev)),
+                "step_select_train_counted")
     return out
 
 

@@ -28,6 +28,24 @@ import numpy as np
 from .tube_math import extrapolate_tubes, valid_tubes
 
 
+def read_proposals(path, min_score=0.8):
+    """The person detector's proposals of a split (data/ava.py:199-230 get_proposals) -> {video: {frame id: [[x1, y1, x2, y2], ...]}},
+    percent boxes as Python floats.  A line is `video,fid,x1,y1,x2,y2,...,score`: the score is the LAST column, whatever stands between;
+    lines with score < min_score are dropped (a score of exactly min_score stays), and a box that repeats inside its frame is kept once,
+    boxes in first-seen order.  A frame without an entry falls back to the anchor grid in the loader (data/ava.py:342-358)."""
+    results = {}
+    with open(path) as fin:
+        for line in fin.read().splitlines():
+            cols = line.split(",")
+            if float(cols[-1]) < min_score:
+                continue
+            box = [float(v) for v in cols[2:6]]
+            boxes = results.setdefault(cols[0], {}).setdefault(int(cols[1]), [])
+            if box not in boxes:
+                boxes.append(box)
+    return results
+
+
 def box_iou(a, b):
     """IoU table [len(a), len(b)] of boxes [x1,y1,x2,y2] without the +1 pixel convention (tube_utils.py:269-306):
     zero unless both overlap extents are positive; degenerate pairs divide by zero like the reference (nan / inf)."""
@@ -155,6 +173,9 @@ def train_select(step, history, targets, tubes, args, device=None):
     sorts and the draws from the random streams, which decide WHICH tubes are trained on, stay here.  Same selections, bit for bit."""
     if args.temporal_mode not in ("predict", "extrapolate", "mean"):
         raise NotImplementedError("temporal_mode %r" % (args.temporal_mode,))
+    if history is not None and history.get("tubes_count") is not None:
+        raise ValueError("train_select: a padded history (tubes_count) belongs to the device selection (DeviceSelector.select(clip_count=...)); "
+                         "the host selection keeps its ragged form")
     chunks, max_chunks = args.NUM_CHUNKS[step], args.NUM_CHUNKS[args.max_iter]
     T = args.T
     t_start = int((max_chunks - chunks) / 2) * T
@@ -327,11 +348,12 @@ class DeviceSelector:
             self._gt_mid = (key, gt[:, :, mid, :4].contiguous())
         return self._gt_mid[1]
 
-    def select(self, step, history, gt, gt_count, init_flat, clip_start, pad_tubes, max_tubes=None):
+    def select(self, step, history, gt, gt_count, init_flat, clip_start, pad_tubes, max_tubes=None, clip_count=None):
         """history: the previous step's predictions (driver.inference_flat's entry; None at step 1); gt [B,Gmax,F,4+NC], gt_count [B]
         int32, init_flat [N,T,4] the initial tubes (step 1's candidates), clip_start [B+1] int32, pad_tubes [B,Tl,4] of THIS step -- all
         on the device.  max_tubes: the most tubes of one clip (default: read from clip_start the first time the table is seen).
-        -> (sel, tgt, mask, inv, counts), the step's static buffers."""
+        clip_count [B] int32 | None: padded clips -- clip_start describes the SLOTS, the first clip_count[b] of clip b's are real tubes
+        (step_select_train_counted; step_select_prepare runs over all slots).  -> (sel, tgt, mask, inv, counts), the step's static buffers."""
         from . import ops
         a = self.args
         chunks, max_chunks = a.NUM_CHUNKS[step], a.NUM_CHUNKS[a.max_iter]
@@ -351,7 +373,7 @@ class DeviceSelector:
         n_max = int(max_tubes) if max_tubes is not None else most
         return ops.select_train(cand, first, last, score, iou, clip_start, n_max, gt, gt_count, pad_tubes, self.rng, mid, before, after, a.topk,
                                 a.cls_thresh[step - 1], a.reg_thresh[step - 1], a.max_pos_num, a.neg_ratio, a.selection_sampling, self.budget,
-                                out=self.out[step])
+                                out=self.out[step], clip_count=clip_count)
 
 
 # ---- classification pre-training (train_cls.py: stage 1 of the reference's two-stage recipe) --------------------------------------------

@@ -13,7 +13,7 @@ from .driver import GraphedInference, inference, inference_flat, postprocess
 from .backbone import wgrad_into_grad
 from .optim import FlatAdam, FlatSGD
 from .selection import DeviceClsSelector, DeviceSelector, cls_select, sample_anchors, train_select
-from .driver import _flat_tubes
+from .driver import _flat_tubes, pad_tubes
 from .tube_math import ANCHOR_MODES, anchor_tubes, generate_anchors
 
 
@@ -409,13 +409,24 @@ class C4SelectTrainStep(C4TrainStep):
     [B,T,Hs,Ws,3] (src_size) is the iteration's input -- the captured one -- and the front begins with the planner, the noise fill and
     step_clip_augment_u8, which write the clip `x` AND the ground truths the selector reads (`d_gt`, `d_gt_count`: the tubes the crop kept,
     in pixels of the network's resolution), both from the same draws; `d_gt_in` / `d_gt_count_in` hold the loader's percent boxes.  Two
-    more offsets of the generator per iteration.  An augmentation built with rng=None draws from the workload's generator."""
+    more offsets of the generator per iteration.  An augmentation built with rng=None draws from the workload's generator.
+
+    proposals=K (opt-in, selection="device" only): the initial tubes are a person detector's PROPOSALS, whose number changes from key frame
+    to key frame, instead of the anchor grid (train.py:85-86, data/ava.py:320-358).  A clip owns K slots, the first `d_count[b]` real, the
+    others the whole frame; `d_prop_in` [B,K,T,4] (percent) and `d_prop_count` [B] hold what the loader read -- synthetic here, drawn from
+    the seed: counts from 0 to K, with B > 1 at least one clip at 0, which falls back to `d_fill`, the first min(34, K) anchors.  With
+    augment= the front's planner transforms them with the frames (apply(tubes=...): the step-1 candidates and their count are written by the
+    iteration itself); without, they are scaled once.  The no-grad inference runs over B * K slots with the counts, the selector gets
+    clip_count.  set_proposals(list of [n_i,T,4] percent arrays) feeds the next iteration's proposals into the static buffers: no
+    recapture.  The ragged step() runs the host selection on the real ragged lists."""
 
     def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, tubes_per_clip=34, capturable=False, force_exchange=False, budget=None,
                  optimizer="adam", dropout=0.0, rng_seed=0, selection="host", grad_wire="fp32", wire_feedback=True, max_grad_norm=None,
-                 lr_schedule=None, augment=None, src_size=(256, 340)):
+                 lr_schedule=None, augment=None, src_size=(256, 340), proposals=None):
         if selection not in ("host", "device"):
             raise ValueError("C4SelectTrainStep: selection is 'host' or 'device', got %r" % (selection,))
+        if proposals is not None and (selection != "device" or int(proposals) < 1):
+            raise ValueError("C4SelectTrainStep: proposals=K (K >= 1 slots per clip) needs selection='device' (the host selection keeps its ragged form)")
         if augment is not None and selection != "device":
             raise ValueError("C4SelectTrainStep: augment= needs selection='device' (the host selection reads ground truths the device cannot hand it)")
         super().__init__(dev, batch=batch, tubes_per_clip=5, seed=seed, max_iter=3, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
@@ -433,6 +444,27 @@ class C4SelectTrainStep(C4TrainStep):
                     t[g_, c, :4] = box + rs.uniform(-5, 5, 4).astype(np.float32)
                 t[g_, :, 4 + rs.randint(0, 60, 3)] = 1
             self.gt.append(t)
+        self.proposals = None if proposals is None else int(proposals)
+        if self.proposals is not None:
+            K_, W_, H_ = self.proposals, float(self.args.image_size[0]), float(self.args.image_size[1])
+            self.fill = generate_anchors()[:min(34, K_)].astype(np.float32)                      # percent boxes: the fallback of data/ava.py:342-358
+            cnt = rs.randint(1, K_ + 1, batch)
+            if batch > 1:
+                cnt[-1] = 0
+            gt_pct = [t[:, :, :4] / np.array([W_, H_, W_, H_], np.float32) for t in self.gt]
+            props = []
+            for b in range(batch):                               # half of a clip's proposals sit on its ground truths, the others anywhere
+                p = np.zeros((int(cnt[b]), 3, 4), np.float32)
+                for j in range(int(cnt[b])):
+                    if j % 2 == 0:
+                        box = gt_pct[b][(j // 2) % 2, 1] + rs.uniform(-0.03, 0.03, 4)
+                    else:
+                        xy = rs.uniform(0.0, 0.6, 2)
+                        box = np.concatenate([xy, xy + rs.uniform(0.15, 0.35, 2)])
+                    p[j] = box[None, :] + rs.uniform(-0.01, 0.01, (3, 4))
+                props.append(p)
+            self._props = props
+            self.init_tubes = self._scaled(props)
         self.selection = selection
         self.selection_ran = None                                # "host" | "device": the selection of the LAST iteration (step() before capture() is the ragged form: host)
         self._selected = []
@@ -440,7 +472,12 @@ class C4SelectTrainStep(C4TrainStep):
         self.budget = int(budget or a.max_pos_num * (1 + a.neg_ratio))
         # static state of the padded form
         K = batch * self.budget
-        self.flat0, self.nums0 = _flat_tubes(self.init_tubes, dev)
+        if self.proposals is None:
+            self.flat0, self.nums0 = _flat_tubes(self.init_tubes, dev)
+            self.d_count = None
+        else:
+            self.flat0, self.d_count = pad_tubes(self.init_tubes, self.proposals, dev, *self.args.image_size[:2])
+            self.nums0 = [self.proposals] * batch
         self.clip_of0 = torch.as_tensor(np.repeat(np.arange(batch), self.nums0), device=dev)
         self.clip_of_pad = torch.arange(batch, device=dev).repeat_interleave(self.budget)
         self.s_flat, self.s_tgt, self.s_mask, self.s_inv = [], [], [], []
@@ -448,7 +485,11 @@ class C4SelectTrainStep(C4TrainStep):
         self.pad = []                                            # per step [B, Tl, 4]: the clip's first initial tube, a valid box for the padded slots' ROIAlign
         for i in range(1, a.max_iter + 1):
             Tl = a.NUM_CHUNKS[i] * a.T                           # (the last step's tubes are 3 chunks long)
-            self.pad.append(np.stack([np.tile(np.asarray(t[0], np.float32), (Tl // t.shape[1] + 1, 1))[:Tl] for t in self.init_tubes]))
+            if self.proposals is None:
+                self.pad.append(np.stack([np.tile(np.asarray(t[0], np.float32), (Tl // t.shape[1] + 1, 1))[:Tl] for t in self.init_tubes]))
+            else:                                                # (a clip's first proposal changes under the graph: the first anchor, the anchor form's pad)
+                wh = np.array([a.image_size[0], a.image_size[1]] * 2, np.float32)
+                self.pad.append(np.tile(self.fill[0] * wh, (batch, Tl, 1)))
             for dst, host, shape in ((self.s_flat, self.h_flat, (K, Tl, 5)), (self.s_tgt, self.h_tgt, (K, 3, 6 + a.num_classes)),
                                      (self.s_mask, self.h_mask, (K, 1)), (self.s_inv, self.h_inv, (1,))):
                 dst.append(torch.zeros(shape, device=dev) if selection == "host" else None)     # (device: the selector's own buffers, below)
@@ -479,6 +520,12 @@ class C4SelectTrainStep(C4TrainStep):
             self.d_gt_in = self.d_gt.clone()                     # what the loader reads: percent boxes (data/ava.py:283-296)
             self.d_gt_in[..., :4] = (self.d_gt[..., :4] / whwh).clamp_(0.0, 1.0)
             self.d_gt_count_in = self.d_gt_count.clone()
+        if self.proposals is not None:
+            self.d_prop_in = torch.zeros((batch, self.proposals, 3, 4), device=dev)
+            self.d_prop_count = torch.zeros(batch, dtype=torch.int32, device=dev)
+            self.d_fill = torch.from_numpy(self.fill).to(dev)
+            self.d_init_slots = self.d_init.view(batch, self.proposals, 3, 4)     # (what the planner writes: the selector's step-1 candidates)
+            self.set_proposals(self._props)
         self._gF = self._gB = None
         self._front = None
 
@@ -492,6 +539,41 @@ class C4SelectTrainStep(C4TrainStep):
     @selected.setter
     def selected(self, value):
         self._selected = value
+
+    def _scaled(self, props):
+        """percent proposals per clip -> the ragged pixel tubes of the form without augmentation: scale_tubes_abs; a clip without any gets
+        the fill (data/ava.py:342-362)"""
+        W, H = float(self.args.image_size[0]), float(self.args.image_size[1])
+        out = []
+        for p in props:
+            p = np.asarray(p, np.float64).reshape(-1, 3, 4)
+            if p.shape[0] == 0:
+                p = np.repeat(self.fill.astype(np.float64)[:, None, :], 3, axis=1)
+            out.append((np.minimum(np.maximum(p, 0.0), 1.0) * np.array([W, H, W, H])).astype(np.float32))
+        return out
+
+    def set_proposals(self, props):
+        """props: per clip an array [n_i,T,4] of percent boxes, 0 <= n_i <= K (an empty clip falls back to the fill): the NEXT iteration's
+        proposals, written into the static buffers the eager and the captured forms read -- no recapture.  With augment= they go to the
+        planner's inputs; without, they are scaled here and go to the slots themselves."""
+        if self.proposals is None:
+            raise RuntimeError("C4SelectTrainStep: set_proposals needs a workload built with proposals=K")
+        K, B = self.proposals, self.batch
+        props = [np.asarray(p, np.float32).reshape(-1, 3, 4) for p in props]
+        if len(props) != B or any(p.shape[0] > K for p in props):
+            raise ValueError("C4SelectTrainStep: set_proposals takes %d clips of at most %d proposals" % (B, K))
+        self._props = props
+        self.init_tubes = self._scaled(props)
+        host = np.zeros((B, K, 3, 4), np.float32)
+        for b, p in enumerate(props):
+            host[b, :p.shape[0]] = p
+        self.d_prop_in.copy_(torch.from_numpy(host))
+        self.d_prop_count.copy_(torch.tensor([p.shape[0] for p in props], dtype=torch.int32))
+        if self.augment is None:
+            flat, count = pad_tubes(self.init_tubes, K, "cpu", *self.args.image_size[:2])
+            self.flat0.copy_(flat)
+            self.d_count.copy_(count)
+            self.d_init.copy_(self.flat0[:, :, 1:])
 
     def select_counts(self):
         """device selection: [max_iter, B, 2] (positives, negatives) of the last iteration, on the host; synchronises"""
@@ -535,13 +617,20 @@ class C4SelectTrainStep(C4TrainStep):
         """backbone + ContextNet (with gradients) and the no-grad, eval-mode inference over the first max_iter - 1 steps (train.py:266-272)"""
         a = self.args
         if self.augment is not None:                            # decisions, noise, pixels and boxes of this iteration, from the same two offsets
-            self.augment.apply(self.stage, self.d_gt_in, self.d_gt_count_in, out=self.x, gt_out=self.d_gt, gt_count_out=self.d_gt_count)
+            if self.proposals is None:
+                self.augment.apply(self.stage, self.d_gt_in, self.d_gt_count_in, out=self.x, gt_out=self.d_gt, gt_count_out=self.d_gt_count)
+            else:                                               # ... and the proposals: the step-1 candidates, their count, the inference's slots
+                self.augment.apply(self.stage, self.d_gt_in, self.d_gt_count_in, out=self.x, gt_out=self.d_gt, gt_count_out=self.d_gt_count,
+                                   tubes=self.d_prop_in, tube_count=self.d_prop_count, fill=self.d_fill, tubes_out=self.d_init_slots,
+                                   tube_count_out=self.d_count)
+                self.flat0[:, :, 1:].copy_(self.d_init)
         cf = self.base(self.x)
         cx = self.ctx(cf)
         for m in self.mods:
             m.eval()
         with torch.no_grad():
-            history, _ = inference_flat(a, cf.detach(), cx.detach(), self.nets, a.max_iter - 1, self.flat0, self.nums0, self.clip_of0, want_classes=False)
+            history, _ = inference_flat(a, cf.detach(), cx.detach(), self.nets, a.max_iter - 1, self.flat0, self.nums0, self.clip_of0, want_classes=False,
+                                        counts=self.d_count)
         for m in self.mods:
             m.train()
         return cf, cx, history
@@ -555,7 +644,7 @@ class C4SelectTrainStep(C4TrainStep):
             self.selection_ran = "device"
             for i in range(1, a.max_iter + 1):
                 self.selector.select(i, history[i - 2] if i > 1 else None, self.d_gt, self.d_gt_count, self.d_init, self.d_clip_start,
-                                     self.d_pad[i - 1], max_tubes=max(self.nums0))
+                                     self.d_pad[i - 1], max_tubes=max(self.nums0), clip_count=self.d_count)
             return
         self.selected = []
         self.selection_ran = "host"

@@ -13,10 +13,13 @@ device events after a warm-up, the forms alternated round by round, the spread (
 --device-plan runs another leg INSTEAD: the decisions of the same batch made on the device (step_augment_plan: planner + noise fill, timed
 between device events) beside the host form (`.plan` per clip + pack + the copy of the block, wall time up to the copy's completion), rounds
 alternated; and with --train-runs K, train_step_amd.py --feed u8 --augment --select-device against --feed u8 --augment-device
---select-device at 1 and 8 clips per GPU, child processes alternated, K runs each, each form's own spread beside its median.
+--select-device at 1 and 8 clips per GPU, child processes alternated, K runs each, each form's own spread beside its median.  With
+--plan-tubes P the leg also times planner + fill WITH P proposals per clip (step_augment_plan_tubes) against the same call without tubes,
+at 1 and 8 clips, rounds alternated.
 
     python tools/augment_bench.py [--out profiles/clip_augment_timing.txt] [--train-runs 3]
     python tools/augment_bench.py --device-plan --train-runs 3 --out profiles/augment_plan_timing.txt
+    python tools/augment_bench.py --device-plan --plan-tubes 34
 """
 import argparse
 import ctypes
@@ -40,6 +43,7 @@ ap.add_argument("--train-runs", type=int, default=0)
 ap.add_argument("--train-iters", type=int, default=60)
 ap.add_argument("--np-clips", type=int, default=2, help="clips the numpy restatement is timed on")
 ap.add_argument("--device-plan", action="store_true", help="the step_augment_plan leg instead of the kernel forms (see above)")
+ap.add_argument("--plan-tubes", type=int, default=0, metavar="P", help="--device-plan: also time the planner with P proposals per clip")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "tools/augment_bench.py needs a ROCm device"
 dev = torch.device("cuda:0")
@@ -136,6 +140,34 @@ if a.device_plan:
     say("  host:   .plan x %d, median %.3f ms per batch (min %.3f .. max %.3f); pack + copy of the block, %.3f ms (min %.3f .. max %.3f; ~%d bytes)"
         % (N, float(np.median(host_plan)), min(host_plan), max(host_plan), float(np.median(host_copy)), min(host_copy), max(host_copy), int(np.median(blk_bytes))))
     res = {"device_plan_ms": dev_ms, "host_plan_ms": host_plan, "host_pack_copy_ms": host_copy}
+    if a.plan_tubes:
+        P, Tp = a.plan_tubes, 3
+        xy = rs.uniform(0.0, 0.6, (N, P, 1, 2))
+        props = np.tile(np.concatenate([xy, xy + rs.uniform(0.15, 0.35, (N, P, 1, 2))], 3), (1, 1, Tp, 1)).astype(np.float32)
+        d_props, d_pcnt = torch.from_numpy(props).to(dev), torch.from_numpy(rs.randint(0, P + 1, N).astype(np.int32)).to(dev)
+        d_fill = torch.from_numpy(np.tile(np.array([[0.1, 0.1, 0.8, 0.8]], np.float32), (min(P, 34), 1))).to(dev)
+        t_out, tc_out = torch.empty_like(d_props), torch.empty_like(d_pcnt)
+
+        def plan_tubes(n, with_tubes):
+            t = (_lib.dptr(d_props), _lib.dptr(d_pcnt), P, Tp, _lib.dptr(d_fill), d_fill.shape[0], _lib.dptr(t_out), _lib.dptr(tc_out)) if with_tubes \
+                else (None, None, 0, 0, None, 0, None, None)
+            _capi.check(L.step_augment_plan_tubes(_lib.dptr(src), _lib.dptr(dims), _lib.dptr(d_gt), _lib.dptr(d_cnt), n, 2, T, NC, 15, 2, Wo, Ho, Hs * Ws,
+                                                  _lib.dptr(dev_aug.rng.state), _lib.dptr(block), _lib.dptr(g_out), _lib.dptr(c_out), *t,
+                                                  _lib.stream_ptr(dev)), "step_augment_plan_tubes")
+
+        say("planner + noise fill with %d proposal slots per clip x %d frames (counts %s) against the same call without tubes; %d rounds x %d launches, alternated"
+            % (P, Tp, d_pcnt.tolist(), a.rounds, a.launches))
+        for n in (1, 8):
+            forms = {"without tubes": lambda: plan_tubes(n, False), "with tubes": lambda: plan_tubes(n, True)}
+            for fn in forms.values():
+                timed(fn, 10)
+            ms = {k: [] for k in forms}
+            for _ in range(a.rounds):
+                for k, fn in forms.items():
+                    ms[k].append(timed(fn, a.launches))
+            for k, v in ms.items():
+                say("  %d clip(s), %-14s median %.4f ms per batch (min %.4f .. max %.4f)" % (n, k + ":", float(np.median(v)), min(v), max(v)))
+            res["plan_tubes_%d" % n] = ms
     if a.train_runs:
         del frames, out
         torch.cuda.empty_cache()

@@ -21,7 +21,9 @@ Every rank
      --dropout P trains with the heads' dropout (the reference's recipe: 0.3) on the device-side generator: the captured step draws new masks
      on every replay (`step_amd.Dropout`, `step_amd.rng`); --rng-seed S seeds it, rank r with S + r,
      --select-device trains on the reference's whole iteration with the proposal selection on the device, drawing from the same generator: one
-     graph per iteration instead of two around the host's selection,
+     graph per iteration instead of two around the host's selection; --proposals K starts it from detector proposals instead of the anchor
+     grid -- a changing number per clip in K padded slots with a device-side count (`step_select_train_counted`), transformed with the
+     frames under --augment-device (`step_augment_plan_tubes`),
      --cls trains the classification pre-training iteration instead (train_cls.py, the stage whose checkpoint the iteration above starts from): one
      cls_only head on boxes sampled around the ground truths, ONE graph per iteration; the host draws sampling and selection before each
      replay, --cls --select-device moves both into the graph (`step_anchor_sample`, `step_select_train`),
@@ -108,6 +110,10 @@ def main():
     ap.add_argument("--augment-device", action="store_true",
                     help="--feed u8 --select-device only: the augmentation's decisions, erase noise and transformed ground truths are made on the device "
                          "too (step_augment_plan, draws from the generator of --rng-seed, not numpy's), inside the captured iteration")
+    ap.add_argument("--proposals", type=int, default=0, metavar="K",
+                    help="--select-device only: the initial tubes are detector proposals, a changing number per clip in K padded slots with a "
+                         "device-side count (synthetic here; a clip without any falls back to the anchors), instead of the anchor grid; with "
+                         "--augment-device the planner transforms them with the frames")
     ap.add_argument("--src-size", default="256x340", help="--augment / --augment-device: HxW of the decoded source frames")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
@@ -125,6 +131,8 @@ def main():
     if a.augment_device and (a.feed != "u8" or not a.select_device or a.cls or a.augment):
         raise SystemExit("train_step_amd.py: --augment-device needs --feed u8 --select-device (the device selection reads the boxes the planner "
                          "writes), without --cls and --augment")
+    if a.proposals and (a.proposals < 0 or not a.select_device or a.cls):
+        raise SystemExit("train_step_amd.py: --proposals K needs --select-device (the host selection keeps its ragged form), without --cls, and K >= 1")
     if a.scheduler and a.lr_decay_every:
         raise SystemExit("train_step_amd.py: --scheduler and --lr-decay-every both write the learning rate; pick one")
     if a.clip_grad_norm is not None and not a.clip_grad_norm > 0:
@@ -174,6 +182,8 @@ def main():
         if a.augment_device:                                     # (400 x 400: the workload's clips; the generator is the workload's)
             extra.update(augment=step_amd.DeviceTubeAugmentation((400, 400), do_flip=True, do_crop=True, do_photometric=True, do_erase=True, scale=2),
                          src_size=tuple(int(v) for v in a.src_size.lower().split("x")))
+        if a.proposals:
+            extra.update(proposals=a.proposals)
         w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=capturable, optimizer=a.optimizer,
                                         dropout=a.dropout, rng_seed=a.rng_seed + rank, selection="device" if a.select_device else "host",
                                         grad_wire=a.grad_wire, wire_feedback=not a.no_wire_feedback, **extra)
@@ -295,7 +305,8 @@ def main():
                           "gradient_exchange": _exchange_label(w, world),
                           "grad_wire": a.grad_wire, "exchange_bytes_per_step": w.opt.numel * (2 if a.grad_wire == "bf16" else 4), "param_checksum": checksum,
                           "feed": a.feed + ("+augment" if a.augment else "+augment-device" if a.augment_device else ""),
-                          **({"gt_kept": int(w.d_gt_count.sum().item())} if a.augment_device else {}), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
+                          **({"gt_kept": int(w.d_gt_count.sum().item())} if a.augment_device else {}),
+                          **({"proposals": a.proposals, "proposals_real": int(w.d_count.sum().item())} if a.proposals else {}), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
                           "dropout": a.dropout, "rng_offset": w.rng.offset(), **({"selection": w.selection_ran} if (a.select or a.cls) else {}),
                           **({"workload": "cls"} if a.cls else {}),
                           **({"clip_grad_norm": a.clip_grad_norm, "grad_norm": round(float(w.opt.grad_norm[0]), 6)} if a.clip_grad_norm is not None else {}),
