@@ -52,7 +52,7 @@ enum {
     STEP_E_ALIGN = -5
 };
 
-/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (45: step_grad_norm_flat / step_grad_clip_flat / step_lr_schedule). */
+/* Library identity: returns "step_amd <version> gfx950"; abi is bumped on any signature change (49: step_pool_then_conv_forward / step_pool_then_conv_plan). */
 STEP_API const char* step_version(void);
 STEP_API int step_abi_version(void);
 
@@ -114,6 +114,9 @@ enum {
     STEP_OPT_CONV_GROUP_NARROW,/*  1 (default): the narrow 3x3x3 members of step_conv_forward_group (Cin <= 32, Cout <= 96: an Inception block's branch_2) run the
                                     pixel-split body (512-pixel boxes, both wave groups on pixels, no zero k16 step) where the measured rule of conv_igemm.hip admits
                                     their map | 2: wherever the form is eligible (tests / A-B) | 0: every member on the partner's instantiation (bit-identical) */
+    STEP_OPT_POOL_THEN_CONV,   /*  1 (default): step_pool_then_conv_forward / step_pool_then_conv_plan take the one-launch form (a 3x3x3 / 1 max pool and the pointwise
+                                    conv behind it; the pooled tensor never exists) where the map gives the chip enough workgroups (the rule of conv_igemm.hip) |
+                                    2: wherever the form is eligible (tests / A-B) | 0: never (the caller launches pool and conv; bit-identical) */
     STEP_OPT_COUNT_
 };
 STEP_API int step_set_option(int option, int value);
@@ -291,8 +294,8 @@ STEP_API int step_eval_ap(const long long* cls_start, const uint8_t* label, cons
  *  sums, rounding to 16-bit storage overflows to inf (no saturation), and ReLU PROPAGATES a NaN of either sign and sends -0 and
  *  every negative value to +0 (relu_nan, csrc/common.h; never fmaxf, which would replace a NaN by 0).  Only image pixels and the
  *  Cin channels of the slice are operands: neighbour channels, zero-weight padding taps and K slots are never multiplied, so an
- *  inf beside the operands cannot turn into inf x 0 = NaN.  Every fused form (_pre, _pre_pool, _group, _cat, step_pool_conv_forward)
- *  gives the bits of its separate calls, NaN for NaN.
+ *  inf beside the operands cannot turn into inf x 0 = NaN.  Every fused form (_pre, _pre_pool, _group, _cat, step_pool_conv_forward,
+ *  step_pool_then_conv_forward) gives the bits of its separate calls, NaN for NaN.
  */
 typedef struct step_conv_desc {
     int dtype;                 /* STEP_F32 | STEP_BF16 | STEP_F16 (activations and packed weights) */
@@ -369,6 +372,20 @@ STEP_API int step_pool_conv_forward(int dtype, const void* x, int N, int D, int 
 /* What step_pool_conv_forward would do with the conv d: 0 = no combined form (the caller launches pool and conv separately), 1 | 2 = the
  * accumulator depth of its pointwise workgroups (64 | 128 output channels each; the kernel's second template argument). */
 STEP_API int step_pool_conv_plan_nb(const step_conv_desc* d);
+
+/* An Inception block's branch_3 as ONE launch: the 3x3x3 / 1 TF-SAME max pool of x [N,D,H,W,x_cstride] (channels [x_coff, x_coff + d->Cin))
+ * and the pointwise conv d of the POOLED tensor (models/i3dpt.py:151-155); the pooled tensor is never written.  d describes the conv
+ * (its N, D, H, W must be the call's; its x_cstride / x_coff describe the same input slice); y, scale, shift, w_packed as in
+ * step_conv_forward.  Bit-identical to step_maxpool3d_tf followed by step_conv_forward (the pool's maxima are exact, the conv keeps one
+ * fp32 accumulator per output with K ascending).  The form that exists: 16-bit storage, a 1x1x1 conv, Cin % 8 == 0 and <= 256,
+ * Cout % 8 == 0 and <= 64, channel strides / offsets % 8 == 0, no split, and -- under option pool_then_conv = 1 -- a map of enough
+ * tiles to fill the chip; otherwise STEP_E_UNSUPPORTED, and STEP_E_ALIGN for a pointer off the 16-byte grid, before any launch (the
+ * caller launches pool and conv).  N == 0: STEP_OK. */
+STEP_API int step_pool_then_conv_forward(int dtype, const void* x, int N, int D, int H, int W, int x_cstride, int x_coff, const step_conv_desc* d,
+                                         const void* w_packed, const float* scale, const float* shift, void* y, step_stream_t stream);
+/* What step_pool_then_conv_forward would do with d under the current options: 0 = no such form, 1 | 2 = the 32-channel output blocks of
+ * its workgroups (the kernel's second template argument). */
+STEP_API int step_pool_then_conv_plan(const step_conv_desc* d);
 
 /* step_conv_forward over the channel CONCAT of two tensors that is never materialised (round 6): the reference's resample Bottleneck
  * applies conv1 / conv2 to torch.cat((global_feat, downsampled), 1) (models/two_branch.py:86-111, 313-319); here d->Cin = cin_a + cin_b,

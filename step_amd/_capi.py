@@ -5,7 +5,7 @@ import ctypes as C
 F32, BF16, F16 = 0, 1, 2
 NCHW, NHWC = 0, 1
 ROI_BWD_GATHER, ROI_BWD_ATOMIC = 0, 1
-ABI_VERSION = 48
+ABI_VERSION = 49
 
 vp, fp, ip, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # raw device addresses
 i, f, ll, sz = C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -72,6 +72,8 @@ SIGNATURES = {
     "step_conv_workspace_bytes": (sz, [C.POINTER(ConvDesc)]),
     "step_pool_conv_forward": (i, [i, vp, i, i, i, i, i, i, i, vp, i, i, C.POINTER(ConvDesc), vp, vp, fp, fp, vp, vp, vp]),
     "step_pool_conv_plan_nb": (i, [C.POINTER(ConvDesc)]),
+    "step_pool_then_conv_forward": (i, [i, vp, i, i, i, i, i, i, C.POINTER(ConvDesc), vp, fp, fp, vp, vp]),
+    "step_pool_then_conv_plan": (i, [C.POINTER(ConvDesc)]),
     "step_conv_forward_cat": (i, [C.POINTER(ConvDesc), vp, i, vp, i, i, vp, fp, fp, vp, vp, vp, vp]),
     "step_conv_forward_pre": (i, [C.POINTER(ConvDesc), vp, vp, fp, fp, vp, fp, fp, i, vp, vp]),
     "step_conv_pre_pool_workspace_bytes": (sz, [C.POINTER(ConvDesc)]),
@@ -171,7 +173,8 @@ def check(status, what):
 # ---- planner options (include/step_amd.h: step_set_option) -----------------------------------------------------------
 OPTION_IDS = {name: k for k, name in enumerate((
     "conv_impl", "conv_nb", "conv_waves", "conv_phased", "conv_gen", "conv_gmode", "conv_pws", "conv_splitk", "conv_tail",
-    "conv_slots", "pool_direct", "wgrad_minpix", "wgrad16_lds", "conv_group_pw", "clip_vec", "conv_nb_rule", "throughput", "conv_persist", "conv_pws_waves", "conv_group_narrow"))}
+    "conv_slots", "pool_direct", "wgrad_minpix", "wgrad16_lds", "conv_group_pw", "clip_vec", "conv_nb_rule", "throughput", "conv_persist", "conv_pws_waves", "conv_group_narrow",
+    "pool_then_conv"))}
 
 
 def set_option(lib, name, value):

@@ -828,13 +828,21 @@ class Mixed(nn.Module):
             # 32-88 CUs idle and the library appends its workgroups to their grid (elsewhere it is launched behind them)
             pool = self.branch_3[0]
             p = self._fused(x, out[..., :c0], t, pool=POOL_WITH_POINTWISE and pool.kernel_size == (3, 3, 3) and pool.stride == (1, 1, 1))
+            u1, u2, u3 = self.branch_1[1]._unit, self.branch_2[1]._unit, self.branch_3[1]._unit
+            def member(u, xin, o):
+                scale, shift = u.affine()
+                return (xin, u.packed(x.dtype), u.cout, u.k, scale, None if shift is None else shift.detach().contiguous(), True, o)
+            m = [member(u1, t[..., :oc[1]], out[..., c0:c1]), member(u2, t[..., oc[1]:], out[..., c1:c2])]
+            if p is None and POOL_THEN_POINTWISE and pool.kernel_size == (3, 3, 3) and pool.stride == (1, 1, 1):
+                # the pool did not ride with the triple (the 28x28 and larger maps): pool and branch_3's 1x1x1 conv as ONE launch where the
+                # library has that form -- the pooled tensor never exists and the grouped launch carries the two 3x3x3 members only
+                b3 = member(u3, x, out[..., c2:])
+                if ops.pool_then_conv_forward(x, b3[1], b3[2], b3[4], b3[5], True, b3[7]) is not None:
+                    ops.conv_forward_group(m)
+                    return out
             if p is None:
                 p = pool(x)
-            u1, u2, u3 = self.branch_1[1]._unit, self.branch_2[1]._unit, self.branch_3[1]._unit
-            m = []
-            for u, xin, o in ((u1, t[..., :oc[1]], out[..., c0:c1]), (u2, t[..., oc[1]:], out[..., c1:c2]), (u3, p, out[..., c2:])):
-                scale, shift = u.affine()
-                m.append((xin, u.packed(x.dtype), u.cout, u.k, scale, None if shift is None else shift.detach().contiguous(), True, o))
+            m.append(member(u3, p, out[..., c2:]))
             ops.conv_forward_group(m)
             return out
         # The branches are independent: run them on three HIP streams (fork/join with events -- under
@@ -871,6 +879,7 @@ class Mixed(nn.Module):
 
 
 POOL_WITH_POINTWISE = True     # inference: an Inception block's max pool and its fused 1x1x1 triple as one launch where the library has the form
+POOL_THEN_POINTWISE = True     # inference: where the pool did not ride with the triple, branch_3's pool + 1x1x1 conv as one launch, no pooled tensor (ops.pool_then_conv_forward; module switch for A/B)
 FUSE_STEM_POOL = True          # inference: maxPool3d_2a is taken on the stem's tiles while they are on the chip (ops.stem_pool_forward)
 FUSE_STEM_U8 = False           # BaseNet.forward_u8: True = the stem stages uint8 frames itself (ops.stem_pool_forward_u8, bit-identical); False (default) = one conversion
                                # pass in front -- MEASURED: the table look-ups in the stem's frame staging cost more than the pass they save (fed C2 6.75 k against 6.96 k clips/s)

@@ -62,6 +62,11 @@ struct ConvParams {
 int pool333_pw_launch(int dtype, const void* x, int N, int D, int H, int W, int C, int x_cstride, int x_coff, void* y, int y_cstride, int y_coff,
                       ConvParams cp, long long conv_blocks, int nbc, step_stream_t stream);
 
+// pool.hip: the 3x3x3 / 1 max pool and the pointwise conv of the POOLED tensor as one launch (pool333_then_pw_kernel; cp = the conv's parameter
+// block, N / D the clip axes unfolded); the workgroups that launch would have
+int pool333_then_pw_launch(int dtype, const void* x, int N, int D, int H, int W, int x_cstride, int x_coff, const ConvParams& cp, step_stream_t stream);
+long long pool333_then_pw_blocks(int N, int D, int H, int W);
+
 constexpr int CONV_GROUP_MAX = 2;
 // pw (conv_tap_group_pw_kernel only): a pointwise conv whose 256-thread workgroups follow the members' in the same grid (pw.gbase =
 // the members' total) -- a branch's 1x1x1 conv running on the CUs the 3x3x3 members leave idle

@@ -949,6 +949,50 @@ int step_pool_conv_forward(int dtype, const void* x, int N, int D, int H, int W,
     return pool333_pw_launch(dtype, x, N, D, H, W, C, x_cstride, x_coff, pool_y, py_cstride, py_coff, p, tot, nbc, stream);
 }
 
+// step_pool_then_conv_forward's form for the conv d (0: none | the 32-channel output blocks per workgroup).  Which maps (STEP_OPT_POOL_THEN_CONV
+// = 1): every workgroup of the kernel walks all input channels of a 14 x 14 tile of one plane and two of them fit a CU, so the launch stands
+// against a pool and a conv that each fill the chip only where its workgroups fill whole rounds of the chip's POOL_THEN_CONV_SLOTS places
+// (profiles/r08_pool_bench.txt: C2's 28x28 maps of 8 clips are 512 workgroups = one round, 3b 33.4 -> 24.6 us; the 50x50
+// maps of 4 AVA clips are 1152 = 2.25 rounds, 3b 52.5 -> 55.4 us).
+constexpr long long POOL_THEN_CONV_SLOTS = 512;
+static int pool_then_conv_nbc(const step_conv_desc* d) {
+    const int mode = opt(STEP_OPT_POOL_THEN_CONV);
+    if (!d || mode == 0 || (d->dtype != STEP_BF16 && d->dtype != STEP_F16) || !(d->kd == 1 && d->kh == 1 && d->kw == 1)) return 0;
+    if (d->N <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return 0;
+    if (d->Cin % 8 || d->Cin > 256 || d->Cout % 8 || d->Cout > 64 || (d->split > 0 && d->split < d->Cout)) return 0;
+    if (d->x_cstride % 8 || d->x_coff % 8 || d->y_cstride % 8 || d->y_coff % 8) return 0;
+    if ((long long)d->H * d->W * (d->x_cstride > d->y_cstride ? d->x_cstride : d->y_cstride) > 0x7fffffffLL) return 0;        // (32-bit offsets inside a plane)
+    const int nbc = ceil_div(d->Cout, 32);
+    if (mode == 1) {
+        const long long blocks = pool333_then_pw_blocks(d->N, d->D, d->H, d->W), rounds = ceil_div64(blocks, POOL_THEN_CONV_SLOTS);
+        if (blocks * 2 < POOL_THEN_CONV_SLOTS || blocks * 10 < rounds * POOL_THEN_CONV_SLOTS * 9) return 0;      // at least half a round, rounds >= 90 % full
+#ifdef STEP_EXP_PTP_ONLY_NBC                                   // (timing experiments, tools/step_ab.py lib=...: never the product library)
+        if (nbc != STEP_EXP_PTP_ONLY_NBC) return 0;
+#endif
+    }
+    return nbc;
+}
+
+int step_pool_then_conv_plan(const step_conv_desc* d) { return pool_then_conv_nbc(d); }
+
+int step_pool_then_conv_forward(int dtype, const void* x, int N, int D, int H, int W, int x_cstride, int x_coff, const step_conv_desc* d,
+                                const void* w_packed, const float* scale, const float* shift, void* y, step_stream_t stream) {
+    if (!d) return STEP_E_NULL;
+    if (N < 0 || D <= 0 || H <= 0 || W <= 0) return STEP_E_SHAPE;
+    if (d->N != N || d->D != D || d->H != H || d->W != W) return STEP_E_SHAPE;
+    if (x_coff < 0 || x_coff + d->Cin > x_cstride) return STEP_E_SHAPE;
+    if (d->split > 0 && d->split < d->Cout) return STEP_E_UNSUPPORTED;
+    step_conv_desc dx = *d;                                      // the conv over the slice the pool reads
+    dx.x_cstride = x_cstride; dx.x_coff = x_coff;
+    step_conv_desc canon;
+    ConvParams p;
+    const int rc = conv_fill_params(&dx, x, w_packed, scale, shift, nullptr, y, nullptr, canon, p);
+    if (rc != STEP_OK || p.N == 0) return rc;
+    if (dtype != d->dtype || pool_then_conv_nbc(&dx) == 0) return STEP_E_UNSUPPORTED;
+    if (((uintptr_t)x % 16) || ((uintptr_t)w_packed % 16) || ((uintptr_t)y % 16)) return STEP_E_ALIGN;
+    return pool333_then_pw_launch(dtype, x, N, D, H, W, x_cstride, x_coff, p, stream);
+}
+
 int step_conv_forward_pre(const step_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift,
                           const void* pre_w_packed, const float* pre_scale, const float* pre_shift, int pre_cin, void* y, step_stream_t stream) {
     step_conv_desc canon;
@@ -1394,7 +1438,7 @@ int step_conv_pre_pool_plan_info(const step_conv_desc* d, int* info, int n) {
 __attribute__((visibility("default"))) void step_probe_set(void* buf) { step::g_probe_buf = (unsigned long long*)buf; }
 #endif
 const char* step_version(void) { return "step_amd 0.1.0 gfx950"; }
-int step_abi_version(void) { return 48; }
+int step_abi_version(void) { return 49; }
 
 }  // extern "C"
 

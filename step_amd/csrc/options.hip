@@ -30,6 +30,7 @@ constexpr OptSpec SPEC[STEP_OPT_COUNT_] = {
     {"conv_persist", 1, 0, 1},
     {"conv_pws_waves", 0, 0, 16},
     {"conv_group_narrow", 1, 0, 2},
+    {"pool_then_conv", 1, 0, 2},
 };
 std::atomic<int> g_delta[STEP_OPT_COUNT_];      // value - default: zero-initialised static storage IS the default table
 }  // namespace

@@ -290,6 +290,221 @@ __global__ __launch_bounds__(256, NBC == 1 ? 3 : 2) void pool333_pw_kernel(const
     else conv_pw_body<T, NBC, 4, true, 2>(cp, arena);
 }
 
+// The 3x3x3 / 1 pool of an Inception block's branch_3 AND the pointwise conv behind it in ONE launch; the pooled tensor never reaches
+// memory (the 28x28 and larger maps: there pool and conv each fill the chip and the pooled tensor is written and read back for a
+// GEMM of 32-64 output channels).  The GEMM sits inside the separable pool, not the pool inside a conv's slab staging (that form, a
+// 27-tap pass per slab, was built twice and lost: DESIGN.md 3.2):
+//   * a 256-thread workgroup owns one clip, one spatial tile of pool_sep_plan's tiling (<= 14 x 14 outputs, 16 x 16 inputs), `dseg`
+//     output planes and ALL input channels; it loads the conv's packed weight image [NBC][Cin / 16] (1 KiB fragments, <= 32 KiB), the
+//     scale and the shift into LDS once;
+//   * per output plane it walks the input channels in ascending 32-channel chunks (64 bytes per pixel, maxpool_sep_body's unit): the
+//     D maximum of the three input planes is taken in registers (the planes its neighbours in D read too are L2 hits -- the launch
+//     order keeps them on one XCD), then the W and the H pass run through the two LDS images with maxpool_sep_body's keys (VecMax) and
+//     pad classes (an explicit TF pad carries 0); the next chunk's loads fly during the two passes;
+//   * the H pass hands every lane of a wave the two 16-byte vectors (pixel = lane & 31 of a 32-pixel group, channels 16 j + 8 (lane >> 5)
+//     .. + 7) that are the activation fragments of conv_pws_kernel's transposed product D^T = W X^T: 2 NBC MFMAs per group and chunk
+//     straight from the pass's registers, no extra LDS pass (the W-pass image is XOR-swizzled like conv_pw_body's slabs so that 16
+//     lanes = 16 pixels x one slot read conflict-free);
+//   * one fp32 accumulator per output, K ascending: the bits of step_maxpool3d_tf followed by step_conv_forward; the epilogue is
+//     conv_pws_kernel's (scale, shift, relu_nan, v_permlane32_swap, 16-byte stores into the output's channel slice).
+// A 14 x 14 tile is 7 groups on 4 waves (NG = 2 per wave); LDS 32 KiB of pool images + 16 NBC KiB of weights and ~200 VGPRs (three
+// planes of the next chunk in flight beside the accumulators): two workgroups per CU (three would spill).
+constexpr int PTP_MAXKC16 = 16;                     // Cin <= 256
+constexpr int PTP_NG = 2;                           // 32-pixel groups per wave: 4 waves x 2 x 32 >= 14 x 14 pixels
+template <int NBC> constexpr int ptp_lds_bytes() { return PP_LDS_BYTES + NBC * PTP_MAXKC16 * 1024 + 2 * NBC * 32 * 4; }
+
+template <typename T, int NBC>
+__global__ __launch_bounds__(256, 2) void pool333_then_pw_kernel(const T* __restrict__ x, PoolParams p, int TH, int TW, int tiles_h, int tiles_w,
+                                                                 int dseg, int nseg, ConvParams cp) {
+    static_assert(sizeof(T) == 2, "16-bit storage types");
+    constexpr int V = 8, SL = PP_SL, R = PP_R, NT = 256, NG = PTP_NG;
+    static_assert(R * NT == PP_MAXIN * PP_MAXIN * SL, "one load item per 16-byte vector of the input tile");
+    typedef u16x8 raw;
+    typedef typename frag<T>::type frag_t;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[ptp_lds_bytes<NBC>()];
+    raw* const lds_raw = (raw*)lds;
+    raw* const lds_w = lds_raw + R * NT;
+    unsigned char* const wl = lds + PP_LDS_BYTES;
+    float* const scl = (float*)(wl + NBC * PTP_MAXKC16 * 1024);
+    float* const shl = scl + NBC * 32;
+
+    const int tid = threadIdx.x, lane = tid & 63, khalf = lane >> 5;
+#ifdef STEP_EMUL
+    const int wave = tid >> 6;
+#else
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#endif
+    const int nch = cp.nchunks32, KC16 = 2 * nch;          // the packed image pads K to whole 32-channel chunks with zero weights
+    {
+        const u32x4* src = (const u32x4*)cp.w;
+        const int nv = NBC * KC16 * 64;                     // (NBC == cp.nblk32)
+        for (int v = tid; v < nv; v += NT) ((u32x4*)wl)[v] = src[v];
+        for (int i = tid; i < NBC * 32; i += NT) {
+            scl[i] = (cp.scale && i < cp.Cout) ? cp.scale[i] : 1.f;
+            shl[i] = (cp.shift && i < cp.Cout) ? cp.shift[i] : 0.f;
+        }
+    }                                                       // (visible behind the first barrier of the chunk loop)
+
+    // launch order -> XCD as in maxpool_sep_body: neighbours in (tile, D segment) order share halos and planes -> one L2
+    int t = (int)blockIdx.x;
+    const int nblk = (int)gridDim.x;
+    if ((nblk & 7) == 0) t = (t & 7) * (nblk >> 3) + (t >> 3);
+    const int tw_i = t % tiles_w; t /= tiles_w;
+    const int th_i = t % tiles_h; t /= tiles_h;
+    const int seg = t % nseg;
+    const int n = t / nseg;
+    const int oh0 = th_i * TH, ow0 = tw_i * TW;
+    const int IR = TH + 2, IC = TW + 2;                     // input tile
+    const int n_ld = IR * IC * SL, n_wp = IR * TW * SL, npix = TH * TW;
+
+    raw zero;
+#pragma unroll
+    for (int i = 0; i < V; ++i) zero[i] = 0;
+    const raw klow = VecMax<T>::lowest();
+
+    // ---- per-thread item tables (the same every chunk and plane)
+    int ld_goff[R];                      // load items: element offset inside a plane of chunk 0 (-1: pad = 0, -2: overhang = lowest, -3: no item)
+    int wp_off[R], wp_dst[R];            // W-pass items: lds_raw index of the window's first vector (-1: none), swizzled lds_w index
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        const int item = tid + q * NT;
+        const int sl = item & (SL - 1), pix = item / SL;
+        {
+            const int r = pix / IC, cl = pix % IC;
+            const int pr = oh0 + r, pc = ow0 + cl;                     // padded coordinates
+            const int ih = pr - p.pfh, iw = pc - p.pfw;
+            ld_goff[q] = item >= n_ld ? -3 : ((pr >= p.Lph || pc >= p.Lpw) ? -2
+                       : ((ih >= 0 && ih < p.H && iw >= 0 && iw < p.W) ? (ih * p.W + iw) * p.x_cstride + p.x_coff + sl * V : -1));
+        }
+        {
+            const int r = pix / TW, ow = pix % TW;
+            wp_off[q] = item < n_wp ? (r * IC + ow) * SL + sl : -1;
+            wp_dst[q] = (pix * SL) | (sl ^ ((pix >> 2) & 3));
+        }
+    }
+    // H-pass items = the operand layout: group g = wave + 4 gi, pixel 32 g + (lane & 31) of the tile, slices 2 j + khalf
+    int hp_pix[NG], hp_yoff[NG];         // tile pixel (-1: none), output offset inside a plane (-1: not stored)
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi) {
+        const int pix = (wave + 4 * gi) * 32 + (lane & 31);
+        const int oh = pix / TW, ow = pix % TW;
+        const int gh = oh0 + oh, gw = ow0 + ow;
+        const bool ok = pix < npix && gh < p.Ho && gw < p.Wo;
+        hp_pix[gi] = ok ? pix : -1;
+        hp_yoff[gi] = ok ? (gh * p.Wo + gw) * cp.y_cstride + cp.y_coff : -1;
+    }
+    const int ngroups = (npix + 31) >> 5;
+    const size_t xplane = (size_t)p.H * p.W * p.x_cstride, yplane = (size_t)p.Ho * p.Wo * cp.y_cstride;
+    const T* const xn = x + (size_t)n * p.D * xplane;
+    T* const yn = (T*)cp.y + (size_t)n * p.Do * yplane;
+
+    const int obeg = seg * dseg, oend = min(obeg + dseg, p.Do);
+    // the three input planes of output plane od, chunk ch: padded planes od .. od + 2 = input planes od - 1 .. od + 1; a plane inside the
+    // explicit TF pad and a channel past Cin carry 0
+    raw rg[3][R];
+    auto load_chunk = [&](int od, int ch) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int d = od + a - p.pfd;
+            const bool real = od < oend && d >= 0 && d < p.D;
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                raw val = zero;
+                if (real && ld_goff[q] >= 0 && ch * 32 + ((tid + q * NT) & (SL - 1)) * V < p.C)
+                    val = *(const raw*)(xn + (size_t)d * xplane + ld_goff[q] + ch * 32);
+                rg[a][q] = val;
+            }
+        }
+    };
+
+    f32x16 acc[NG][NBC];
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi)
+#pragma unroll
+        for (int i = 0; i < NBC; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[gi][i][r] = 0.f;
+
+    load_chunk(obeg, 0);
+    for (int od = obeg; od < oend; ++od) {
+        for (int ch = 0; ch < nch; ++ch) {
+            // D stage first, in registers (enc(0) is the key of the pad's 0)
+#pragma unroll
+            for (int q = 0; q < R; ++q)
+                if (ld_goff[q] != -3) {
+                    raw m = klow;
+                    if (ld_goff[q] != -2) m = VecMax<T>::max(VecMax<T>::max(VecMax<T>::enc(rg[0][q]), VecMax<T>::enc(rg[1][q])), VecMax<T>::enc(rg[2][q]));
+                    lds_raw[tid + q * NT] = m;
+                }
+            __syncthreads();                             // input tile visible; previous H pass done with lds_w
+            if (ch + 1 < nch) load_chunk(od, ch + 1);    // in flight during the two passes
+            else load_chunk(od + 1, 0);
+#pragma unroll
+            for (int q = 0; q < R; ++q)
+                if (wp_off[q] >= 0) {
+                    const raw* s0 = lds_raw + wp_off[q];
+                    lds_w[wp_dst[q]] = VecMax<T>::max(VecMax<T>::max(s0[0], s0[SL]), s0[2 * SL]);
+                }
+            __syncthreads();
+#pragma unroll
+            for (int gi = 0; gi < NG; ++gi) {
+                if (wave + 4 * gi >= ngroups) continue;                  // (wave-uniform)
+                frag_t xf[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    raw m = zero;
+                    if (hp_pix[gi] >= 0) {
+                        const int sl = 2 * j + khalf;
+                        const int p0 = hp_pix[gi], p1 = p0 + TW, p2 = p1 + TW;
+                        m = VecMax<T>::max(VecMax<T>::max(lds_w[(p0 * SL) | (sl ^ ((p0 >> 2) & 3))], lds_w[(p1 * SL) | (sl ^ ((p1 >> 2) & 3))]),
+                                           lds_w[(p2 * SL) | (sl ^ ((p2 >> 2) & 3))]);
+                        m = VecMax<T>::dec(m);
+                    }
+                    xf[j] = m;
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int i = 0; i < NBC; ++i)
+                        mma_k16(lds_read_bfrag<T>(wl + ((size_t)(i * KC16 + 2 * ch + j) * 64 + lane) * 16), xf[j], acc[gi][i], T());
+            }
+        }
+        // epilogue of plane od (conv_pws_kernel's): the accumulators hold, per lane, one pixel and groups of 4 consecutive output channels
+#pragma unroll
+        for (int gi = 0; gi < NG; ++gi) {
+            if (wave + 4 * gi >= ngroups) continue;
+#pragma unroll
+            for (int i = 0; i < NBC; ++i) {
+                unsigned d[4][2];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c4 = i * 32 + 8 * q + 4 * khalf;
+                    const f32x4 s4 = *(const f32x4*)(scl + c4), h4 = *(const f32x4*)(shl + c4);
+                    float v[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        v[e] = acc[gi][i][4 * q + e] * s4[e] + h4[e];
+                        if (cp.relu) v[e] = relu_nan(v[e]);
+                        acc[gi][i][4 * q + e] = 0.f;
+                    }
+                    d[q][0] = (unsigned)elem<T>::bits16(v[0]) | ((unsigned)elem<T>::bits16(v[1]) << 16);
+                    d[q][1] = (unsigned)elem<T>::bits16(v[2]) | ((unsigned)elem<T>::bits16(v[3]) << 16);
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    lane32_swap(d[2 * h][0], d[2 * h + 1][0]);
+                    lane32_swap(d[2 * h][1], d[2 * h + 1][1]);
+                    const int co = i * 32 + 16 * h + 8 * khalf;
+                    if (hp_yoff[gi] >= 0 && co < cp.Cout) {
+                        const u32x4 o = {d[2 * h][0], d[2 * h][1], d[2 * h + 1][0], d[2 * h + 1][1]};
+                        *(u32x4*)(yn + (size_t)od * yplane + hp_yoff[gi] + co) = o;
+                    }
+                }
+            }
+        }
+    }
+}
+
 // Backward of the TF-SAME max pool (training): the gradient of an output goes to the FIRST maximum of its window in
 // (d, h, w) scan order -- torch's MaxPool3d rule (`val > max`), applied to the explicitly zero-padded tensor as
 // MaxPool3dTFPadding builds it (models/i3dpt.py:114-126): when a pad element wins, the gradient is dropped.
@@ -1246,6 +1461,53 @@ int pool333_pw_launch(int dtype, const void* x, int N, int D, int H, int W, int 
     else
         STEP_LAUNCH((pool333_pw_kernel<f16_t>), grid, dim3(256), stream, (const f16_t*)x, (f16_t*)y, p, sp.TH, sp.TW, sp.tiles_h, sp.tiles_w, sp.cchunks,
                     sp.dseg, sp.nseg, (int)npool, cp);
+    return STEP_LAUNCH_CHECK();
+}
+
+// workgroups of pool333_then_pw_kernel on a map: pool_sep_plan's spatial tiling, `dseg` output planes each (the weight image is loaded once
+// for all of them).  One plane: measured on C2's 28x28 maps (512 workgroups = two per CU) against two planes (256 workgroups) 3b 24.6 | 33.7 us,
+// 3c 33.8 | 46.7 us, and on the 50x50 maps of 4 AVA clips 55.4 | 64.1 us, 75.4 | 88.1 us (profiles/r08_pool_bench.txt).
+#ifndef STEP_EXP_PTP_DSEG                                      // (timing experiments, tools/pool_bench.py --lib NAME: never the product library)
+#define STEP_EXP_PTP_DSEG 1
+#endif
+static void pool333_then_pw_shape(int D, int H, int W, int& TH, int& TW, int& tiles_h, int& tiles_w, int& dseg, int& nseg) {
+    tiles_h = ceil_div(H, 14); tiles_w = ceil_div(W, 14);
+    TH = ceil_div(H, tiles_h); TW = ceil_div(W, tiles_w);
+    dseg = STEP_EXP_PTP_DSEG;
+    nseg = ceil_div(D, dseg);
+}
+long long pool333_then_pw_blocks(int N, int D, int H, int W) {
+    int TH, TW, th, tw, dseg, nseg;
+    pool333_then_pw_shape(D, H, W, TH, TW, th, tw, dseg, nseg);
+    return (long long)N * th * tw * nseg;
+}
+
+template <typename T>
+static void pool333_then_pw_launch_t(const void* x, const PoolParams& p, int TH, int TW, int tiles_h, int tiles_w, int dseg, int nseg, const ConvParams& cp,
+                                     dim3 grid, step_stream_t stream) {
+    if (cp.nblk32 == 1) STEP_LAUNCH((pool333_then_pw_kernel<T, 1>), grid, dim3(256), stream, (const T*)x, p, TH, TW, tiles_h, tiles_w, dseg, nseg, cp);
+    else STEP_LAUNCH((pool333_then_pw_kernel<T, 2>), grid, dim3(256), stream, (const T*)x, p, TH, TW, tiles_h, tiles_w, dseg, nseg, cp);
+}
+
+// the launch behind step_pool_then_conv_forward (conv_igemm.hip checks the contract and prepares the conv's parameter block; N, D: the
+// clip axes as the caller gave them -- the conv's canonical descriptor folds them, the pool must not look across clips)
+int pool333_then_pw_launch(int dtype, const void* x, int N, int D, int H, int W, int x_cstride, int x_coff, const ConvParams& cp, step_stream_t stream) {
+    PoolParams p;
+    p.N = N; p.D = D; p.H = H; p.W = W; p.C = cp.Cin; p.x_cstride = x_cstride; p.x_coff = x_coff;
+    p.Do = D; p.Ho = H; p.Wo = W;
+    p.y_cstride = cp.y_cstride; p.y_coff = cp.y_coff;
+    p.kd = p.kh = p.kw = 3; p.sd = p.sh = p.sw = 1;
+    p.pfd = p.pfh = p.pfw = tf_pad_front(3, 1);
+    p.Lpd = D + tf_pad_total(3, 1); p.Lph = H + tf_pad_total(3, 1); p.Lpw = W + tf_pad_total(3, 1);
+    int TH, TW, tiles_h, tiles_w, dseg, nseg;
+    pool333_then_pw_shape(D, H, W, TH, TW, tiles_h, tiles_w, dseg, nseg);
+    const long long blocks = (long long)N * tiles_h * tiles_w * nseg;
+    if (blocks <= 0 || blocks > 0x7fffffffLL || cp.nblk32 < 1 || cp.nblk32 > 2 || cp.nchunks32 * 2 > PTP_MAXKC16) return STEP_E_UNSUPPORTED;
+    if (TH < 1 || TW < 1 || TH > PP_MAXIN - 2 || TW > PP_MAXIN - 2) return STEP_E_UNSUPPORTED;                 // (the kernel's LDS images and wave slots)
+    const dim3 grid((unsigned)blocks);
+    if (dtype == STEP_BF16) pool333_then_pw_launch_t<bf16_t>(x, p, TH, TW, tiles_h, tiles_w, dseg, nseg, cp, grid, stream);
+    else if (dtype == STEP_F16) pool333_then_pw_launch_t<f16_t>(x, p, TH, TW, tiles_h, tiles_w, dseg, nseg, cp, grid, stream);
+    else return STEP_E_UNSUPPORTED;
     return STEP_LAUNCH_CHECK();
 }
 

@@ -263,6 +263,29 @@ def pool_conv_forward(x, w_packed, Cout, scale, shift, relu, out, out2=None, spl
     return pooled if ran else None
 
 
+def pool_then_conv_forward(x, w_packed, Cout, scale, shift, relu, out):
+    """The 3x3x3 / 1 TF-SAME max pool of x and the pointwise conv of the POOLED tensor as one launch (step_pool_then_conv_forward: an
+    Inception block's branch_3 on the 28x28 and larger maps); the pooled tensor is never written.  Returns `out`, or None where the
+    library has no such form for the shapes or keeps the two apart there (the caller launches pool and conv; same results bit for bit)."""
+    L = _lib.lib()
+    N, D, H, W, Cin = x.shape
+    if x.dtype == torch.float32 or not hasattr(L, "step_pool_then_conv_plan"):         # (an older library beside this one: the A/B tools)
+        return None
+    d = _conv_desc(x, Cout, (1, 1, 1), _chan_slice(out), relu=relu)
+    nbc = L.step_pool_then_conv_plan(ctypes.byref(d))
+    if nbc <= 0:
+        return None
+
+    def describe():
+        pix = N * D * H * W
+        return ("void step::pool333_then_pw_kernel<%s, %d>(%s const*, step::PoolParams, int, int, int, int, int, int, step::ConvParams)" % (
+            _TNAME[x.dtype], nbc, _TNAME[x.dtype]), 2.0 * pix * Cin * Cout, (pix * (Cin + Cout) + Cin * Cout) * _ES[x.dtype])
+    ran = _run_fused(lambda: L.step_pool_then_conv_forward(_dt(x), _lib.dptr(x), N, D, H, W, _chan_slice(x), 0, ctypes.byref(d), _lib.dptr(w_packed),
+                                                           _lib.dptr(scale), _lib.dptr(shift), _lib.dptr(out), _lib.stream_ptr(x.device)),
+                     describe, "step_pool_then_conv_forward")
+    return out if ran else None
+
+
 def conv_forward_pre(x, w_packed, Cout, k, scale, shift, relu, pre, out=None):
     """conv_forward whose input is a pointwise conv + affine + ReLU of x, evaluated on the fly (step_conv_forward_pre: conv3d_2b in
     front of conv3d_2c; the tensor between them never exists).  pre = (packed pointwise weight, scale, shift, Cmid): x has the
