@@ -189,7 +189,8 @@ def get_option(lib, name):
 
 class options:
     """Context manager: `with options(lib, conv_waves=4, conv_nb=2): ...` sets planner options and restores the previous
-    values on exit (tests and tools/ab_bench.py; the product never changes an option)."""
+    values on exit (tests and single tools; A/B runs set options through tools/abkit.py's Variant.applied, e.g.
+    `python tools/step_ab.py --var default --var conv_waves=4`; the product never changes an option)."""
 
     def __init__(self, lib, **kw):
         self.lib, self.kw = lib, kw

@@ -4,6 +4,7 @@ There is NO fallback: if the library is missing, cannot be loaded, or a tensor i
 device, this module raises.  (The oracle under oracle/ and the interpreter under tests/emul are test
 infrastructure and are never imported from here.)
 """
+import contextlib
 import ctypes
 import os
 
@@ -38,6 +39,18 @@ def lib():
             raise RuntimeError("step_amd: ABI mismatch between libstep_amd.so and step_amd/_capi.py")
         _LIB = L
     return _LIB
+
+
+@contextlib.contextmanager
+def use(handle):
+    """`with use(handle): ...` makes `handle` (a declared ctypes library: an earlier build in an A/B tool, the host interpreter
+    in a test) what lib() returns, and puts the previous one back on exit.  Nests.  The product never calls this."""
+    global _LIB
+    prev, _LIB = _LIB, handle
+    try:
+        yield handle
+    finally:
+        _LIB = prev
 
 
 def stream_ptr(device=None):

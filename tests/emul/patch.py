@@ -11,11 +11,11 @@ from step_amd import _lib
 def emulated_kernels():
     from tests.emul import emul_lib
 
-    saved = (_lib._LIB, _lib.dptr, _lib.stream_ptr)
-    _lib._LIB = emul_lib.lib()
+    saved = (_lib.dptr, _lib.stream_ptr)
     _lib.dptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
     _lib.stream_ptr = lambda device=None: None
     try:
-        yield
+        with _lib.use(emul_lib.lib()):
+            yield
     finally:
-        _lib._LIB, _lib.dptr, _lib.stream_ptr = saved
+        _lib.dptr, _lib.stream_ptr = saved

@@ -58,7 +58,7 @@ def test_planner_dispatch(lib):
 
 
 def test_planner_nb_rule(lib):
-    """conv_nb_rule (round 5 A/B, tools/plan_ab.py): 0 = the accumulator depth that needs the fewest ROUNDS of the chip (the default: the
+    """conv_nb_rule (round 5 A/B, now `tools/step_ab.py --var default --var conv_nb_rule=1`): 0 = the accumulator depth that needs the fewest ROUNDS of the chip (the default: the
     14x14 layers take NB = 1, one round of 224-280 workgroups), 1 = the depth with the least chip time (workgroups x per-workgroup time):
     the 14x14 layers go deeper, conv3d_2c and the 28x28 layers keep their depth."""
     BF = _capi.BF16

@@ -16,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from step_amd import _capi, _lib  # noqa: E402
+from tools import abkit  # noqa: E402
 
 # (name, Cin, Cout, k, D, H, W) per clip
 C2 = [
@@ -46,22 +47,14 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--custom", action="append", default=[], help="name,Cin,Cout,k,D,H,W (repeatable; replaces the layer set)")
     ap.add_argument("--nocheck", action="store_true", help="variants may compute different things (timing experiments)")
-    ap.add_argument("--var", action="append", default=[], help="option=VAL[,option=VAL] planner options of one variant, or `default` (repeatable)")
+    ap.add_argument("--var", action="append", default=[], type=abkit.Variant.arg,
+                    help="option=VAL[,option=VAL][,lib=NAME] of one variant (tools/abkit.py's grammar), or `default` (repeatable)")
     a = ap.parse_args()
-    variants = a.var or ["conv_waves=8", "conv_waves=4"]
+    variants = a.var or [abkit.Variant.parse("conv_waves=8"), abkit.Variant.parse("conv_waves=4")]
+    for v in variants:
+        if v.switches:                       # the layers are launched through the C ABI: a module switch of the Python layer would change nothing
+            ap.error("--var %s: module switches have no effect on a per-layer launch (tools/step_ab.py times them on the whole step)" % v.text)
     L = _lib.lib()
-    # `lib=NAME` in a variant: tools/libstep_amd_NAME.so -- `prev` from tools/build_prev.sh, experiment builds from
-    # `make -C step_amd/csrc EXP=NAME EXPFLAGS=-D...`
-    LIBS = {}
-
-    def lib_of(v):
-        for kv in v.split(","):
-            if kv.startswith("lib="):
-                n = kv[4:]
-                if n not in LIBS:
-                    LIBS[n] = _capi.declare(ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libstep_amd_%s.so" % n)), strict=False)
-                return LIBS[n]
-        return L
     dt, tdt = _capi.BF16, torch.bfloat16
     dev = torch.device("cuda:0")
     st = _lib.stream_ptr()
@@ -74,7 +67,7 @@ def main():
             layers.append((f[0],) + tuple(int(v) for v in f[1:]))
     only = set(x for x in a.only.split(",") if x)
     tot = [0.0] * len(variants)
-    print("%-8s %s" % ("layer", "  ".join("%28s" % v for v in variants)))
+    print("%-8s %s" % ("layer", "  ".join("%28s" % v.text for v in variants)))
     if "stem" in only or a.set == "stem":
         # conv3d_1a_7x7 (its own entry point): B clips [32,3,224,224] (c2) or [36,3,400,400] (c3)
         T_, HW_ = (36, 400) if a.set == "c3" else (32, 224)
@@ -84,7 +77,7 @@ def main():
         To, Ho = (T_ - 2) // 2 + 1, (HW_ - 2) // 2 + 1
         y = torch.empty(B, To, Ho, Ho, 64, dtype=tdt, device=dev)
         times, ref = [[] for _ in variants], None
-        libs = [lib_of(v) for v in variants]
+        libs = [abkit.load_build(v.lib) if v.lib else L for v in variants]        # (as before the harness, the stem leg compares builds only: a variant's planner options are not set for it)
         wps = []
         for lib in libs:
             wp = torch.empty(lib.step_stem_packed_elems(64), dtype=tdt, device=dev)
@@ -103,14 +96,7 @@ def main():
                 assert a.nocheck or float((y.float() - ref).abs().max() / ref.abs().max()) < 2e-2
         for _ in range(a.rounds):
             for vi in range(len(variants)):
-                run_stem(vi)
-                s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s_.record()
-                for _ in range(a.iters):
-                    run_stem(vi)
-                e_.record()
-                torch.cuda.synchronize()
-                times[vi].append(s_.elapsed_time(e_) / a.iters)
+                times[vi].append(abkit.event_ms(lambda: run_stem(vi), a.iters, warm=1))
         gf = 2.0 * B * To * Ho * Ho * 64 * 1029 / 1e9
         med = [statistics.median(t) for t in times]
         print("%-8s %s" % ("stem", "  ".join("%7.1f us %6.0f TF %-12s" % (m * 1e3, gf / m, "stem_stream") for m in med)))
@@ -136,47 +122,31 @@ def main():
         def run():
             _capi.check(cur[0].step_conv_forward(ctypes.byref(d), _lib.dptr(x), _lib.dptr(wp), _lib.dptr(sc), _lib.dptr(sh), _lib.dptr(res) if with_res else None, _lib.dptr(y), None, st), name)
 
-        def setenv(v):                       # a variant = planner options (include/step_amd.h), everything else at its default
-            cur[0] = lib_of(v)
-            cur[0].step_reset_options()
-            for kv in v.split(","):
-                if kv and kv != "default" and not kv.startswith("lib="):
-                    kk, vv = kv.split("=")
-                    _capi.set_option(cur[0], kk, int(vv))
-
         times = [[] for _ in variants]
         names = []
         ref = None
         for vi, v in enumerate(variants):
-            setenv(v)
-            kn = ctypes.create_string_buffer(256)
-            cur[0].step_conv_kernel_name(ctypes.byref(d), kn, 256)
-            names.append(kn.value.decode()[11:].split("(")[0].replace("step::", "").replace("_kernel", ""))
-            run()
-            torch.cuda.synchronize()
+            with v.applied() as cur[0]:      # a variant = its build + planner options (include/step_amd.h), everything else at its default
+                kn = ctypes.create_string_buffer(256)
+                cur[0].step_conv_kernel_name(ctypes.byref(d), kn, 256)
+                names.append(kn.value.decode()[11:].split("(")[0].replace("step::", "").replace("_kernel", ""))
+                run()
+                torch.cuda.synchronize()
             if ref is None:
                 ref = y.float().clone()
             else:
                 err = float((y.float() - ref).abs().max() / ref.abs().max().clamp_min(1e-20))
-                assert a.nocheck or err < 2e-2, (name, v, err)            # every variant computes the same layer
+                assert a.nocheck or err < 2e-2, (name, v.text, err)       # every variant computes the same layer
         for _ in range(a.rounds):
             for vi, v in enumerate(variants):
-                setenv(v)
-                run()
-                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s.record()
-                for _ in range(a.iters):
-                    run()
-                e.record()
-                torch.cuda.synchronize()
-                times[vi].append(s.elapsed_time(e) / a.iters)
+                with v.applied() as cur[0]:
+                    times[vi].append(abkit.event_ms(run, a.iters, warm=1))
         gf = 2.0 * B * D * H * W * co * ci * k ** 3 / 1e9
         med = [statistics.median(t) for t in times]
         for vi in range(len(variants)):
             tot[vi] += med[vi]
         print("%-8s %s" % (name, "  ".join("%7.1f us %6.0f TF %-12s" % (m * 1e3, gf / m, n[-14:]) for m, n in zip(med, names))))
     print("%-8s %s" % ("total", "  ".join("%7.1f us %21s" % (t * 1e3, "") for t in tot)))
-    L.step_reset_options()
 
 
 if __name__ == "__main__":

@@ -34,6 +34,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 from step_amd import BaseTransform, TubeAugmentation, _capi, _lib, ops
+from tools import abkit
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
@@ -48,13 +49,8 @@ a = ap.parse_args()
 assert torch.cuda.is_available(), "tools/augment_bench.py needs a ROCm device"
 dev = torch.device("cuda:0")
 L = _lib.lib()
-lines = []
-
-
-def say(s=""):
-    print(s, flush=True)
-    lines.append(s)
-
+say = abkit.tee(a.out)
+timed = abkit.event_ms                                                         # ms per launch, no warm-up of its own: every form is warmed below
 
 N, T, Hs, Ws, Ho, Wo = 8, 36, 256, 340, 400, 400
 rs = np.random.RandomState(11)
@@ -63,16 +59,6 @@ frames = torch.from_numpy(frames_np).to(dev)
 centre, half = rs.uniform(0.35, 0.65, (N, 2, 1, 2)), rs.uniform(0.1, 0.25, (N, 2, 1, 2))
 tubes = np.tile(np.concatenate([centre - half, centre + half], 3), (1, 1, T, 1)).astype(np.float32)
 out = torch.empty((N, T, 3, Ho, Wo), dtype=torch.bfloat16, device=dev)
-
-
-def timed(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
 
 
 def train_children(forms, extra, what):
@@ -108,7 +94,8 @@ if a.device_plan:
     np.random.seed(11)
 
     def host_form():
-        """what `--augment` does per batch ahead of the one launch: plan per clip, pack, the copy of the block (waited for here)"""
+        """what `--augment` does per batch ahead of the one launch: plan per clip, pack, the copy of the block (waited for here);
+        its own host clock: ONE call split into the CPU part and the part that ends in the synchronise"""
         t0 = time.perf_counter()
         plans = [host_aug.plan((T, Hs, Ws), tubes[n])[0] for n in range(N)]
         t1 = time.perf_counter()
@@ -179,9 +166,7 @@ if a.device_plan:
                 % (float(np.median(d) - np.median(h)), max(h) - min(h)))
             res["train_%d" % clips_per_gpu] = runs
     say(json.dumps(res))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    say.close()
     raise SystemExit(0)
 
 forms = {
@@ -269,6 +254,4 @@ if a.train_runs:
         % (diff, max(plain) - min(plain), res["all four switches"]["ms"] / N))
     res["train"] = runs
 say(json.dumps({"hbm_probe_TBps": hbm / 1e12, "forms": res, "plan_ms_per_clip": plan_ms, "np_apply_ms_per_clip": np_ms}))
-if a.out:
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+say.close()

@@ -17,7 +17,7 @@ REC = []
 orig = ops.conv_wgrad
 
 
-def timed(x, gy, Cout, k):
+def timed(x, gy, Cout, k):                   # (not abkit.event_ms: one event pair per call INSIDE the running step, read after the step's end)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     r = orig(x, gy, Cout, k)

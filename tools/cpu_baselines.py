@@ -21,7 +21,7 @@ from oracle import i3d_ref as R  # noqa: E402
 from oracle import postprocess_ref as PR  # noqa: E402
 
 
-def timed(fn, budget, iters=5):
+def timed(fn, budget, iters=5):              # (not abkit.wall_ms: CPU work, no device; per-call samples that stop at a time budget)
     fn()
     ts = []
     t_all = time.perf_counter()

@@ -25,14 +25,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools import abkit  # noqa: E402
 
 LEGS = (("False (a)", False), ("True", True), ("False (b)", False))
-OUT = []
-
-
-def say(text):
-    print(text, flush=True)
-    OUT.append(text)
 
 
 def history(seed, nums, dev):
@@ -72,7 +67,7 @@ def syncs(fn):
     return sum(1 for x in w if "synchronizing" in str(x.message) and "prototype" not in str(x.message))
 
 
-def measure(name, nums, rounds, calls, dev):
+def measure(say, name, nums, rounds, calls, dev):
     from step_amd import driver
     args = types.SimpleNamespace(image_size=(400, 400), num_classes=60, conf_thresh=0.01, nms_thresh=0.4, evaluate_topk=-1, topk=-1)
     hist = history(2025, nums, dev)
@@ -107,7 +102,7 @@ def measure(name, nums, rounds, calls, dev):
     driver.DETECT_BLOCK = True
 
 
-def kernel_alone(nums, dev, reps=200):
+def kernel_alone(say, nums, dev, reps=200):
     from step_amd import ops
     h = history(2025, nums, dev)[0]
     B, kmax, NC = len(nums), max(nums), 60
@@ -115,18 +110,9 @@ def kernel_alone(nums, dev, reps=200):
     start = (torch.cumsum(n, 0) - n).to(torch.int32)
     prob, loc = h["pred_prob"][:, 1].float(), h["pred_loc"][:, 1].float()
     keep = torch.empty((B, NC, kmax), dtype=torch.uint8, device=dev)
-    for _ in range(10):
-        ops.detect_nms(prob, loc, start, n, kmax, 0.01, 0.4, 400.0, 400.0, keep)
-    torch.cuda.synchronize()
-    per = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            ops.detect_nms(prob, loc, start, n, kmax, 0.01, 0.4, 400.0, 400.0, keep)
-        e1.record()
-        torch.cuda.synchronize()
-        per.append(e0.elapsed_time(e1) / reps * 1e3)
+    call = lambda: ops.detect_nms(prob, loc, start, n, kmax, 0.01, 0.4, 400.0, 400.0, keep)
+    abkit.event_ms(call, 10)
+    per = [abkit.event_ms(call, reps) * 1e3 for _ in range(5)]
     masked = (prob > 0.01).sum(0)
     say("ops.detect_nms alone, %d clips x %d tubes, kmax %d, %d groups (kept %d of %d masked; most masked tubes in a class column %d): %.1f us per "
         "call incl. its box allocation, back to back (five windows: %s)"
@@ -144,15 +130,14 @@ def main():
     assert a.rounds >= 5 and a.calls >= 50, "at least 5 rounds x 50 calls"
     import step_amd  # noqa: F401
     dev = torch.device("cuda:0")
+    say = abkit.tee(a.out)
     say("# tools/detect_block_bench.py on %s: driver.postprocess with and without the workgroup form of step_detect_nms" % torch.cuda.get_device_name(0))
     for name, nums in (("4 clips x 84 tubes (anchor mode 3)", [84] * 4), ("4 clips x 109 tubes (anchor mode 4)", [109] * 4),
                        ("4 clips x 34 tubes (the <= 64 path: same routing in every leg)", [34] * 4)):
-        measure(name, nums, a.rounds, a.calls, dev)
-    kernel_alone([109] * 4, dev)
-    kernel_alone([1024] * 4, dev)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(OUT) + "\n")
+        measure(say, name, nums, a.rounds, a.calls, dev)
+    kernel_alone(say, [109] * 4, dev)
+    kernel_alone(say, [1024] * 4, dev)
+    say.close()
 
 
 if __name__ == "__main__":

@@ -21,20 +21,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def host_ms(fn, reps):
-    """median / min / max over `reps` calls, each ending in a device synchronise"""
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
+    """median / min / max over `reps` calls, each ending in a device synchronise (the statistics are this tool's, the clock abkit's)"""
+    from tools import abkit                        # (after main() has put --tree's step_amd first)
+    ts = [abkit.wall_ms(fn, 1) for _ in range(reps)]
     return statistics.median(ts), min(ts), max(ts)
 
 
 def measure(name, args, hist, kw, gthr, reps):
     from step_amd import driver, ops
     from tests import merge_cases as MG
+    from tools import abkit
 
     merged = hasattr(driver, "postprocess_merged")
     plain = lambda: driver.postprocess(args, hist, **kw)
@@ -62,19 +58,10 @@ def measure(name, args, hist, kw, gthr, reps):
     for g, d in enumerate(d for clips in rows for d in clips):
         seg[g, :n[g]] = d["boxes"]
     cnt = torch.tensor(n, dtype=torch.int32, device="cuda")
-    for _ in range(10):
-        out = ops.detect_merge(seg, cnt, gthr)
-    torch.cuda.synchronize()
-    per = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            out = ops.detect_merge(seg, cnt, gthr)
-        e1.record()
-        torch.cuda.synchronize()
-        per.append(e0.elapsed_time(e1) / reps * 1e3)
-    K = out[3].tolist()
+    call = lambda: ops.detect_merge(seg, cnt, gthr)
+    abkit.event_ms(call, 10)
+    per = [abkit.event_ms(call, reps) * 1e3 for _ in range(5)]
+    K = call()[3].tolist()
     print("%s: step_detect_merge, %d groups, rows per group %s, clusters per group %s: %.1f us per launch incl. its four output "
           "allocations, back to back (five windows: %s)" % (name, G, n, K, statistics.median(per), ", ".join("%.1f" % v for v in per)), flush=True)
     boxes = [d["boxes"].cpu().numpy() for clips in rows for d in clips]

@@ -17,13 +17,13 @@ import ctypes
 import os
 import statistics
 import sys
-import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from step_amd import _capi, _lib, heads, ops, rng, workloads  # noqa: E402
+from tools import abkit  # noqa: E402
 
 
 def hbm_copy_rate(dev):
@@ -32,21 +32,15 @@ def hbm_copy_rate(dev):
     src = torch.empty(nbytes, dtype=torch.uint8, device=dev).random_(0, 255)
     dst = torch.empty_like(src)
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    best = None
-    for k in range(6):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _capi.check(L.step_hbm_stream_probe(ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()), nbytes, cus * 16, _lib.stream_ptr(dev)),
-                    "step_hbm_stream_probe")
-        e1.record()
-        torch.cuda.synchronize()
-        if k:
-            best = e0.elapsed_time(e1) if best is None else min(best, e0.elapsed_time(e1))
-    return 2 * nbytes / (best * 1e-3)
+    probe = lambda: _capi.check(L.step_hbm_stream_probe(ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()), nbytes, cus * 16, _lib.stream_ptr(dev)),
+                                "step_hbm_stream_probe")
+    probe()
+    return 2 * nbytes / (min(abkit.event_ms(probe, 1) for _ in range(5)) * 1e-3)
 
 
 def graph_time(fn, calls, reps=5):
-    """microseconds per call of `fn(k)`, k = 0 .. calls - 1 recorded back to back in one graph; best of `reps` replays after a warm-up"""
+    """microseconds per call of `fn(k)`, k = 0 .. calls - 1 recorded back to back in one graph; best of `reps` replays after a warm-up
+    (its own: it builds the graph of indexed calls that it times, which abkit's timers do not)"""
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
@@ -57,16 +51,8 @@ def graph_time(fn, calls, reps=5):
     with torch.cuda.graph(g):
         for k in range(calls):
             fn(k)
-    best = None
-    for r in range(reps + 1):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        if r:
-            best = e0.elapsed_time(e1) if best is None else min(best, e0.elapsed_time(e1))
-    return best * 1e3 / calls
+    g.replay()
+    return min(abkit.event_ms(g.replay, 1) for _ in range(reps)) * 1e3 / calls
 
 
 def kernel_rates(dev, a, lines, copy_rate):
@@ -119,15 +105,9 @@ def step_timing(dev, a, lines):
         times = [[] for _ in legs]
         for r in range(a.rounds + 1):
             for k, w in enumerate(ws):
-                run = w.step if form == "captured" else w._eager_step
-                run()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(a.iters):
-                    run()
-                torch.cuda.synchronize()
+                ms = abkit.wall_ms(w.step if form == "captured" else w._eager_step, a.iters, warm=1)
                 if r:
-                    times[k].append((time.perf_counter() - t0) / a.iters * 1e3)
+                    times[k].append(ms)
         lines.append("C4 bf16 step, %d clips x %d tubes, %s: ms per step, median [min .. max] of %d interleaved rounds x %d steps" % (a.batch, a.tubes, form, a.rounds, a.iters))
         for (name, _, _), t in zip(legs, times):
             lines.append("  %-30s %8.3f  [%8.3f .. %8.3f]" % (name, statistics.median(t), min(t), max(t)))

@@ -19,6 +19,7 @@ sys.path.insert(0, ROOT)
 from step_amd import ops  # noqa: E402
 from step_amd.evaluate import FrameMAP  # noqa: E402
 from tests import eval_cases as EV  # noqa: E402
+from tools import abkit  # noqa: E402
 
 NC = 60
 
@@ -61,17 +62,8 @@ def build(rows, dev, per_call=200):
 
 
 def events(fn, reps):
-    for _ in range(3):
-        fn()
-    ts = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return ts
+    """`reps` single calls, each between device events of its own, after three warm calls (the list: fmt() reports median, min .. max)"""
+    return [abkit.event_ms(fn, 1, warm=3 if r == 0 else 0) for r in range(reps)]            # (abkit's timer; the per-call list is this tool's)
 
 
 def fmt(ts):
@@ -95,12 +87,7 @@ def measure(tag, rows, dev, reps, out):
     out.append("  step_eval_ap    (one launch, %d workgroups)          %s" % (NC, fmt(events(lambda: ops.eval_ap(cls_start, label_b, c["num_gt"]), reps))))
     out.append("  sorts: labelling order (score, image)              %s" % fmt(events(lambda: ev._labelling_order(c), reps)))
     out.append("  sorts: class-major order (score, class)            %s" % fmt(events(lambda: ev._class_order(c, label, cls_a, score_a), reps)))
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        ev.evaluate()
-        ts.append((time.perf_counter() - t0) * 1e3)
+    ts = [abkit.wall_ms(ev.evaluate, 1) for _ in range(reps)]
     out.append("  evaluate() (host clock, ends in its one copy)      %s" % fmt(ts))
     t_dev = float(np.median(ts))
     t0 = time.perf_counter()

@@ -4,12 +4,12 @@ host -> device copy on the MAIN stream + conversion, (d) train_step_amd.py's arr
 default-priority copy stream, (f) the copy alone."""
 import os
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from step_amd import ops, workloads  # noqa: E402
+from tools import abkit  # noqa: E402
 
 
 def main():
@@ -21,15 +21,11 @@ def main():
     stage = [torch.empty((N, T, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
     main = torch.cuda.current_stream()
 
-    def timed(fn, iters=30):
+    def timed(fn, iters=30):                   # abkit's host-clock timer around fn(k), k = 0, 1, ..: three warm calls, then k starts again
         for k in range(3):
             fn(k)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for k in range(iters):
-            fn(k)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / iters * 1e3
+        ks = iter(range(iters))
+        return abkit.wall_ms(lambda: fn(next(ks)), iters)
 
     def a_(k):
         w.step()

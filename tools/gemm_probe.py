@@ -7,6 +7,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from step_amd import ops  # noqa: E402
+from tools import abkit  # noqa: E402
 
 # (name, M, Cin, Cout)
 SHAPES = [("5cf@7x1080", 1080 * 49, 832, 624), ("lc1@7x1080", 1080 * 49, 1088, 1024), ("lc_c1", 1080 * 49, 1024, 256), ("lc_c3", 1080 * 49, 256, 1024),
@@ -14,17 +15,8 @@ SHAPES = [("5cf@7x1080", 1080 * 49, 832, 624), ("lc1@7x1080", 1080 * 49, 1088, 1
           ("3bf (one read)", 8 * 18 * 2500, 192, 176), ("2b@400x8", 8 * 18 * 10000, 64, 64), ("4bf@400", 9 * 625, 480, 304)]
 
 
-def timeit(fn, iters=10):
-    fn(); torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def main():
+    timeit = lambda fn: abkit.event_ms(fn, 10, warm=1)
     print("%-16s %10s %10s %10s   (ms; TFLOP/s in brackets)" % ("shape", "step_amd", "torch.mm", "mm fp32out"))
     for name, M, ci, co in SHAPES:
         x = torch.randn(M, ci, device="cuda").bfloat16()

@@ -17,7 +17,6 @@ import json
 import os
 import socket
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -37,6 +36,7 @@ assert a.launches * a.rounds >= 200, "at least 200 timed repetitions per form"
 
 from step_amd import _capi, _lib, workloads
 from step_amd import dist as sdist
+from tools import abkit
 
 HBM_COPY_TBPS = 6.29                                             # measured copy ceiling of the MI355X
 LINK_GBPS = 153.0                                                # per xGMI link
@@ -47,12 +47,7 @@ s.bind(("127.0.0.1", 0))
 port = s.getsockname()[1]
 s.close()
 dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % port, rank=0, world_size=1, device_id=dev)      # "nccl" IS RCCL on ROCm
-lines = []
-
-
-def say(text=""):
-    print(text, flush=True)
-    lines.append(text)
+say = abkit.tee(a.out)
 
 
 def workload(grad_wire, feedback=True, capturable=True):
@@ -90,16 +85,6 @@ def adam():
     opt._launch(L, 1.0, 1, None)                                 # step_adam_flat_dev, gradient clear in the same pass: 16 B read + 16 B written
 
 
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / a.launches                # us per launch
-
-
 forms = (("pack16 + residual", pack_res, 14), ("pack16, no residual", pack_plain, 6), ("unpack16", unpack, 6), ("adam_flat_dev + clear", adam, 32))
 for _, fn, _ in forms:
     for _ in range(5):
@@ -110,7 +95,7 @@ for _ in range(a.rounds):
     for k, fn, _ in forms:
         if fn is not adam:
             opt.flat_grad.copy_(g_keep)
-        us[k].append(timed(fn))
+        us[k].append(abkit.event_ms(fn, a.launches) * 1e3)       # us per launch
 say("bf16 gradient wire over the C4 arena: %d elements (%.1f MB fp32), %d rounds x %d launches per form, alternated, device events" % (n, n * 4e-6, a.rounds, a.launches))
 say("%-24s %10s %22s %6s %8s %14s" % ("form", "median us", "min .. max us", "B/el", "TB/s", "of 6.29 TB/s"))
 res = {"elements": n, "rounds": a.rounds, "launches": a.launches, "forms": {}}
@@ -140,12 +125,7 @@ torch.cuda.synchronize()
 ms = {k: [] for k in ws}
 for _ in range(a.step_rounds):
     for k, wk in ws.items():
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(a.steps_per_round):
-            wk.step()
-        torch.cuda.synchronize()
-        ms[k].append((time.perf_counter() - t0) * 1e3 / a.steps_per_round)
+        ms[k].append(abkit.wall_ms(wk.step, a.steps_per_round))
 say()
 say("C4 step, bf16 activations, one clip, one-rank RCCL group with the exchange forced, split form (graph, eager flat all-reduce, graph);")
 say("%d rounds x %d steps per wire, interleaved, host clock around synchronised blocks:" % (a.step_rounds, a.steps_per_round))
@@ -193,8 +173,6 @@ say("  fp32 ring %.2f ms, bf16 ring %.2f ms: %.2f ms less on the link per step, 
     % (r32, r16, r32 - r16, both * 1e-3))
 say("  (both run bucket by bucket on the communication stream under backward; the projection compares totals, not what stays exposed)")
 say(json.dumps(res))
-os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-with open(a.out, "w") as f:
-    f.write("\n".join(lines) + "\n")
+say.close()
 dist.barrier()
 dist.destroy_process_group()

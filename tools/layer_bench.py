@@ -9,6 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from step_amd import _capi, _lib  # noqa: E402
+from tools import abkit  # noqa: E402
 
 TORCH_DT = {_capi.F32: torch.float32, _capi.BF16: torch.bfloat16, _capi.F16: torch.float16}
 
@@ -23,18 +24,6 @@ LAYERS = [
     ("4c_b1b", 112, 224, 3, 8, 14, 14), ("4d_b1b", 128, 256, 3, 8, 14, 14), ("4e_b1b", 144, 288, 3, 8, 14, 14),
     ("4f_b0", 528, 256, 1, 8, 14, 14), ("4f_b1b", 160, 320, 3, 8, 14, 14), ("4f_b2b", 32, 128, 3, 8, 14, 14),
 ]
-
-
-def time_it(fn, iters):
-    fn()
-    torch.cuda.synchronize()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(iters):
-        fn()
-    e.record()
-    torch.cuda.synchronize()
-    return s.elapsed_time(e) / iters
 
 
 def main():
@@ -70,14 +59,14 @@ def main():
     sc = torch.ones(64, device=dev)
     sh = torch.zeros(64, device=dev)
     y = torch.empty(B, 16, 112, 112, 64, dtype=tdt, device=dev)
-    ms = time_it(lambda: _capi.check(L.step_stem_forward(dt, _lib.dptr(x), B, 32, 224, 224, _lib.dptr(wp), _lib.dptr(sc), _lib.dptr(sh), 1, 64, _lib.dptr(y), 64, 0, st), "stem"), a.iters)
+    ms = abkit.event_ms(lambda: _capi.check(L.step_stem_forward(dt, _lib.dptr(x), B, 32, 224, 224, _lib.dptr(wp), _lib.dptr(sc), _lib.dptr(sh), 1, 64, _lib.dptr(y), 64, 0, st), "stem"), a.iters, warm=1)
     gf = 2 * B * 16 * 112 * 112 * 64 * 1029 / 1e9
     print("%-8s %8.3f ms %8.1f TFLOP/s (useful)" % ("stem", ms, gf / ms))
     tot_ms += ms
     tot_gf += gf
     # pool 2a
     y2 = torch.empty(B, 16, 56, 56, 64, dtype=tdt, device=dev)
-    ms = time_it(lambda: _capi.check(L.step_maxpool3d_tf(dt, _lib.dptr(y), B, 16, 112, 112, 64, 64, 0, 1, 3, 3, 1, 2, 2, _lib.dptr(y2), 64, 0, st), "pool"), a.iters)
+    ms = abkit.event_ms(lambda: _capi.check(L.step_maxpool3d_tf(dt, _lib.dptr(y), B, 16, 112, 112, 64, 64, 0, 1, 3, 3, 1, 2, 2, _lib.dptr(y2), 64, 0, st), "pool"), a.iters, warm=1)
     byts = (y.numel() + y2.numel()) * y.element_size()
     print("%-8s %8.3f ms %8.1f GB/s" % ("pool2a", ms, byts / ms / 1e6))
     tot_ms += ms
@@ -95,7 +84,7 @@ def run_layers(L, dt, tdt, dev, st, B, a, layers, tot_ms=0.0, tot_gf=0.0):
         y = torch.empty(B, D, H, W, co, dtype=tdt, device=dev)
         d = _capi.ConvDesc(dtype=dt, N=B, D=D, H=H, W=W, Cin=ci, Cout=co, kd=k, kh=k, kw=k, x_cstride=ci, x_coff=0,
                            y_cstride=co, y_coff=0, res_cstride=0, res_coff=0, relu=1, split=0, y2_cstride=0, y2_coff=0)
-        ms = time_it(lambda: _capi.check(L.step_conv_forward(ctypes.byref(d), _lib.dptr(x), _lib.dptr(wp), _lib.dptr(sc), _lib.dptr(sh), None, _lib.dptr(y), None, st), name), a.iters)
+        ms = abkit.event_ms(lambda: _capi.check(L.step_conv_forward(ctypes.byref(d), _lib.dptr(x), _lib.dptr(wp), _lib.dptr(sc), _lib.dptr(sh), None, _lib.dptr(y), None, st), name), a.iters, warm=1)
         gf = 2.0 * B * D * H * W * co * ci * k ** 3 / 1e9
         byts = (x.numel() + y.numel() + wp.numel()) * x.element_size()
         kn = ctypes.create_string_buffer(256)

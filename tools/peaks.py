@@ -1,21 +1,15 @@
 """tools/peaks.py -- achievable peaks of the box next to the datasheet values: a device-to-device stream copy
 (HBM read + write) and a large bf16 / fp32 GEMM through torch (hipBLASLt / rocBLAS) for the matrix cores."""
+import os
+import sys
+
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools import abkit  # noqa: E402
+
 dev = torch.device("cuda:0")
-
-
-def timed(fn, n):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e-3
+timed = lambda fn, n: abkit.event_ms(fn, n, warm=3) * 1e-3       # seconds per call
 
 
 for mb in (256, 1024, 4096):

@@ -17,8 +17,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from step_amd import _capi  # noqa: E402
+from tools import abkit  # noqa: E402
 
-PROBE_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libstep_amd_probe.so")
 MAXWG = 1 << 15
 
 
@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--tail", type=int, default=0, help="conv_tail option (0: one launch, no NB = 1 tail launch that would overwrite records)")
     a = ap.parse_args()
-    L = _capi.declare(ctypes.CDLL(PROBE_LIB), strict=False)
+    L = abkit.load_build("probe")
     L.step_probe_set.argtypes = [ctypes.c_void_p]
     L.step_probe_set.restype = None
     dev = torch.device("cuda:0")

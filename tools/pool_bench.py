@@ -9,6 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from step_amd import _capi, _lib, ops  # noqa: E402
+from tools import abkit  # noqa: E402
 
 # (name, C, D, H, W, kernel, stride) per clip
 C2 = [("pool2a", 64, 16, 112, 112, (1, 3, 3), (1, 2, 2)), ("pool3a", 192, 16, 56, 56, (1, 3, 3), (1, 2, 2)),
@@ -27,21 +28,9 @@ B3 = {"c2": [("3b_b3", 192, 32, 16, 28, 28), ("3c_b3", 256, 64, 16, 28, 28)],
       "c3": [("3b_b3", 192, 32, 18, 50, 50), ("3c_b3", 256, 64, 18, 50, 50)]}
 
 
-def timed(fn, iters):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3
-
-
 def branch3(a, dev):
     bf = torch.bfloat16
+    timed = lambda fn, iters: abkit.event_ms(fn, iters, warm=3) * 1e3          # us per launch
     for name, Cin, Cout, D, H, W in B3[a.set]:
         x = torch.randn(a.batch, D, H, W, Cin, device=dev).to(bf)
         w = ops.pack_conv_weight(torch.randn(Cout, Cin, 1, 1, 1, device=dev) / Cin ** 0.5, bf)
@@ -61,33 +50,21 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--set", default="c2")
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--lib", default=None, help="NAME: time tools/libstep_amd_NAME.so (an experiment build: make -C step_amd/csrc EXP=NAME EXPFLAGS=-D...)")
+    ap.add_argument("--lib", default=None, help="NAME: time the experiment build NAME (abkit.load_build: make -C step_amd/csrc EXP=NAME EXPFLAGS=-D...)")
     ap.add_argument("--branch3-only", action="store_true")
     a = ap.parse_args()
-    if a.lib:
-        import ctypes
-        _lib.lib()
-        _lib._LIB = _capi.declare(ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libstep_amd_%s.so" % a.lib)), strict=False)
-    dev = torch.device("cuda:0")
-    tot = 0.0
-    for name, C, D, H, W, k, s in ([] if a.branch3_only else C2 if a.set == "c2" else C3):
-        x = torch.randn(a.batch, D, H, W, C, device=dev).to(torch.bfloat16)
-        y = ops.maxpool_tf(x, k, s)
-        for _ in range(3):
-            ops.maxpool_tf(x, k, s, y)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            ops.maxpool_tf(x, k, s, y)
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) / a.iters * 1e3
-        tot += us
-        print("%-8s C=%3d %2dx%3dx%3d k%s s%s  %7.1f us  %6.0f GB/s" % (name, C, D, H, W, "".join(map(str, k)), "".join(map(str, s)), us,
-                                                                    (x.numel() + y.numel()) * 2 / us * 1e-3))
-    print("total %.1f us" % tot)
-    branch3(a, dev)
+    with _lib.use(abkit.load_build(a.lib) if a.lib else _lib.lib()):
+        dev = torch.device("cuda:0")
+        tot = 0.0
+        for name, C, D, H, W, k, s in ([] if a.branch3_only else C2 if a.set == "c2" else C3):
+            x = torch.randn(a.batch, D, H, W, C, device=dev).to(torch.bfloat16)
+            y = ops.maxpool_tf(x, k, s)
+            us = abkit.event_ms(lambda: ops.maxpool_tf(x, k, s, y), a.iters, warm=3) * 1e3
+            tot += us
+            print("%-8s C=%3d %2dx%3dx%3d k%s s%s  %7.1f us  %6.0f GB/s" % (name, C, D, H, W, "".join(map(str, k)), "".join(map(str, s)), us,
+                                                                        (x.numel() + y.numel()) * 2 / us * 1e-3))
+        print("total %.1f us" % tot)
+        branch3(a, dev)
 
 
 if __name__ == "__main__":

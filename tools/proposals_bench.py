@@ -11,17 +11,16 @@ spread (min .. max of the rounds) beside its median:
     python tools/proposals_bench.py [--prev] [--out profiles/proposals_timing.txt]
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 import torch
-from step_amd import _capi, _lib, driver, workloads
+from step_amd import _lib, driver, workloads
+from tools import abkit
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
@@ -35,34 +34,17 @@ ap.add_argument("--skip-inference", action="store_true")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "tools/proposals_bench.py needs a ROCm device"
 dev = torch.device("cuda:0")
-lines = []
-
-
-def say(s=""):
-    print(s, flush=True)
-    lines.append(s)
+say = abkit.tee(a.out)
+wall = abkit.wall_ms
 
 
 def prev_library():
     """the parent's library behind this tree's host layer: the two new entries fall back to the parent's own (their new pointers are NULL
     wherever the anchor form calls them)"""
-    L = ctypes.CDLL(os.path.join(ROOT, "tools", "libstep_amd_prev.so"))
-    for name, (res, args) in _capi.SIGNATURES.items():
-        if hasattr(L, name):
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
+    L = abkit.load_build("prev")
     L.step_select_train_counted = lambda *v: L.step_select_train(*v[:-2], v[-1])
     L.step_augment_plan_tubes = lambda *v: L.step_augment_plan(*v[:17], v[-1])
     return L
-
-
-def wall(fn, n):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n * 1e3
 
 
 res = {}
@@ -76,12 +58,8 @@ if not a.skip_train:
             return w.capture(warmup=3)
 
         if a.prev:
-            this = _lib._LIB or _lib.lib()
-            _lib._LIB = prev_library()
-            try:
+            with _lib.use(prev_library()):
                 forms["anchors x 34, parent's library"] = build(tubes_per_clip=34)
-            finally:
-                _lib._LIB = this
         forms["anchors x 34, this library"] = build(tubes_per_clip=34)
         wp = build(proposals=34)
         forms["proposals=34 (counts %s)" % (wp.d_count.tolist(),)] = wp
@@ -141,6 +119,4 @@ if not a.skip_inference:
             "; ".join("%s median %.3f ms (min %.3f .. max %.3f)" % (k, float(np.median(v)), min(v), max(v)) for k, v in ms.items()))
         res["inference_fill_%.2f" % fill] = ms
 say(json.dumps(res))
-if a.out:
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+say.close()

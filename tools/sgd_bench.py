@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from step_amd import _capi, _lib
+from tools import abkit
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
@@ -51,16 +52,6 @@ def adam():
                 "step_adam_flat")
 
 
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.launches):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / a.launches              # us per launch
-
-
 forms = (("sgd", sgd, 24), ("adam", adam, 32), ("sgd_first", sgd_first, 20))
 for _, fn, _ in forms:
     for _ in range(5):
@@ -69,7 +60,7 @@ torch.cuda.synchronize()
 us = {k: [] for k, _, _ in forms}
 for _ in range(a.rounds):
     for k, fn, _ in forms:
-        us[k].append(timed(fn))
+        us[k].append(abkit.event_ms(fn, a.launches) * 1e3)     # us per launch
 res = {"elements": n, "launches": a.launches, "rounds": a.rounds}
 for k, _, bpe in forms:
     med = float(np.median(us[k]))

@@ -11,18 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from step_amd import ops  # noqa: E402
-
-
-def timeit(fn, iters=10):
-    fn(); fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters * 1e3
+from tools import abkit  # noqa: E402
 
 
 def main():
@@ -41,8 +30,8 @@ def main():
         ref = ops.stem_wgrad(x, g32, 64)
         got = ops.stem_wgrad16(x, g, 64)
         err = float((got - ref).norm() / ref.norm())
-        t0 = timeit(lambda: ops.stem_wgrad(x, g32, 64))
-        t1 = timeit(lambda: ops.stem_wgrad16(x, g, 64))
+        t0 = abkit.event_ms(lambda: ops.stem_wgrad(x, g32, 64), 10, warm=2) * 1e3
+        t1 = abkit.event_ms(lambda: ops.stem_wgrad16(x, g, 64), 10, warm=2) * 1e3
         gf = 2.0 * a.n * To * Ho * Ho * 64 * 1029 / 1e9
         print("%s  [%d,%d,3,%d,%d]: stem_wgrad %.1f us (%.0f TF)   stem_wgrad16 %.1f us (%.0f TF)   rel diff %.2e" % (
             str(dt)[6:], a.n, a.t, a.hw, a.hw, t0, gf / t0 * 1e3, t1, gf / t1 * 1e3, err))

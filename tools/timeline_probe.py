@@ -18,24 +18,15 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from step_amd import _capi  # noqa: E402
+from tools import abkit  # noqa: E402
 from tools.ab_bench import C2, C3  # noqa: E402
 
-PROBE_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libstep_amd_probe.so")
 MAXWG = 1 << 17
 
 
 def report(L, name, run, probe, stem=False):
     L.step_probe_set(None)
-    for _ in range(3):
-        run()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(10):
-        run()
-    e1.record()
-    torch.cuda.synchronize()
-    kern_us = e0.elapsed_time(e1) * 100.0
+    kern_us = abkit.event_ms(run, 10, warm=3) * 1e3
     probe.zero_()
     L.step_probe_set(ctypes.c_void_p(probe.data_ptr()))
     run()                                   # (a layer with a tail launch overwrites the first blocks' records: run with conv_tail=0 for those)
@@ -95,7 +86,7 @@ def main():
     ap.add_argument("--stem", action="store_true", help="the stem (stem_stream_kernel) instead of the conv_tap layers")
     ap.add_argument("--var", default="", help="option=VAL[,option=VAL] planner options")
     a = ap.parse_args()
-    L = _capi.declare(ctypes.CDLL(PROBE_LIB))
+    L = abkit.load_build("probe", strict=True)
     L.step_probe_set.argtypes = [ctypes.c_void_p]
     L.step_probe_set.restype = None
     for kv in a.var.split(","):

@@ -1,50 +1,26 @@
-"""tools/two_in_flight.py -- C2 throughput with ONE captured step replayed back to back against TWO captured steps (two batches, two
-streams) replayed alternately, so that the tail of one batch's launches overlaps the other's (GPU only, measurement aid)."""
+"""tools/two_in_flight.py -- C2 throughput with ONE captured step replayed back to back against N captured steps (N batches, N streams;
+default 2) replayed alternately, so that the tail of one batch's launches overlaps the other's: tools/step_ab.py's run of the default
+variant with the legs 1 and N (GPU only, measurement aid).     python tools/two_in_flight.py [N]
+
+It prints ONE line, the median (element len // 2) and the minimum of three rounds of 200 steps per leg.  Before the harness it printed
+three lines, one per round, with that round's two raw figures and every batch on a side stream: the lines quoted in DESIGN.md 3.2 and
+bench.py's comments are of that form."""
+import argparse
 import os
 import sys
-import time
-
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench  # noqa: E402
+from tools import abkit, step_ab  # noqa: E402
 
 
 def main():
-    dev = torch.device("cuda:0")
-    net = bench.build_net(dev)
-    NF = int(sys.argv[1]) if len(sys.argv) > 1 else 2
-    xs = [(torch.rand(8, 32, 3, 224, 224) * 2 - 1).to(dev).to(torch.bfloat16) for _ in range(NF)]
-    streams = [torch.cuda.Stream(dev) for _ in range(NF)]
-    graphs = []
-    with torch.no_grad():
-        net(xs[0]); net(xs[1])
-        torch.cuda.synchronize()
-        for i in range(NF):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.stream(streams[i]):
-                for _ in range(2):
-                    net(xs[i])
-                torch.cuda.synchronize()
-                with torch.cuda.graph(g, stream=streams[i]):
-                    y = net(xs[i])
-            graphs.append((g, y))
-    torch.cuda.synchronize()
-
-    def run(two, steps=200):
-        for _ in range(20):
-            graphs[0][0].replay()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for k in range(steps):
-            i = (k % NF) if two else 0
-            with torch.cuda.stream(streams[i]):
-                graphs[i][0].replay()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / steps * 1e3
-    for _ in range(3):
-        a, b = run(False), run(True)
-        print("one batch in flight: %.4f ms/step = %.0f clips/s | %d in flight: %.4f ms/step = %.0f clips/s" % (a, 8 / a * 1e3, NF, b, 8 / b * 1e3))
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", nargs="?", type=int, default=2, help="batches in flight beside the one-batch leg")
+    a = ap.parse_args()
+    clips, _, (t,) = step_ab.run([abkit.Variant.parse("default")], "c2", (1, a.n), rounds=3, steps=200)
+    one, many = t[1], t[a.n]
+    print("one batch in flight: %.4f ms/step (min %.4f) = %.0f clips/s | %d in flight: %.4f ms/step (min %.4f) = %.0f clips/s" % (
+        one.median, one.min, clips / one.median * 1e3, a.n, many.median, many.min, clips / many.median * 1e3))
 
 
 if __name__ == "__main__":

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 from step_amd import BaseTransform, VideoClips, _capi, _lib
 from step_amd.video import clip_frame_indices
+from tools import abkit
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
@@ -38,29 +39,14 @@ a = ap.parse_args()
 assert torch.cuda.is_available(), "tools/video_bench.py needs a ROCm device"
 dev = torch.device("cuda:0")
 L = _lib.lib()
-lines = []
-
-
-def say(s=""):
-    print(s, flush=True)
-    lines.append(s)
-
+say = abkit.tee(a.out)
+timed = abkit.event_ms                                                         # ms per launch, no warm-up of its own: every form is warmed below
 
 T, CHUNKS, SRC_FPS, DST_FPS, Hs, Ws, Ho, Wo, BATCH = 3, 3, 30, 12, 256, 340, 400, 400, 4
 FRAMES = T * CHUNKS * 4
 rs = np.random.RandomState(12)
 video = rs.randint(0, 256, (a.numf, Hs, Ws, 3)).astype(np.uint8)
 aug = BaseTransform((Wo, Ho), scale=2)
-
-
-def timed(fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
 
 
 # ---- kernels ----------------------------------------------------------------------------------------------------------------------------
@@ -132,7 +118,7 @@ del keep, calls
 torch.cuda.empty_cache()
 
 
-# ---- loaders ----------------------------------------------------------------------------------------------------------------------------
+# ---- loaders (their own host clock: one pass over the whole video with a synchronise per batch, returned with the bytes it moved) ------------
 def per_clip_path():
     """np.stack of every clip's frames, upload, BaseTransform.apply -- batch by batch; returns (seconds, H2D bytes)."""
     moved = 0
@@ -172,6 +158,4 @@ for k, v in runs.items():
     say("  %-14s %8.3f ms per clip (min %.3f .. max %.3f)   H2D %10.0f bytes per clip" % (k, float(np.median(v)), min(v), max(v), moved[k]))
 say("  uploads per video: %d frames against %d (= %d x numf), by construction" % (a.numf, FRAMES * a.numf, FRAMES))
 say(json.dumps({"hbm_probe_TBps": hbm / 1e12, "kernels": res, "loader_ms_per_clip": runs, "h2d_bytes_per_clip": moved}))
-if a.out:
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+say.close()

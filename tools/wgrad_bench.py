@@ -7,6 +7,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from step_amd import _capi, _lib, ops  # noqa: E402
+from tools import abkit  # noqa: E402
 
 # (name, N, Cin, Cout, k, D, H, W)
 LAYERS = [("2c@400", 1, 64, 192, 3, 18, 100, 100), ("3c_b1b@400", 1, 128, 192, 3, 18, 50, 50), ("4f_b1b@400", 1, 160, 320, 3, 9, 25, 25),
@@ -36,14 +37,9 @@ def main():
     print("%-14s %s" % ("layer", "  ".join("%26s" % v[0] for v in variants)))
     if a.lds_only:
         variants = [v for v in variants if v[1] == "lds"]
+    libs = {"default": _lib.lib()}
     if a.libs:
-        import ctypes
-        base = _lib.lib()
-        libs = {"default": base}
-        for nm in a.libs.split(","):
-            L_ = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libstep_amd_%s.so" % nm))
-            _capi.declare(L_, strict=False)
-            libs[nm] = L_
+        libs.update((nm, abkit.load_build(nm)) for nm in a.libs.split(","))
         variants = [("LDS tiles, lib=" + nm, "lib:" + nm) for nm in libs]
     for name, N, ci, co, k, D, H, W in LAYERS:
         if a.only and not any(o in name for o in a.only.split(",")):
@@ -55,46 +51,34 @@ def main():
         gf = 2.0 * N * D * H * W * ci * co * kk[0] * kk[1] * kk[2] / 1e9
         cells, ref = [], None
         for _, row in variants:
-            if row is None:
-                fn = lambda: ops.conv_wgrad(x, gy16.float(), co, kk)     # (same rounded dY as the 16-bit forms)
-                g32 = gy16.float()
-                fn = lambda: ops.conv_wgrad(x, g32, co, kk)
-            elif row.startswith("lib:"):
-                _lib._LIB = libs[row[4:]]
-                fn = lambda: ops.conv_wgrad16(x, gy16, co, kk)
-            else:
-                _capi.set_option(_lib.lib(), "wgrad16_lds", 1 if row == "lds" else 0)
-                fn = lambda: ops.conv_wgrad16(x, gy16, co, kk)
-            out = fn()
-            torch.cuda.synchronize()
-            if ref is None:
-                ref = out
-            else:
-                err = float((out - ref).abs().max() / ref.abs().max())
-                assert err < 1e-3, (name, row, err)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            if a.graph:
-                gr = torch.cuda.CUDAGraph()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    fn()
-                    with torch.cuda.graph(gr, stream=side):
-                        for _ in range(a.iters):
-                            fn()
-                torch.cuda.current_stream().wait_stream(side)
-                gr.replay()
+            with _lib.use(libs[row[4:]] if row and row.startswith("lib:") else libs["default"]):
+                if row is None:
+                    g32 = gy16.float()                                   # (same rounded dY as the 16-bit forms)
+                    fn = lambda: ops.conv_wgrad(x, g32, co, kk)
+                else:
+                    if not row.startswith("lib:"):
+                        _capi.set_option(_lib.lib(), "wgrad16_lds", 1 if row == "lds" else 0)
+                    fn = lambda: ops.conv_wgrad16(x, gy16, co, kk)
+                out = fn()
                 torch.cuda.synchronize()
-                e0.record()
-                gr.replay()
-                e1.record()
-            else:
-                e0.record()
-                for _ in range(a.iters):
-                    fn()
-                e1.record()
-            torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1) / a.iters
+                if ref is None:
+                    ref = out
+                else:
+                    err = float((out - ref).abs().max() / ref.abs().max())
+                    assert err < 1e-3, (name, row, err)
+                if a.graph:
+                    gr = torch.cuda.CUDAGraph()
+                    side = torch.cuda.Stream()
+                    side.wait_stream(torch.cuda.current_stream())
+                    with torch.cuda.stream(side):
+                        fn()
+                        with torch.cuda.graph(gr, stream=side):
+                            for _ in range(a.iters):
+                                fn()
+                    torch.cuda.current_stream().wait_stream(side)
+                    ms = abkit.event_ms(gr.replay, 1, warm=1) / a.iters
+                else:
+                    ms = abkit.event_ms(fn, a.iters)
             cells.append("%10.3f ms %7.1f TFLOP/s" % (ms, gf / ms))
         print("%-14s %s" % (name, "  ".join(cells)))
 
