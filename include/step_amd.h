@@ -920,6 +920,37 @@ STEP_API int step_tube_update(const float* tubes, int N, int T, const float* loc
                               float width, float height, float* pred_loc, float* pred_first, float* pred_last,
                               float* next_tubes, step_stream_t stream);
 
+/* Tube growth outside temporal_mode "predict": the tube's own boxes grow it from T to Tn = T + 2 Tw frames, one launch, fp32, every
+ * operation rounded on its own (no contraction).  grow(boxes[T], Tw, mode), with new[Tw .. Tw+T-1] = boxes and L = Tn:
+ *   mode 1, "extrapolate" (tube_utils.py:159-176): for i = 0 .. Tw-1, in this order,
+ *             new[L-Tw+i] = a * new[L-Tw+i-1] - b * new[L-2Tw+i]        new[Tw-i-1] = a * new[Tw-i] - b * new[2Tw-i-1]
+ *           a = (float)(Tw / (Tw-1)), b = (float)(1 / (Tw-1)) (the quotients in double, rounded to fp32 once: what numpy makes of the
+ *           reference's Python floats), two rounded products and a rounded difference per step; then on EVERY frame x1, y1 are clamped
+ *           below at 0 and x2, y2 above at ext_w - 1, ext_h - 1 (v < 0 ? 0 : v, v > m ? m : v: a NaN stays a NaN, as under np.maximum).
+ *           The reference calls extrapolate_tubes with its 400 x 400 default whatever the image size: callers pass ext_w = ext_h = 400.
+ *   mode 2, "mean" (utils.py:114-118): per coordinate the sequential sum over the T frames in frame order, divided by (float)T
+ *           (np.mean(axis=1) of fp32, step_select_prepare's convention), repeated Tw times on both sides; no clamp.
+ * Errors of both entries: a mode outside {1, 2} -> STEP_E_SHAPE; growing in mode 1 with Tw < 2 or T < Tw -> STEP_E_SHAPE; more than 64
+ * output frames -> STEP_E_UNSUPPORTED; N == 0 -> STEP_OK, nothing launched.
+ *
+ * step_tube_update_mode: one refinement step's bookkeeping in these modes (utils/utils.py:64-129), step_tube_update's counterpart:
+ *   pred_loc   [N,T,4]  = decode_coef(tubes[:, :, 1:5], local_loc)                              (step_tube_update's arithmetic)
+ *   next_tubes [N,Tn,5] = extend ? grow(pred_loc) : pred_loc  (Tn = T + 2 Tw | T), through valid_tubes(width, height) -- a NaN coordinate
+ *                         gives the whole frame --, column 0 = clip_of[n] * Tn + frame.
+ * tubes [N,T,5] fp32 (column 0 ignored), local_loc [N,T,4], clip_of [N] int32.  The head's neighbour regressions are not read. */
+STEP_API int step_tube_update_mode(const float* tubes, int N, int T, const float* local_loc, const int32_t* clip_of, int mode, int extend,
+                                   int Tw, float ext_w, float ext_h, float width, float height, float* pred_loc, float* next_tubes,
+                                   step_stream_t stream);
+
+/* step_tube_grow: the growth alone, for rows that are boxes already.  boxes [N,T,box_cols] fp32, box_cols 4 or 5 (the box is the last
+ * four columns); clip_of [N] int32; mask [N] fp32 or NULL; pad_tubes [B,Tn,4], given iff mask is (otherwise STEP_E_NULL); validate 0, or 1:
+ * valid_tubes(width, height) after growing.  out [N,Tn,5]: column 0 = clip_of[n] * Tn + t on every row; a row with mask[n] == 0 gets
+ * pad_tubes[clip_of[n]] as it lies (never validated), every other row grow(boxes[n]).  With clip_of[n] = n / budget this turns
+ * step_select_train's un-grown sel [B*budget,Tc,5] and mask into the sel it would have written for grown tubes. */
+STEP_API int step_tube_grow(const float* boxes, int box_cols, int N, int T, int Tw, int mode, float ext_w, float ext_h,
+                            const int32_t* clip_of, const float* mask, const float* pad_tubes, int validate, float width, float height,
+                            float* out, step_stream_t stream);
+
 /* Training sample selection, device front end (utils/utils.py:179-214 train_select, utils/tube_utils.py:59-92,269-351): from a
  * previous step's predictions -- prob [N,T,NC], loc [N,T,4], first / last [N,Tw,4] (NULL outside temporal_mode "predict"), all fp32
  * dense -- in one launch: mean_prob [N,NC] = the class scores averaged over the tube's frames (sequential fp32 sum / T, as numpy's

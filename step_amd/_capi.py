@@ -5,7 +5,7 @@ import ctypes as C
 F32, BF16, F16 = 0, 1, 2
 NCHW, NHWC = 0, 1
 ROI_BWD_GATHER, ROI_BWD_ATOMIC = 0, 1
-ABI_VERSION = 49
+ABI_VERSION = 50
 
 vp, fp, ip, u8p = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p   # raw device addresses
 i, f, ll, sz = C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -126,6 +126,8 @@ SIGNATURES = {
     "step_dropout_backward": (i, [i, vp, vp, vp, ll, C.c_double, vp]),
     "step_rng_words": (i, [vp, C.c_ulonglong, ll, vp, vp]),
     "step_tube_update": (i, [fp, i, i, fp, fp, fp, i, i, i, ip, i, f, f, fp, fp, fp, fp, vp]),
+    "step_tube_update_mode": (i, [fp, i, i, fp, ip, i, i, i, f, f, f, f, fp, fp, vp]),
+    "step_tube_grow": (i, [fp, i, i, i, i, i, f, f, ip, fp, fp, i, f, f, fp, vp]),
     "step_select_prepare": (i, [fp, fp, fp, fp, i, i, i, i, ip, fp, ip, i, f, f, fp, fp, fp, fp, fp, vp]),
     "step_select_train": (i, [fp, fp, fp, fp, fp, i, i, i, i, ip, i, i, fp, ip, i, i, fp, vp, i, i, i, i, f, f, i, i, i, i, fp, fp, fp, fp, ip, vp]),
     "step_select_train_counted": (i, [fp, fp, fp, fp, fp, i, i, i, i, ip, i, i, fp, ip, i, i, fp, vp, i, i, i, i, f, f, i, i, i, i, fp, fp, fp, fp, ip, ip, vp]),

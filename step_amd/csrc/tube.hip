@@ -64,6 +64,96 @@ __global__ void tube_update_kernel(TubeParams p) {
     }
 }
 
+// ---- tube growth outside temporal_mode "predict" (step_tube_update_mode, step_tube_grow; include/step_amd.h has the contract) ----------
+// "extrapolate" (tube_utils.py:159-176) and "mean" (utils.py:114-118) grow a tube from its own boxes.  A workgroup owns TB = 256 / Tn tubes
+// in LDS ([tube][frame][4], Tn <= 64 frames): phase 1, a thread per (tube, frame), decodes or loads the T middle boxes; phase 2, a thread
+// per (tube, side, coordinate), runs the Tw sequential steps of its side, or the mean; phase 3, a thread per (tube, output frame), clamps,
+// validates or pads the box and writes its row.  One global round trip in, one out: the launch is latency-bound at tens of tubes.
+__device__ __forceinline__ void valid_box(const float* b, float w, float h, float* o);     // (below, with the selection's front end)
+
+constexpr int GROW_THREADS = 256, GROW_MAX_FRAMES = 64;
+enum { GROW_EXTRAPOLATE = 1, GROW_MEAN = 2 };
+
+struct GrowParams {
+    const float* boxes; const float* local_loc; const int32_t* clip_of; const float* mask; const float* pad;
+    float* pred_loc; float* out;
+    int N, T, Tw, box_cols, mode, extend, validate, TB;
+    float ext_x, ext_y, width, height;                        // ext_x / ext_y = ext_w - 1 / ext_h - 1: extrapolate's upper clamp
+    float ca, cb;                                             // extrapolate's coefficients (grow_launch)
+};
+
+// grow(boxes[T], Tw, mode): coordinate c of one side of the tube at b (frame stride 4, Tn = T + 2 Tw frames, the middle T filled)
+__device__ __forceinline__ void grow(float* b, int T, int Tw, int mode, int side, float ca, float cb) {
+    const int L = T + 2 * Tw;
+    if (mode == GROW_EXTRAPOLATE) {
+        // every product and the difference rounded on their own (the file is compiled without contraction); sequential in i: no closed
+        // form is bit-equal
+        if (side) for (int i = 0; i < Tw; ++i) b[4 * (L - Tw + i)] = ca * b[4 * (L - Tw + i - 1)] - cb * b[4 * (L - 2 * Tw + i)];
+        else      for (int i = 0; i < Tw; ++i) b[4 * (Tw - i - 1)] = ca * b[4 * (Tw - i)] - cb * b[4 * (2 * Tw - i - 1)];
+    } else {
+        float s = b[4 * Tw];                                  // np.mean(axis=1): the sequential sum in frame order / T (select_prepare_kernel's)
+        for (int t = 1; t < T; ++t) s = s + b[4 * (Tw + t)];
+        const float m = s / (float)T;
+        const int at = side ? Tw + T : 0;
+        for (int i = 0; i < Tw; ++i) b[4 * (at + i)] = m;
+    }
+}
+
+__global__ __launch_bounds__(GROW_THREADS) void tube_grow_kernel(GrowParams p) {
+    __shared__ float s_box[GROW_THREADS * 4];                 // TB * Tn <= 256 boxes
+    const int tid = threadIdx.x;
+    const int Tn = p.extend ? p.T + 2 * p.Tw : p.T, off = p.extend ? p.Tw : 0;
+    const long long n0 = (long long)blockIdx.x * p.TB;
+    for (int i = tid; i < p.TB * p.T; i += GROW_THREADS) {
+        const int tl = i / p.T, t = i % p.T;
+        const long long n = n0 + tl;
+        if (n >= p.N) break;
+        const size_t at = (size_t)n * p.T + t;
+        float o[4];
+        if (p.local_loc) {
+            decode_box(p.boxes + at * 5 + 1, p.local_loc + at * 4, o);
+            float* d = p.pred_loc + at * 4;
+            d[0] = o[0]; d[1] = o[1]; d[2] = o[2]; d[3] = o[3];
+        } else {
+            const float* q = p.boxes + at * p.box_cols + (p.box_cols - 4);
+            o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3];
+        }
+        float* s = s_box + (tl * Tn + off + t) * 4;
+        s[0] = o[0]; s[1] = o[1]; s[2] = o[2]; s[3] = o[3];
+    }
+    __syncthreads();
+    if (p.extend) {
+        for (int i = tid; i < p.TB * 8; i += GROW_THREADS) {
+            const int tl = i >> 3;
+            if (n0 + tl >= p.N) break;
+            grow(s_box + tl * Tn * 4 + (i & 3), p.T, p.Tw, p.mode, (i >> 2) & 1, p.ca, p.cb);
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < p.TB * Tn; i += GROW_THREADS) {
+        const int tl = i / Tn, t = i % Tn;
+        const long long n = n0 + tl;
+        if (n >= p.N) break;
+        const int b = p.clip_of[n];
+        float v[4];
+        if (p.mask && p.mask[n] == 0.0f) {                    // a padded slot of the selection: the clip's pad, as it lies
+            const float* q = p.pad + ((size_t)b * Tn + t) * 4;
+            v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+        } else {
+            const float* s = s_box + i * 4;
+            v[0] = s[0]; v[1] = s[1]; v[2] = s[2]; v[3] = s[3];
+            if (p.extend && p.mode == GROW_EXTRAPOLATE) {     // extrapolate_tubes clamps the whole tube; np.maximum / np.minimum keep a NaN
+                v[0] = v[0] < 0.0f ? 0.0f : v[0]; v[1] = v[1] < 0.0f ? 0.0f : v[1];
+                v[2] = v[2] > p.ext_x ? p.ext_x : v[2]; v[3] = v[3] > p.ext_y ? p.ext_y : v[3];
+            }
+            if (p.validate) valid_box(v, p.width, p.height, v);
+        }
+        float* q = p.out + ((size_t)n * Tn + t) * 5;
+        q[0] = (float)b * (float)Tn + (float)t;
+        q[1] = v[0]; q[2] = v[1]; q[3] = v[2]; q[4] = v[3];
+    }
+}
+
 // ---- training sample selection, device front end -------------------------------------------------------------
 // What utils/utils.py:179-214 (train_select) and utils/tube_utils.py:269-351 compute per clip on the host from a previous step's
 // predictions, for EVERY refined tube in one launch: the class scores averaged over the tube's frames, the three predicted tubes
@@ -1021,4 +1111,53 @@ extern "C" int step_tube_update(const float* tubes, int N, int T, const float* l
     if (g > 4096) g = 4096;
     STEP_LAUNCH(tube_update_kernel, dim3((unsigned)g), dim3(256), stream, p);
     return STEP_LAUNCH_CHECK();
+}
+
+// the checks step_tube_update_mode and step_tube_grow share: the growth's own limits
+static int grow_check(int T, int Tw, int mode, int extend) {
+    if (mode != GROW_EXTRAPOLATE && mode != GROW_MEAN) return STEP_E_SHAPE;
+    if (extend && mode == GROW_EXTRAPOLATE && (Tw < 2 || T < Tw)) return STEP_E_SHAPE;      // (division by Tw - 1; the recurrence reaches Tw frames back)
+    if ((extend ? T + 2 * Tw : T) > GROW_MAX_FRAMES) return STEP_E_UNSUPPORTED;
+    return STEP_OK;
+}
+
+static int grow_launch(GrowParams& p, float ext_w, float ext_h, step_stream_t stream) {
+    const int Tn = p.extend ? p.T + 2 * p.Tw : p.T;
+    p.TB = GROW_THREADS / Tn;
+    p.ext_x = ext_w - 1.0f; p.ext_y = ext_h - 1.0f;
+    // the reference's Python-float coefficients T / (T - 1) and 1 / (T - 1), rounded to fp32 once where numpy multiplies an fp32 array by them
+    p.ca = p.Tw > 1 ? (float)((double)p.Tw / (double)(p.Tw - 1)) : 0.0f; p.cb = p.Tw > 1 ? (float)(1.0 / (double)(p.Tw - 1)) : 0.0f;
+    const long long g = ((long long)p.N + p.TB - 1) / p.TB;
+    STEP_LAUNCH(tube_grow_kernel, dim3((unsigned)g), dim3(GROW_THREADS), stream, p);
+    return STEP_LAUNCH_CHECK();
+}
+
+extern "C" int step_tube_update_mode(const float* tubes, int N, int T, const float* local_loc, const int32_t* clip_of, int mode, int extend,
+                                     int Tw, float ext_w, float ext_h, float width, float height, float* pred_loc, float* next_tubes,
+                                     step_stream_t stream) {
+    if (N < 0 || T <= 0 || Tw <= 0) return STEP_E_SHAPE;
+    const int rc = grow_check(T, Tw, mode, extend ? 1 : 0);
+    if (rc != STEP_OK) return rc;
+    if (N == 0) return STEP_OK;
+    if (!tubes || !local_loc || !clip_of || !pred_loc || !next_tubes) return STEP_E_NULL;
+    GrowParams p;
+    p.boxes = tubes; p.local_loc = local_loc; p.clip_of = clip_of; p.mask = nullptr; p.pad = nullptr; p.pred_loc = pred_loc; p.out = next_tubes;
+    p.N = N; p.T = T; p.Tw = Tw; p.box_cols = 5; p.mode = mode; p.extend = extend ? 1 : 0; p.validate = 1;
+    p.width = width; p.height = height;
+    return grow_launch(p, ext_w, ext_h, stream);
+}
+
+extern "C" int step_tube_grow(const float* boxes, int box_cols, int N, int T, int Tw, int mode, float ext_w, float ext_h, const int32_t* clip_of,
+                              const float* mask, const float* pad_tubes, int validate, float width, float height, float* out,
+                              step_stream_t stream) {
+    if (N < 0 || T <= 0 || Tw <= 0 || (box_cols != 4 && box_cols != 5) || (validate != 0 && validate != 1)) return STEP_E_SHAPE;
+    const int rc = grow_check(T, Tw, mode, 1);
+    if (rc != STEP_OK) return rc;
+    if (N == 0) return STEP_OK;
+    if (!boxes || !clip_of || !out || (mask != nullptr) != (pad_tubes != nullptr)) return STEP_E_NULL;
+    GrowParams p;
+    p.boxes = boxes; p.local_loc = nullptr; p.clip_of = clip_of; p.mask = mask; p.pad = pad_tubes; p.pred_loc = nullptr; p.out = out;
+    p.N = N; p.T = T; p.Tw = Tw; p.box_cols = box_cols; p.mode = mode; p.extend = 1; p.validate = validate;
+    p.width = width; p.height = height;
+    return grow_launch(p, ext_w, ext_h, stream);
 }

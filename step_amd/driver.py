@@ -13,7 +13,9 @@ Differences from the reference's host glue (they do not change results):
   * the ROI-pooled features are produced channels-last by the NHWC ROIAlign kernel straight from the
     channels-last backbone feature (no `.contiguous()` transpose of the slice, utils.py:48).
 All three temporal modes of the reference are implemented (utils.py:102-120): "predict" (every shipped script: the head's
-neighbour regressions extend the tube), "extrapolate" (linear, tube_utils.py:159-176) and "mean".
+neighbour regressions extend the tube), "extrapolate" (linear, tube_utils.py:159-176; config.py:92's default) and "mean".  In all three
+a step's bookkeeping is ONE launch (step_tube_update; step_tube_update_mode for the other two, which grow a tube from its own boxes);
+TUBE_KERNEL = False keeps the tensor-op restatement of each.
 """
 import numpy as np
 import torch
@@ -21,7 +23,7 @@ import torch
 from . import ops
 from .tube_math import extrapolate_tubes, decode_coef, valid_tubes
 
-TUBE_KERNEL = True             # per-step tube bookkeeping as one HIP launch (False: the tensor-op restatement below)
+TUBE_KERNEL = True             # per-step tube bookkeeping as one HIP launch, in every temporal mode (False: the tensor-op restatement below)
 COMPACT_KERNEL = True          # postprocess: the detection rows of all iterations and clips compacted by one HIP launch (False: nonzero / gather / bincount);
                                # postprocess_merged always compacts with the launch: step_detect_merge reads its segments
 DETECT_BLOCK = True            # clips of 65 .. 1024 tubes take the fused path too (step_detect_nms' workgroup form); False: they go through
@@ -135,6 +137,18 @@ def inference_flat(args, conv_feat, context_feat, nets, exec_iter, flat, nums, c
                 history[-1]["tubes_count"] = counts
             trajectory.append((flat[:, :, 1:], torch.argmax(prob, dim=-1) if want_classes else None))
             continue
+        if mode in ("extrapolate", "mean") and TUBE_KERNEL and local_loc is not None and flat.shape[1] == T_length:
+            # decode -> extrapolate_tubes / mean tiling -> valid_tubes -> frame-index column: one launch (step_tube_update_mode); the head's
+            # neighbour regressions are neither decoded nor kept in these modes (utils.py:83-84)
+            if clip32 is None:
+                clip32 = clip_of.to(torch.int32)
+            pred_loc, flat = ops.tube_update_mode(flat, local_loc, clip32, mode, extend, args.T, args.image_size[0], args.image_size[1])
+            history.append({"pred_prob": pred_prob.detach(), "pred_loc": pred_loc, "pred_first_loc": None, "pred_last_loc": None,
+                            "tubes_nums": list(nums)})
+            if counts is not None:
+                history[-1]["tubes_count"] = counts
+            trajectory.append((flat[:, :, 1:], torch.argmax(prob, dim=-1) if want_classes else None))
+            continue
         flat = flat.to(local_loc)
         pred_loc = decode_coef(flat.reshape(-1, 5)[:, 1:], local_loc.reshape(-1, 4)).view(local_loc.shape)
         lo, hi = chunk_idx[0] - half_T, chunk_idx[0] + half_T + 1
@@ -154,7 +168,13 @@ def inference_flat(args, conv_feat, context_feat, nets, exec_iter, flat, nums, c
             elif mode == "extrapolate":
                 prop = extrapolate_tubes(pred_loc, args.T)
             else:                                               # the tube's mean box on both sides (utils.py:116-120)
-                m = pred_loc.mean(dim=1, keepdim=True).expand(-1, args.T, -1)
+                # np.mean's arithmetic, bit for bit: the sequential fp32 sum in frame order, DIVIDED by the frame count.  torch's mean, and
+                # its division by a host scalar, multiply by fl(1 / Tl) instead (a third of the values differ in the last bit at Tl = 3):
+                # the divisor is a device tensor
+                s = pred_loc[:, 0]
+                for t in range(1, pred_loc.shape[1]):
+                    s = s + pred_loc[:, t]
+                m = (s / torch.full_like(s, float(pred_loc.shape[1]))).unsqueeze(1).expand(-1, args.T, -1)
                 prop = torch.cat([m, pred_loc, m], dim=1)
         else:
             prop = pred_loc

@@ -1304,6 +1304,63 @@ def tube_update(flat, local_loc, first_loc, last_loc, clip_of, first_off, last_o
     return pl, pf, pla, nxt
 
 
+GROW_MODES = {"extrapolate": 1, "mean": 2}
+EXTRAPOLATE_SIZE = 400.0       # the reference calls extrapolate_tubes with its 400 x 400 default whatever the image size (utils.py:113)
+
+
+def tube_update_mode(flat, local_loc, clip_of, mode, extend, Tw, width, height):
+    """One refinement step's tube bookkeeping in temporal_mode "extrapolate" / "mean" (step_tube_update_mode): flat [N,T,5], local_loc
+    [N,T,4], clip_of [N] int32 -> (pred_loc [N,T,4], next_flat [N,Tn,5]), Tn = T + 2 Tw when extend else T."""
+    L = _lib.lib()
+    N, T, _ = flat.shape
+    f32 = lambda t: t.detach().float().contiguous()
+    flat, local_loc = f32(flat), f32(local_loc)
+    if tuple(local_loc.shape) != (N, T, 4) or tuple(clip_of.shape) != (N,):
+        raise RuntimeError("step_amd: tube_update_mode wants local_loc [N=%d,T=%d,4] and clip_of [N], got %s and %s"
+                           % (N, T, tuple(local_loc.shape), tuple(clip_of.shape)))
+    if clip_of.dtype != torch.int32:
+        clip_of = clip_of.to(torch.int32)
+    Tn = T + 2 * int(Tw) if extend else T
+    dev = flat.device
+    pl = torch.empty((N, T, 4), dtype=torch.float32, device=dev)
+    nxt = torch.empty((N, Tn, 5), dtype=torch.float32, device=dev)
+    _capi.check(L.step_tube_update_mode(_lib.dptr(flat), N, T, _lib.dptr(local_loc), _lib.dptr(clip_of.contiguous()), GROW_MODES[mode],
+                                        int(bool(extend)), int(Tw), EXTRAPOLATE_SIZE, EXTRAPOLATE_SIZE, float(width), float(height),
+                                        _lib.dptr(pl), _lib.dptr(nxt), _lib.stream_ptr(dev)), "step_tube_update_mode")
+    return pl, nxt
+
+
+def tube_grow(boxes, Tw, mode, clip_of, mask=None, pad_tubes=None, validate=False, width=0.0, height=0.0, out=None):
+    """step_tube_grow: boxes [N,T,4 | 5] fp32 (the box is the last four columns) grown to Tn = T + 2 Tw frames by temporal_mode
+    "extrapolate" / "mean" -> out [N,Tn,5], column 0 = clip_of[n] * Tn + t.  mask [N] or [N,1] fp32 with pad_tubes [B,Tn,4]: a row with
+    mask 0 gets its clip's pad.  validate: valid_tubes(width, height) after growing.  out: the caller's (static) buffer.  No host
+    synchronisation."""
+    L = _lib.lib()
+    dev = boxes.device
+    if boxes.dtype != torch.float32 or not boxes.is_contiguous() or boxes.dim() != 3 or boxes.shape[2] not in (4, 5):
+        raise RuntimeError("step_amd: tube_grow wants boxes as a contiguous float32 tensor [N,T,4|5], got %s %s" % (tuple(boxes.shape), boxes.dtype))
+    N, T, cols = boxes.shape
+    Tn = T + 2 * int(Tw)
+    if clip_of.dtype != torch.int32 or not clip_of.is_contiguous() or tuple(clip_of.shape) != (N,) or clip_of.device != dev:
+        raise RuntimeError("step_amd: tube_grow wants clip_of as a contiguous int32 tensor [N=%d] on %s" % (N, dev))
+    if (mask is None) != (pad_tubes is None):
+        raise RuntimeError("step_amd: tube_grow takes mask and pad_tubes together")
+    if mask is not None:
+        if mask.dtype != torch.float32 or not mask.is_contiguous() or mask.numel() != N or mask.device != dev:
+            raise RuntimeError("step_amd: tube_grow wants mask as a contiguous float32 tensor of N=%d elements on %s" % (N, dev))
+        if (pad_tubes.dtype != torch.float32 or not pad_tubes.is_contiguous() or pad_tubes.dim() != 3 or tuple(pad_tubes.shape[1:]) != (Tn, 4)
+                or pad_tubes.device != dev):
+            raise RuntimeError("step_amd: tube_grow wants pad_tubes as a contiguous float32 tensor [B,Tn=%d,4] on %s, got %s" % (Tn, dev, tuple(pad_tubes.shape)))
+    if out is None:
+        out = torch.empty((N, Tn, 5), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (N, Tn, 5) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError("step_amd: tube_grow output wants shape %s float32, got %s %s" % ((N, Tn, 5), tuple(out.shape), out.dtype))
+    _capi.check(L.step_tube_grow(_lib.dptr(boxes), cols, N, T, int(Tw), GROW_MODES[mode], EXTRAPOLATE_SIZE, EXTRAPOLATE_SIZE, _lib.dptr(clip_of),
+                                 _lib.dptr(mask), _lib.dptr(pad_tubes), int(bool(validate)), float(width), float(height), _lib.dptr(out),
+                                 _lib.stream_ptr(dev)), "step_tube_grow")
+    return out
+
+
 def grad_norm_workspace(n, n_seg, device):
     """the fp64 scratch step_grad_norm_flat wants for an arena of n elements in n_seg segments (uninitialised: every slot read is written first)"""
     nbytes = int(_lib.lib().step_grad_norm_workspace_bytes(int(n), int(n_seg)))

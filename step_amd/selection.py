@@ -19,7 +19,9 @@ selection of train_cls.py:263-291.  `DeviceClsSelector` is their opt-in device f
 
 `DeviceSelector` is the opt-in device form of the same rule (step_select_train, include/step_amd.h): no host synchronisation, static
 output shapes, draws from the device-side generator -- its own stream of draws and index-ordered ties, so it selects other tubes than
-the reference does under the reference's seeds.  `train_select` stays the default and the one that is pinned to the reference.
+the reference does under the reference's seeds.  `train_select` stays the default and the one that is pinned to the reference.  Built with
+`temporal_modes=("predict", "extrapolate", "mean")` it takes all three modes (step_tube_grow grows the selected rows of the other two);
+without the keyword it refuses them, as it always has.
 """
 import random
 
@@ -297,12 +299,23 @@ def _prepare_on_device(history, targets, mid, predict, W, H):
 class DeviceSelector:
     """train_select for a FIXED batch on the device: select(step, ...) is step_select_prepare (step > 1) + step_select_train on the
     current stream, into static buffers -- nothing is copied to the host, nothing waits, so the calls can be recorded in a graph and the
-    draws (step_amd.rng.DeviceRNG: one offset per select()) change from replay to replay.  temporal_mode "predict" only."""
+    draws (step_amd.rng.DeviceRNG: one offset per select()) change from replay to replay.
 
-    def __init__(self, args, batch, budget, device, rng, dynamic_gt=False):
+    temporal_modes: the allow-list of args.temporal_mode values this selector may be built for.  The default is ("predict",): the
+    selector was written for that mode alone, callers (and tests/select_cases.py) rely on the positional form refusing the other two
+    with NotImplementedError before any launch, and a caller that never asked for them should keep falling back to the host selection
+    rather than silently change path.  temporal_modes=("predict", "extrapolate", "mean") admits all three: outside "predict" the step
+    that grows the tubes selects the un-grown rows (step_select_train without neighbour candidates, into a scratch buffer) and grows
+    the selected rows from their own boxes (step_tube_grow), as train_select does -- without valid_tubes after the growth, like it --
+    and no step writes neighbour targets."""
+
+    ALL_MODES = ("predict", "extrapolate", "mean")
+
+    def __init__(self, args, batch, budget, device, rng, dynamic_gt=False, temporal_modes=("predict",)):
         import torch
-        if args.temporal_mode != "predict":
-            raise NotImplementedError("DeviceSelector: temporal_mode %r stays on the host path (selection.train_select)" % (args.temporal_mode,))
+        if args.temporal_mode not in temporal_modes or args.temporal_mode not in self.ALL_MODES:
+            raise NotImplementedError("DeviceSelector: temporal_mode %r stays on the host path (selection.train_select) unless temporal_modes= "
+                                      "admits it" % (args.temporal_mode,))
         if args.selection_sampling not in ("uniform", "random", "softmax"):
             raise NotImplementedError(args.selection_sampling)
         if budget < args.max_pos_num * (1 + args.neg_ratio):
@@ -315,11 +328,15 @@ class DeviceSelector:
         # which bumps no tensor version -- so the middle-frame gather is issued on every select() (and recorded with it in a graph)
         self.dynamic_gt = bool(dynamic_gt)
         self.out = {}
+        self._ungrown = {}                                       # outside "predict": the growing steps' selected rows before step_tube_grow
+        self._slot_clip = torch.arange(self.batch, dtype=torch.int32, device=self.device).repeat_interleave(self.budget)
         for i in range(1, args.max_iter + 1):
             Tl = args.NUM_CHUNKS[i] * args.T
             self.out[i] = (torch.zeros((K, Tl, 5), device=self.device), torch.zeros((K, 3, 6 + nc), device=self.device),
                            torch.zeros((K, 1), device=self.device), torch.zeros((1,), device=self.device),
                            torch.zeros((self.batch, 2), dtype=torch.int32, device=self.device))
+            if args.temporal_mode != "predict" and (i - 1) in args.NUM_CHUNKS and args.NUM_CHUNKS[i] == args.NUM_CHUNKS[i - 1] + 2:
+                self._ungrown[i] = torch.zeros((K, Tl - 2 * args.T, 5), device=self.device)
 
     @staticmethod
     def _key(t):
@@ -361,19 +378,32 @@ class DeviceSelector:
         t_start = int((max_chunks - chunks) / 2) * T
         mid = int(max_chunks / 2)
         grow = (step - 1) in a.NUM_CHUNKS and a.NUM_CHUNKS[step] == a.NUM_CHUNKS[step - 1] + 2
-        grows_next = step < a.max_iter and a.NUM_CHUNKS[step + 1] == a.NUM_CHUNKS[step] + 2
+        predict = a.temporal_mode == "predict"
+        grows_next = predict and step < a.max_iter and a.NUM_CHUNKS[step + 1] == a.NUM_CHUNKS[step] + 2      # (neighbour targets: "predict" only)
         before, after = (int((t_start - T) / T), int((t_start + chunks * T) / T)) if grows_next else (-1, -1)
         clip_of, most = self._clip_layout(clip_start)
         if step == 1:
             cand, first, last, score, iou = init_flat, None, None, None, None
         else:
-            score, cand, first, last, iou = ops.select_prepare(history["pred_prob"], history["pred_loc"], history["pred_first_loc"] if grow else None,
-                                                               history["pred_last_loc"] if grow else None, clip_of, self._gt_mid_boxes(gt, mid),
+            nbr = grow and predict                               # (the other modes' histories carry None for the neighbours)
+            score, cand, first, last, iou = ops.select_prepare(history["pred_prob"], history["pred_loc"], history["pred_first_loc"] if nbr else None,
+                                                               history["pred_last_loc"] if nbr else None, clip_of, self._gt_mid_boxes(gt, mid),
                                                                gt_count, float(a.image_size[0]), float(a.image_size[1]))
         n_max = int(max_tubes) if max_tubes is not None else most
+        out = self.out[step]
+        if grow and not predict:
+            # the selected rows grow from their own boxes: step_select_train writes them un-grown (its pad: the middle frames of the step's),
+            # step_tube_grow makes the step's sel of them -- the padded slots get the step's pad, the index column is rewritten for Tl frames
+            Tc = cand.shape[1]
+            mid_pad = pad_tubes[:, T:T + Tc].contiguous()
+            ops.select_train(cand, None, None, score, iou, clip_start, n_max, gt, gt_count, mid_pad, self.rng, mid, before, after, a.topk,
+                             a.cls_thresh[step - 1], a.reg_thresh[step - 1], a.max_pos_num, a.neg_ratio, a.selection_sampling, self.budget,
+                             out=(self._ungrown[step],) + tuple(out[1:]), clip_count=clip_count)
+            ops.tube_grow(self._ungrown[step], T, a.temporal_mode, self._slot_clip, mask=out[2], pad_tubes=pad_tubes, out=out[0])
+            return out
         return ops.select_train(cand, first, last, score, iou, clip_start, n_max, gt, gt_count, pad_tubes, self.rng, mid, before, after, a.topk,
                                 a.cls_thresh[step - 1], a.reg_thresh[step - 1], a.max_pos_num, a.neg_ratio, a.selection_sampling, self.budget,
-                                out=self.out[step], clip_count=clip_count)
+                                out=out, clip_count=clip_count)
 
 
 # ---- classification pre-training (train_cls.py: stage 1 of the reference's two-stage recipe) --------------------------------------------

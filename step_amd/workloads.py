@@ -418,11 +418,17 @@ class C4SelectTrainStep(C4TrainStep):
     augment= the front's planner transforms them with the frames (apply(tubes=...): the step-1 candidates and their count are written by the
     iteration itself); without, they are scaled once.  The no-grad inference runs over B * K slots with the counts, the selector gets
     clip_count.  set_proposals(list of [n_i,T,4] percent arrays) feeds the next iteration's proposals into the static buffers: no
-    recapture.  The ragged step() runs the host selection on the real ragged lists."""
+    recapture.  The ragged step() runs the host selection on the real ragged lists.
+
+    temporal_mode="predict" | "extrapolate" | "mean" (config.py:92; every shipped script passes "predict"): how the tubes grow from one chunk
+    to three, in the no-grad inference and in the selection alike.  Outside "predict" nobody reads the heads' neighbour regressions for the
+    next step and no neighbour targets are written; both selections handle all three modes, so selection="device" stays ONE graph."""
 
     def __init__(self, dev, batch=1, seed=123, dtype=torch.float32, tubes_per_clip=34, capturable=False, force_exchange=False, budget=None,
                  optimizer="adam", dropout=0.0, rng_seed=0, selection="host", grad_wire="fp32", wire_feedback=True, max_grad_norm=None,
-                 lr_schedule=None, augment=None, src_size=(256, 340), proposals=None):
+                 lr_schedule=None, augment=None, src_size=(256, 340), proposals=None, temporal_mode="predict"):
+        if temporal_mode not in DeviceSelector.ALL_MODES:
+            raise ValueError("C4SelectTrainStep: temporal_mode is one of %r, got %r" % (DeviceSelector.ALL_MODES, temporal_mode))
         if selection not in ("host", "device"):
             raise ValueError("C4SelectTrainStep: selection is 'host' or 'device', got %r" % (selection,))
         if proposals is not None and (selection != "device" or int(proposals) < 1):
@@ -432,6 +438,7 @@ class C4SelectTrainStep(C4TrainStep):
         super().__init__(dev, batch=batch, tubes_per_clip=5, seed=seed, max_iter=3, dtype=dtype, capturable=capturable, force_exchange=force_exchange,
                          optimizer=optimizer, dropout=dropout, rng_seed=rng_seed, grad_wire=grad_wire, wire_feedback=wire_feedback,
                          max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
+        self.args.temporal_mode = temporal_mode                  # (read by the no-grad inference and by both selections, nowhere in the networks)
         rs = np.random.RandomState(seed)
         anchors = (generate_anchors()[:tubes_per_clip] * 400.0).astype(np.float32)
         self.init_tubes = [np.tile(anchors[:, None, :], (1, 3, 1)) for _ in range(batch)]
@@ -497,7 +504,8 @@ class C4SelectTrainStep(C4TrainStep):
                     host.append(torch.zeros(shape).pin_memory())
         if selection == "device":
             # everything the selection reads is resident: ground truths, the initial tubes (step 1's candidates), the padded slots' box
-            self.selector = DeviceSelector(a, batch, self.budget, dev, self.rng, dynamic_gt=augment is not None)
+            self.selector = DeviceSelector(a, batch, self.budget, dev, self.rng, dynamic_gt=augment is not None,
+                                           temporal_modes=DeviceSelector.ALL_MODES)
             self.d_gt = torch.from_numpy(np.stack(self.gt)).to(dev)
             self.d_gt_count = torch.full((batch,), self.gt[0].shape[0], dtype=torch.int32, device=dev)
             self.d_init = self.flat0[:, :, 1:].float().contiguous()

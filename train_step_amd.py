@@ -114,6 +114,9 @@ def main():
                     help="--select-device only: the initial tubes are detector proposals, a changing number per clip in K padded slots with a "
                          "device-side count (synthetic here; a clip without any falls back to the anchors), instead of the anchor grid; with "
                          "--augment-device the planner transforms them with the frames")
+    ap.add_argument("--temporal-mode", default="predict", choices=["predict", "extrapolate", "mean"],
+                    help="--select / --select-device: how the tubes grow from one chunk to three (config.py:92 --temporal_mode): the head's neighbour "
+                         "regressions, linear extrapolation of the tube's own boxes, or its mean box (step_tube_update_mode, step_tube_grow)")
     ap.add_argument("--src-size", default="256x340", help="--augment / --augment-device: HxW of the decoded source frames")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
@@ -133,6 +136,8 @@ def main():
                          "writes), without --cls and --augment")
     if a.proposals and (a.proposals < 0 or not a.select_device or a.cls):
         raise SystemExit("train_step_amd.py: --proposals K needs --select-device (the host selection keeps its ragged form), without --cls, and K >= 1")
+    if a.temporal_mode != "predict" and not a.select:
+        raise SystemExit("train_step_amd.py: --temporal-mode needs --select or --select-device (only the selecting iteration grows tubes from predictions)")
     if a.scheduler and a.lr_decay_every:
         raise SystemExit("train_step_amd.py: --scheduler and --lr-decay-every both write the learning rate; pick one")
     if a.clip_grad_norm is not None and not a.clip_grad_norm > 0:
@@ -186,7 +191,7 @@ def main():
             extra.update(proposals=a.proposals)
         w = workloads.C4SelectTrainStep(dev, batch=len(mine), seed=123 + rank, dtype=tdt, capturable=capturable, optimizer=a.optimizer,
                                         dropout=a.dropout, rng_seed=a.rng_seed + rank, selection="device" if a.select_device else "host",
-                                        grad_wire=a.grad_wire, wire_feedback=not a.no_wire_feedback, **extra)
+                                        grad_wire=a.grad_wire, wire_feedback=not a.no_wire_feedback, temporal_mode=a.temporal_mode, **extra)
     else:
         w = workloads.C4TrainStep(dev, batch=len(mine), tubes_per_clip=a.tubes, seed=123 + rank, dtype=tdt, capturable=capturable,
                                   optimizer=a.optimizer, dropout=a.dropout, rng_seed=a.rng_seed + rank, grad_wire=a.grad_wire,
@@ -308,6 +313,7 @@ def main():
                           **({"gt_kept": int(w.d_gt_count.sum().item())} if a.augment_device else {}),
                           **({"proposals": a.proposals, "proposals_real": int(w.d_count.sum().item())} if a.proposals else {}), "dtype": a.dtype, "final_loss": round(float(w.loss), 6), "optimizer": a.optimizer, "opt_steps": w.opt.step_count,
                           "dropout": a.dropout, "rng_offset": w.rng.offset(), **({"selection": w.selection_ran} if (a.select or a.cls) else {}),
+                          **({"temporal_mode": a.temporal_mode} if a.select else {}),
                           **({"workload": "cls"} if a.cls else {}),
                           **({"clip_grad_norm": a.clip_grad_norm, "grad_norm": round(float(w.opt.grad_norm[0]), 6)} if a.clip_grad_norm is not None else {}),
                           **({"scheduler": a.scheduler, "last_epoch": w.sched.last_epoch, "lr": w.sched.get_last_lr()[0]} if w.sched is not None else {}),
