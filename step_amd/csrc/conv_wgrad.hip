@@ -1,5 +1,8 @@
-// step_amd/csrc/conv_wgrad.hip -- weight gradients (training): conv_wgrad_kernel, stem_wgrad_kernel and their C entry
-// points step_conv_wgrad / step_stem_wgrad.
+// step_amd/csrc/conv_wgrad.hip -- weight gradients (training).
+//   kernels: conv_wgrad_kernel (per tap), conv_wgrad16_lds12{,_wide}_kernel / conv_wgrad16_lds2_kernel (LDS-tiled 16-bit GEMM), conv_wgrad16_pws_kernel
+//            (pointwise pixel stream), the fixed-order sums of their partial tiles, stem_wgrad_kernel / stem_wgrad16_kernel and their sums.
+//   host:    wgrad_plan decides ONCE per call which form runs, its grids, its workspace and the pending sum; step_conv_wgrad{,_ws,16,16_ws,
+//            _partial}, the workspace / kernel-name queries and step_wgrad_reduce_group only read that plan; step_stem_wgrad{,_ws,16}.
 #include "conv_common.h"
 
 namespace step {
@@ -230,8 +233,8 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restr
 // and reads the MFMA operands with ds_read_b64_tr_b16: the hardware transpose hands every lane the 8 consecutive pixels (k)
 // of one channel that v_mfma_f32_16x16x32 wants, and a tap shift is just another pixel address -- no transposed or shifted
 // copies (common.h: lds_tr8).  Six waves = 3 filter rows (kh) x 2 halves of the 64 input channels; each accumulates the three
-// kw taps of its row: 3 x (64 co x 32 ci) = 24 MFMAs per 32-pixel step from 20 transpose reads (NW = 6; the product form of the 3x3
-// windows since round 4 is NW = 12: the co tile split over a second pair of waves, conv_wgrad16_lds12_kernel below).  A workgroup walks several
+// kw taps of its row: 3 x (64 co x 32 ci) = 24 MFMAs per 32-pixel step from 20 transpose reads (the form of rounds 2-3; since round 4
+// the 3x3 windows run with NW = 12: the co tile split over a second pair of waves, conv_wgrad16_lds12_kernel below).  A workgroup walks several
 // (plane, row chunk) units with its accumulators in registers and ends in one pass of fp32 atomics.
 constexpr int WG16_P = 224;              // output pixels per chunk (7 k32 steps)
 constexpr int WG16_XP = 320;             // halo pixels per chunk
@@ -261,12 +264,12 @@ struct Wgrad16Params {
 
 // KW = 1 (pointwise convs / Linear layers): no halo; the unit is a chunk of 128 consecutive pixels of the flattened N*D*H*W
 // axis, the six waves take six 32-channel blocks of a 192-channel ci tile (X image pitch 400 B) and accumulate one tap.
-template <typename T, int KW, bool PF, int XPMAX = WG16_XP, int NW = 6, bool DB = false>
+template <typename T, int KW, bool PF, int XPMAX = WG16_XP, int NW = 6>
 __device__ __forceinline__ void conv_wgrad16_lds_body(const Wgrad16Params& p) {
     static_assert(sizeof(T) == 2, "16-bit storage");
     static_assert(KW == 3 || KW == 1, "3x3 windows or pointwise");
     constexpr bool PW = KW == 1;
-    static_assert(NW == 6 || (NW == 12 && KW == 3), "six waves, or twelve for the 3x3 windows");
+    static_assert((NW == 6 && KW == 1 && !PF) || (NW == 12 && KW == 3 && PF), "six waves for the pointwise form, twelve (prefetching) for the 3x3 windows");
     constexpr int THREADS = NW * 64;
     constexpr int MA = NW == 12 ? 2 : 4;                      // 16-channel blocks of the co tile per wave (twelve waves: two halves of the 64)
     constexpr int PITCH = WG16_PITCH;
@@ -274,9 +277,7 @@ __device__ __forceinline__ void conv_wgrad16_lds_body(const Wgrad16Params& p) {
     constexpr int CIT = PW ? 192 : 64;                        // input channels per workgroup
     constexpr int XCV = CIT / 8;                              // 16-byte vectors per X pixel
     constexpr int LDSB = PW ? WG16_PW_P * (PITCH + WG16_PW_XPITCH) : (WG16_P + XPMAX) * PITCH;    // 72 KiB (two workgroups per CU) | 85 / 100 KiB
-    // DB: two images -- unit u + 1 is written while slower waves still multiply unit u, and one barrier per unit instead of two
-    static_assert(!DB || PF, "the double-buffered form prefetches across units");     // (2 x 87 KB no longer fits the LDS at the 160-byte pitch: experiment builds only, with a smaller WG16_P)
-    __shared__ __attribute__((aligned(16))) unsigned char lds[DB ? 2 * LDSB : LDSB];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[LDSB];
     unsigned char* dyI = lds;
     unsigned char* xI = lds + (PW ? WG16_PW_P : WG16_P) * PITCH;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -346,17 +347,15 @@ __device__ __forceinline__ void conv_wgrad16_lds_body(const Wgrad16Params& p) {
         q.P = q.R * p.W; q.Ppad = (q.P + 31) & ~31; q.XP = (q.R + 2) * W2;
         return q;
     };
-    // (i0, i1: the slice of the thread's NV vectors this call moves -- the form without cross-unit prefetch stages a unit in two halves,
-    // so that only half the staging registers are live at a time)
     // (staging order: the 16 lanes of a ds_write_b128 pass write rows r and r + 1, which share eight banks at this pitch; pairing rows r and
     //  r + 4 instead removes those conflicts (SQ_LDS_BANK_CONFLICT 40 -> 22-32 % of the LDS cycles with it, 40 -> ~35 % without) but measured
     //  SLOWER -- 5c_b1b 0.385 -> 0.416 ms, the heads' 1x3x3 convs 0.197 -> 0.213 -- and is not kept: the kernel is not bound by its LDS cycles)
     auto srow = [](int u) { return u >> 3; };
-    auto prefetch = [&](const Unit& q, int i0, int i1) {
+    auto prefetch = [&](const Unit& q) {
         const size_t gp0 = PW ? (size_t)q.k0 : (((size_t)q.n * p.D + q.d) * p.H + q.r0) * p.W;
         const size_t xp0 = ((size_t)q.n * p.D + q.id) * p.H;
 #pragma unroll
-        for (int i = i0; i < i1; ++i) {
+        for (int i = 0; i < NV; ++i) {
             const int v = tid + i * THREADS;
             u32x4 val = {0u, 0u, 0u, 0u};
             if (v < q.Ppad * 8) {                            // dY [Ppad][64 co]: zero tail, zero past Cout
@@ -377,9 +376,9 @@ __device__ __forceinline__ void conv_wgrad16_lds_body(const Wgrad16Params& p) {
             stg[i] = val;
         }
     };
-    auto to_lds = [&](const Unit& q, int i0, int i1) {
+    auto to_lds = [&](const Unit& q) {
 #pragma unroll
-        for (int i = i0; i < i1; ++i) {
+        for (int i = 0; i < NV; ++i) {
             const int v = tid + i * THREADS;
             if (v < q.Ppad * 8) *(u32x4*)(dyI + srow(v) * PITCH + (v & 7) * 16) = stg[i];
             else if (PW) {
@@ -392,29 +391,19 @@ __device__ __forceinline__ void conv_wgrad16_lds_body(const Wgrad16Params& p) {
         }
     };
     Unit cur = unit_of(u_beg < u_end ? u_beg : 0);
-    if (PF && u_beg < u_end && cur.live) prefetch(cur, 0, NV);
+    if (PF && u_beg < u_end && cur.live) prefetch(cur);
     for (long long u = u_beg; u < u_end; ++u) {
         if (!PF) {                                           // no cross-unit prefetch: the staging registers die before the matrix phase (fewer
             cur = unit_of(u);                                // VGPRs -> two resident workgroups per CU, whose staging and matrix phases interleave)
-            if (cur.live) prefetch(cur, 0, KW == 3 ? NV / 2 : NV);
+            if (cur.live) prefetch(cur);
         }
-        if (DB) {                                            // this unit's images: the last reader of them (unit u - 2) is a barrier behind
-            dyI = lds + (size_t)((u - u_beg) & 1) * LDSB;
-            xI = dyI + (PW ? WG16_PW_P : WG16_P) * PITCH;
-        } else
-            __syncthreads();                                 // every wave is done with the previous unit's images
-        if (!PF && KW == 3) {
-            if (cur.live) {
-                to_lds(cur, 0, NV / 2);
-                prefetch(cur, NV / 2, NV);
-                to_lds(cur, NV / 2, NV);
-            }
-        } else if (cur.live) to_lds(cur, 0, NV);
+        __syncthreads();                                     // every wave is done with the previous unit's images
+        if (cur.live) to_lds(cur);
         __syncthreads();
         const Unit done = cur;
         if (PF && u + 1 < u_end) {
             cur = unit_of(u + 1);
-            if (cur.live) prefetch(cur, 0, NV);
+            if (cur.live) prefetch(cur);
         }
         if (!done.live) continue;                            // (workgroup-uniform)
         const int P = done.P, Ppad = done.Ppad;
@@ -471,27 +460,19 @@ __device__ __forceinline__ void conv_wgrad16_lds_body(const Wgrad16Params& p) {
     }
 }
 
-template <typename T, int KW>
-__global__ __launch_bounds__(384) void conv_wgrad16_lds_kernel(Wgrad16Params p) { conv_wgrad16_lds_body<T, KW, true>(p); }
 // twelve waves (3 filter rows x 2 halves of the ci tile x 2 halves of the co tile, 12 accumulator tiles each): three waves per SIMD
 // instead of 1.5, every SIMD equally loaded
 // (measured, bf16, 8 AVA clips, same process: 3c_b1b 0.883 -> 0.669 ms = 714 TFLOP/s, 3b_b1b 0.582 -> 0.454, 4f_b1b 0.335 -> 0.270, 5c on 1080
 // 7x7 maps 0.468 -> 0.387, the heads' 1x3x3 convs 0.262 -> 0.196; 142 VGPRs, no spill: the product form of the 3x3 windows.  The six-wave
-// kernels remain for experiment builds, -DWG16_NW6.)
+// 3x3 kernels, a double-buffered LDS image and a fixed workgroup target were experiment builds of rounds 3-4, measured and removed.)
 template <typename T, int KW>
-#ifdef WG16_DB
-__global__ __launch_bounds__(768) STEP_WAVES_PER_SIMD(3) void conv_wgrad16_lds12_kernel(Wgrad16Params p) { conv_wgrad16_lds_body<T, KW, true, WG16_XP, 12, true>(p); }
-#else
 __global__ __launch_bounds__(768) STEP_WAVES_PER_SIMD(3) void conv_wgrad16_lds12_kernel(Wgrad16Params p) { conv_wgrad16_lds_body<T, KW, true, WG16_XP, 12>(p); }
-#endif
 template <typename T, int KW>
 __global__ __launch_bounds__(768) STEP_WAVES_PER_SIMD(3) void conv_wgrad16_lds12_wide_kernel(Wgrad16Params p) { conv_wgrad16_lds_body<T, KW, true, WG16_XP_WIDE, 12>(p); }
-template <typename T, int KW>
-__global__ __launch_bounds__(384) void conv_wgrad16_lds_wide_kernel(Wgrad16Params p) { conv_wgrad16_lds_body<T, KW, true, WG16_XP_WIDE>(p); }
 // The same without the cross-unit register prefetch, held to 168 VGPRs: TWO workgroups per CU, whose staging and matrix phases interleave
 // (and 12 waves spread evenly over the 4 SIMDs instead of 6).  Measured (tools/wgrad_bench.py, bf16, 8 AVA clips, same process):
 // pointwise 480 -> 304 on 25x25x9x8: 137 -> 96 us, 832 -> 624 on 1080 7x7 maps: 914 -> 572 us (140 VGPRs, no spill) -- the product
-// form for KW = 1; the 3x3 windows spill at 168 VGPRs and measured 15-25 % SLOWER than the prefetching form even with the staging
+// form for KW = 1; the 3x3 windows spilled at 168 VGPRs and measured 15-25 % SLOWER than the prefetching form even with the staging
 // split in two halves (profiles/r04_wgrad16_variants.txt): they keep one prefetching workgroup per CU.
 template <typename T, int KW>
 __global__ __launch_bounds__(384) STEP_WAVES_PER_SIMD(3) void conv_wgrad16_lds2_kernel(Wgrad16Params p) { conv_wgrad16_lds_body<T, KW, false>(p); }
@@ -679,9 +660,9 @@ __global__ void wgradpws_reduce_kernel(const float* __restrict__ ws, float* __re
 // the one-clip step 13.4 -> 13.7 ms.  The scattered stores are merged by the L2; a block-per-workgroup walk has too few workgroups.)
 __device__ __forceinline__ void wgrad16_reduce_body(const float* __restrict__ ws, float* __restrict__ dw, int gx, int gy, int cot, int cit, int Cout,
                                                     int Cin, int kd, int accumulate, int pw, unsigned bx, unsigned nbx) {
-    // pw: 0 = 3x3 windows, six waves x 24 tiles | 1 = pointwise, six waves x 8 tiles | 2 = 3x3 windows, twelve waves x 12 tiles
-    const int tpw = pw == 1 ? 8 : (pw == 2 ? 12 : 24);                  // accumulator tiles per wave
-    const int nw = pw == 2 ? 12 : 6;
+    // pw: 1 = pointwise, six waves x 8 tiles | 2 = 3x3 windows, twelve waves x 12 tiles
+    const int tpw = pw == 1 ? 8 : 12;                                   // accumulator tiles per wave
+    const int nw = pw == 1 ? 6 : 12;
     const long long per_x = (long long)gy * nw * tpw * 64;             // f32x4 groups of one pixel-axis workgroup
     const int ntaps = pw == 1 ? 1 : kd * 9;
     // 256 threads = 64 consecutive 16-byte groups x 4 subgroups of the pixel-axis workgroups (subgroup w adds x = w, w + 4, ... in ascending
@@ -723,8 +704,8 @@ __device__ __forceinline__ void wgrad16_reduce_body(const float* __restrict__ ws
             const int y = (int)t;
             const int nb = tile & 1;
             const int khw = pw == 1 ? 0 : wave % 3, wrest = pw == 1 ? wave : wave / 3;
-            const int cb = pw == 2 ? (wrest & 1) : wrest;
-            const int ma = pw == 2 ? (wrest >> 1) * 2 + ((tile >> 1) & 1) : (tile >> 1) & 3, s = pw == 2 ? tile >> 2 : tile >> 3;
+            const int cb = pw == 1 ? wrest : (wrest & 1);
+            const int ma = pw == 1 ? (tile >> 1) & 3 : (wrest >> 1) * 2 + ((tile >> 1) & 1), s = pw == 1 ? 0 : tile >> 2;
             int yy = y;
             const int cit_i = yy % cit; yy /= cit;
             const int cot_i = yy % cot;
@@ -743,6 +724,7 @@ __device__ __forceinline__ void wgrad16_reduce_body(const float* __restrict__ ws
         __syncthreads();
     }
 }
+
 __global__ void wgrad16_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int gx, int gy, int cot, int cit, int Cout, int Cin,
                                       int kd, int accumulate, int pw) {
     wgrad16_reduce_body(ws, dw, gx, gy, cot, cit, Cout, Cin, kd, accumulate, pw, blockIdx.x, gridDim.x);
@@ -1117,9 +1099,9 @@ static int wgrad_min_pixels(int form) {
 }
 
 // launch plan of the LDS-tiled 16-bit form; ok = false: the shape is left to the per-tap forms
-struct Wg16Plan { bool ok = false, pw = false, wide = false, nw12 = false; int rows, cpp, upj, cot, cit; long long units, gx, gy; };
+struct Wg16Plan { bool ok = false, pw = false, wide = false; int rows = 0, cpp = 0, upj = 0, cot = 0, cit = 0; long long units = 0, gx = 0, gy = 0; };
 static Wg16Plan wgrad16_plan(const step_conv_desc* d) {
-    Wg16Plan pl; pl.ok = false; pl.pw = false; pl.wide = false; pl.rows = pl.cpp = pl.upj = pl.cot = pl.cit = 0; pl.units = pl.gx = pl.gy = 0;
+    Wg16Plan pl;
     if (!d || (d->dtype != STEP_BF16 && d->dtype != STEP_F16)) return pl;
     const bool pw = d->kd == 1 && d->kh == 1 && d->kw == 1;
     pl.pw = pw;
@@ -1148,9 +1130,6 @@ static Wg16Plan wgrad16_plan(const step_conv_desc* d) {
         // the wide-halo instantiation only where it cuts the chunks per plane (measured, bf16, 8 clips: conv3d_2c on 100x100 2.61 -> 1.80 ms,
         // on 56x56 0.53 -> 0.48 ms; the 50- and 25-wide layers keep the same rows and would lose 5 % to its longer staging loops)
         if (Rw > 0 && (R <= 0 || ceil_div(d->H, Rw) < ceil_div(d->H, R))) { R = Rw; pl.wide = true; }
-#ifndef WG16_NW6
-        pl.nw12 = true;
-#endif
         if (R <= 0) return pl;
         pl.cot = ceil_div(d->Cout, 64); pl.cit = ceil_div(d->Cin, 64);
         pl.cpp = ceil_div(d->H, R);
@@ -1167,17 +1146,6 @@ static Wg16Plan wgrad16_plan(const step_conv_desc* d) {
 #ifndef WG16_WGCOST
 #define WG16_WGCOST 0.012       /* a workgroup's partial tiles (written here, read back by the sum), in units of a unit's time */
 #endif
-#ifdef WG16_TOTAL           /* experiment builds: a fixed target, as rounds 2-3 had (512) */
-    {
-        long long want = WG16_TOTAL / (pl.gy > 0 ? pl.gy : 1);
-        if (want < 1) want = 1;
-        long long upj = ceil_div64(pl.units, want);
-        if (upj < 1) upj = 1;
-        pl.upj = (int)(upj > 0x3fffffff ? 0x3fffffff : upj);
-        pl.gx = ceil_div64(pl.units, pl.upj);
-        if (pl.gx >= 8) pl.gx = (pl.gx + 7) / 8 * 8;
-    }
-#else
     {
         const long long slots = 256LL * (pw ? 2 : 1);
         double best = -1.0;
@@ -1194,23 +1162,20 @@ static Wg16Plan wgrad16_plan(const step_conv_desc* d) {
         pl.upj = (int)(best_upj > 0x3fffffff ? 0x3fffffff : best_upj);
         pl.gx = best_gx;
     }
-#endif
     pl.ok = pl.gy <= 65535 && pl.gx <= 0x7fffffffLL;
     return pl;
 }
 
 // job split of the per-tap kernel (conv_wgrad_kernel): pointwise layers cut the flattened pixel axis into `chunk`-pixel jobs (+ one
-// ragged tail job), windows cut the (n, d, h) rows; gy = (tap, co tile, ci tile) workgroup rows; per_tile = floats of a job's tile
-struct WgJobs { bool pw; int chunk, tail, rows; long long full, jobs, gy; int cot, cit, nbw; size_t per_tile; };
+// ragged tail job), windows cut the (n, d, h) rows; gy = (tap, co tile, ci tile) workgroup rows
+struct WgJobs { bool pw = false; int chunk = 0, tail = 0, rows = 0; long long full = 0, jobs = 0, gy = 0; int cot = 0, cit = 0, nbw = 2; };
 static WgJobs wgrad_jobs(const step_conv_desc* d, int form) {
     WgJobs j;
     const int ntaps = d->kd * d->kh * d->kw;
     const bool narrow = d->Cin <= 32;
     j.nbw = narrow ? 1 : 2;
     j.cot = ceil_div(d->Cout, 64); j.cit = ceil_div(d->Cin, narrow ? 32 : 64);
-    j.per_tile = (size_t)2 * j.nbw * 16 * 64;
     j.pw = ntaps == 1;
-    j.chunk = j.tail = j.rows = 0; j.full = 0;
     if (j.pw) {
         // pointwise: no neighbourhood, so the pixel axis is cut into chunks ("rows" of one long plane list); ~6000 wavefront jobs per
         // launch (see below), a multiple of the 16-pixel MFMA step
@@ -1249,10 +1214,6 @@ static WgJobs wgrad_jobs(const step_conv_desc* d, int form) {
 }
 // one partial tile per WORKGROUP (four jobs): pointwise layers launch their full chunks and the ragged tail separately
 static long long wgrad_ws_blocks(const WgJobs& j) { return j.pw ? ceil_div64(j.full, 4) + (j.tail ? 1 : 0) : ceil_div64(j.jobs, 4); }
-static size_t wgrad_jobs_ws_bytes(const WgJobs& j) { return (size_t)wgrad_ws_blocks(j) * (size_t)j.gy * j.per_tile * sizeof(float); }
-
-// defer != NULL: the fixed-order sum of the partial tiles is NOT launched; *defer describes it (step_wgrad_reduce_group runs several
-// layers' sums as one launch).  kind 0: nothing is pending (the atomics forms, an empty batch).
 
 // the pixel-stream form of the pointwise weight gradient (conv_wgrad16_pws_kernel): tiles, slices
 struct WgPwsPlan { bool ok = false; int cot = 0, cit = 0, co_t = 0, ci_t = 0; long long gx = 0, gy = 0, ppj = 0; };
@@ -1294,230 +1255,266 @@ static WgPwsPlan wgradpws_plan(const step_conv_desc* d) {
     return pl;
 }
 
-static void reduce_item_none(step_wgrad_reduce_item* it) { if (it) { *it = step_wgrad_reduce_item(); } }
+// The pending sum of a form's partial results is a step_wgrad_reduce_item.  Floats of ONE partial result along the pixel axis -- the only
+// place a form's size is written: the workspace the form needs and the grid of its sum both come from here.
+static long long wgrad_item_partial_floats(const step_wgrad_reduce_item& it) {
+    if (it.kind == 1) return (long long)it.gy * (2 * it.nbw * 16 * 64);       // per-tap kernel: gy workgroup rows x 2 x nbw tiles x 16 registers x 64 lanes
+    if (it.kind == 2) return (long long)it.gy * (it.pw == 1 ? 6 * 8 : 12 * 12) * 64 * 4;    // LDS-tiled: pointwise six waves x 8 tiles | 3x3 twelve x 12
+    return it.kind == 3 ? (long long)it.Cout * it.Cin : 0;                    // pixel stream: a dense [Cout, Cin] image
+}
+static size_t wgrad_item_ws_bytes(const step_wgrad_reduce_item& it) { return (size_t)it.jobs * (size_t)wgrad_item_partial_floats(it) * sizeof(float); }
+// threads the sum wants (its grid is flat_grid(work, 256); the *_reduce_body functions stride over whatever grid they get)
+static long long wgrad_item_work(const step_wgrad_reduce_item& it) {
+    const long long f = wgrad_item_partial_floats(it);
+    if (it.kind == 1) return f * 4;                            // a thread per float x 4 subgroups of the jobs
+    if (it.kind == 2) return f;                                // a thread per 16-byte group x 4 subgroups of the workgroups
+    return (f / 4 + 15) / 16 * 256;                            // kind 3: workgroups of 16 vectors x 16 subgroups of the slices
+}
+// the ONE place a single item becomes a launch.  (As a group of one it measured ~1 us slower per call than these stand-alone kernels on the
+// small layers -- profiles/wgrad_plan_ab.txt -- so they stay.)
+static int wgrad_item_launch(const step_wgrad_reduce_item& it, step_stream_t stream) {
+    const dim3 grid(flat_grid(wgrad_item_work(it), 256));
+    switch (it.kind) {
+        case 1: STEP_LAUNCH(wgrad_reduce_kernel, grid, dim3(256), stream, it.ws, it.dw, it.jobs, it.gy, 2, it.nbw, it.cot, it.cit, it.Cout, it.Cin, it.taps, it.accumulate); break;
+        case 2: STEP_LAUNCH(wgrad16_reduce_kernel, grid, dim3(256), stream, it.ws, it.dw, (int)it.jobs, it.gy, it.cot, it.cit, it.Cout, it.Cin, it.taps, it.accumulate, it.pw); break;
+        case 3: STEP_LAUNCH(wgradpws_reduce_kernel, grid, dim3(256), stream, it.ws, it.dw, it.jobs, (long long)it.Cout * it.Cin / 4, it.accumulate); break;
+    }
+    return STEP_LAUNCH_CHECK();
+}
+// m members as one launch, one per blockIdx.y (the members past m are never read)
+static int wgrad_reduce_group_launch(const WgradReduceGroup& g, int m, long long most, step_stream_t stream) {
+    STEP_LAUNCH(wgrad_reduce_group_kernel, dim3(flat_grid(most, 256), (unsigned)m), dim3(256), stream, g);
+    return STEP_LAUNCH_CHECK();
+}
 
+// The plan of one weight gradient: everything a call decides, decided once: wgrad_plan is the only caller of wgradpws_plan / wgrad16_plan / wgrad_jobs, and the launch
+// (conv_wgrad_impl), the workspace queries and the kernel-name query only read what it returns.
+enum { WGF_TAP_ATOMICS = 0, WGF_TAP_WS, WGF_LDS, WGF_PWS };
+struct WgradPlan {
+    int form = WGF_TAP_ATOMICS;   // per-tap kernel ending in atomics | per-tap kernel with partial tiles | LDS-tiled GEMM | pointwise pixel stream
+    bool w16 = false;
+    const char* kernel = "conv_wgrad_kernel";
+    WgJobs tap; Wg16Plan lds; WgPwsPlan pws;                   // the split of the form that runs (the others stay empty)
+    dim3 grid, tail = dim3(0);    // tail: the second launch of the pointwise per-tap form (its ragged last chunk); x == 0: no such launch
+    int status = STEP_OK;         // a limit of the per-tap forms' launches, returned where the launch would be
+    size_t need = 0;              // bytes of workspace the form's partial results take
+    bool use_ws = false;          // the workspace offered is used (else the form ends in fp32 atomics on dw)
+    step_wgrad_reduce_item item = step_wgrad_reduce_item();     // the pending sum; kind == 0: none (atomics)
+};
+// aligned: x and dy are 16-byte aligned (the LDS-tiled and pixel-stream forms load 16-byte vectors); ideal_ws: plan as if a workspace
+// of the needed size were offered (the queries); else (ws, ws_bytes) is what the caller offers (NULL / 0: atomics everywhere).
+static WgradPlan wgrad_plan(const step_conv_desc* d, bool w16, bool aligned, float* dw, int accumulate, void* ws, size_t ws_bytes, bool ideal_ws) {
+    WgradPlan pl;
+    pl.w16 = w16;
+    if (!d) return pl;
+    pl.tap.nbw = d->Cin <= 32 ? 1 : 2;
+    if (w16 && d->dtype != STEP_BF16 && d->dtype != STEP_F16) return pl;
+    const bool dims = d->N > 0 && d->D > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->kd > 0 && d->kh > 0 && d->kw > 0;
+    bool fits = ideal_ws || (ws && ((uintptr_t)ws % 16) == 0);  // (long enough: below, once the form says how much it needs)
+    step_wgrad_reduce_item it = step_wgrad_reduce_item();
+    it.ws = (const float*)ws; it.dw = dw; it.Cout = d->Cout; it.Cin = d->Cin;
+    if (w16 && aligned && dims) pl.pws = wgradpws_plan(d);
+    if (w16 && aligned && dims && !pl.pws.ok) pl.lds = wgrad16_plan(d);
+    if (pl.pws.ok) {
+        pl.form = WGF_PWS;
+        pl.kernel = "conv_wgrad16_pws_kernel";
+        pl.grid = dim3((unsigned)pl.pws.gx, (unsigned)pl.pws.gy);
+        it.kind = 3; it.jobs = pl.pws.gx; it.taps = 1; it.accumulate = 1;              // (dw is cleared before the launch unless the caller accumulates)
+        fits = fits && ((uintptr_t)dw % 16) == 0;                                      // the sum of the images moves dw in 16-byte vectors
+    } else if (pl.lds.ok) {
+        pl.form = WGF_LDS;
+        pl.kernel = pl.lds.pw ? "conv_wgrad16_lds2_kernel" : (pl.lds.wide ? "conv_wgrad16_lds12_wide_kernel" : "conv_wgrad16_lds12_kernel");
+        pl.grid = dim3((unsigned)pl.lds.gx, (unsigned)pl.lds.gy);
+        it.kind = 2; it.jobs = pl.lds.gx; it.gy = (int)pl.lds.gy; it.cot = pl.lds.cot; it.cit = pl.lds.cit; it.taps = d->kd; it.accumulate = 1;
+        it.pw = pl.lds.pw ? 1 : 2;
+    } else if (dims) {
+        // the per-tap kernel with a workspace: partial tiles + a fixed-order sum write every element of dw themselves; its jobs are
+        // shorter than the atomics form's (wgrad_min_pixels)
+        pl.tap = wgrad_jobs(d, w16 ? WG_WS_16 : WG_WS_F32);
+        it.kind = 1; it.jobs = wgrad_ws_blocks(pl.tap); it.gy = (int)pl.tap.gy; it.nbw = pl.tap.nbw; it.cot = pl.tap.cot; it.cit = pl.tap.cit;
+        it.taps = d->kd * d->kh * d->kw; it.accumulate = accumulate; it.pw = pl.tap.pw ? 1 : 0;
+        fits = fits && pl.tap.jobs > 0;
+    } else
+        return pl;                                                                     // an empty batch, or a shape the entry points refuse
+    pl.need = wgrad_item_ws_bytes(it);
+    pl.use_ws = fits && (ideal_ws || ws_bytes >= pl.need);
+    if (pl.use_ws) pl.item = it;
+    if (pl.form != WGF_TAP_ATOMICS) return pl;
+    if (pl.use_ws) pl.form = WGF_TAP_WS;
+    else pl.tap = wgrad_jobs(d, WG_ATOMICS);                   // (a second split only where an offered workspace is turned down)
+    const WgJobs& j = pl.tap;
+    if (j.pw) {                                                // two launches: the full chunks, then the ragged tail
+        if ((long long)d->N * d->D * d->H * d->W > 0x7fffffffLL) pl.status = STEP_E_UNSUPPORTED;
+        pl.grid = dim3((unsigned)ceil_div64(j.full, 4), (unsigned)j.gy);
+        pl.tail = dim3(j.tail ? 1u : 0u, (unsigned)j.gy);
+    } else {
+        if (j.gy > 65535) pl.status = STEP_E_UNSUPPORTED;
+        pl.grid = dim3((unsigned)ceil_div64(j.jobs, 4), (unsigned)j.gy);
+    }
+    return pl;
+}
+
+extern "C++" template <typename T, bool W16>
+static void wgrad_tap_launch_t(const WgradParams& p, dim3 grid, step_stream_t stream) {
+    if (p.Cin <= 32) STEP_LAUNCH((conv_wgrad_kernel<T, 2, 1, W16>), grid, dim3(256), stream, p);
+    else STEP_LAUNCH((conv_wgrad_kernel<T, 2, 2, W16>), grid, dim3(256), stream, p);
+}
+// conv_wgrad_kernel<T, 2, NB, W16> for a filled WgradParams and a grid
+static int wgrad_tap_launch(int dtype, bool w16, const WgradParams& p, dim3 grid, step_stream_t stream) {
+    switch (dtype) {
+        case STEP_F32: wgrad_tap_launch_t<float, false>(p, grid, stream); break;
+        case STEP_BF16: if (w16) wgrad_tap_launch_t<bf16_t, true>(p, grid, stream); else wgrad_tap_launch_t<bf16_t, false>(p, grid, stream); break;
+        case STEP_F16: if (w16) wgrad_tap_launch_t<f16_t, true>(p, grid, stream); else wgrad_tap_launch_t<f16_t, false>(p, grid, stream); break;
+        default: return STEP_E_DTYPE;
+    }
+    return STEP_OK;
+}
+
+static int wgrad_tap_run(const step_conv_desc* d, const WgradPlan& pl, const void* x, const void* dy, float* dw, float* ws, step_stream_t stream) {
+    const WgJobs& j = pl.tap;
+    WgradParams p;
+    p.x = x; p.dy = dy; p.dw = dw; p.ws = ws;
+    p.N = d->N; p.D = d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.kd = d->kd; p.kh = d->kh; p.kw = d->kw;
+    p.x_cstride = d->x_cstride; p.x_coff = d->x_coff; p.dy_cstride = d->y_cstride; p.dy_coff = d->y_coff;
+    p.cot = j.cot; p.cit = j.cit;
+    if (!j.pw) {
+        // (a tap-row form -- a job owns a row of three kw taps and re-pairs ten loaded pixels in registers -- measured 1.3-2.6x SLOWER
+        // than this per-tap form: 424 VGPRs, one wave per SIMD; removed)
+        p.total_rows = (long long)d->N * d->D * d->H;
+        p.rows = j.rows;
+        p.jobs = j.jobs;
+        return wgrad_tap_launch(d->dtype, pl.w16, p, pl.grid, stream);
+    }
+    // pointwise: `jobs` chunks of W pixels from pixel pix0 on, as the rows of one long plane list
+    auto chunks = [&](long long jobs, int W, size_t pix0, dim3 grid) {
+        p.N = 1; p.D = (int)jobs; p.H = 1; p.W = W; p.jobs = jobs; p.rows = 1; p.total_rows = jobs;
+        p.x = (const char*)x + pix0 * d->x_cstride * (d->dtype == STEP_F32 ? 4 : 2);
+        p.dy = (const char*)dy + pix0 * d->y_cstride * (pl.w16 ? 2 : 4);
+        return wgrad_tap_launch(d->dtype, pl.w16, p, grid, stream);
+    };
+    int rc = STEP_OK;
+    if (pl.grid.x) rc = chunks(j.full, j.chunk, 0, pl.grid);
+    if (rc == STEP_OK && pl.tail.x) {
+        if (ws) p.ws = ws + (size_t)pl.grid.x * wgrad_item_partial_floats(pl.item);    // the tail job's tiles behind the full chunks' tiles
+        rc = chunks(1, j.tail, (size_t)j.full * j.chunk, pl.tail);
+    }
+    return rc;
+}
+
+// the LDS-tiled form (transpose reads): 3x3 windows or deep pointwise layers, channel counts in 16-byte vectors (wgrad16_plan)
+static void wgrad16_lds_run(const step_conv_desc* d, const WgradPlan& pl, const void* x, const void* dy, float* dw, float* ws, step_stream_t stream) {
+    const Wg16Plan& l = pl.lds;
+    Wgrad16Params q;
+    q.x = x; q.dy = dy; q.dw = dw; q.ws = ws;
+    q.N = d->N; q.D = d->D; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.Cout = d->Cout; q.kd = d->kd;
+    q.x_cstride = d->x_cstride; q.x_coff = d->x_coff; q.dy_cstride = d->y_cstride; q.dy_coff = d->y_coff;
+    q.cot = l.cot; q.cit = l.cit; q.cpp = l.cpp; q.rows = l.rows; q.units = l.units; q.upj = l.upj;
+    q.wmagic = (unsigned)(((1u << 22) + d->W - 1) / d->W);
+    q.wmagic2 = (unsigned)(((1u << 22) + d->W + 1) / (d->W + 2));
+    const bool bf = d->dtype == STEP_BF16;
+    if (l.pw) {
+        if (bf) STEP_LAUNCH((conv_wgrad16_lds2_kernel<bf16_t, 1>), pl.grid, dim3(384), stream, q);
+        else STEP_LAUNCH((conv_wgrad16_lds2_kernel<f16_t, 1>), pl.grid, dim3(384), stream, q);
+    } else if (l.wide) {
+        if (bf) STEP_LAUNCH((conv_wgrad16_lds12_wide_kernel<bf16_t, 3>), pl.grid, dim3(768), stream, q);
+        else STEP_LAUNCH((conv_wgrad16_lds12_wide_kernel<f16_t, 3>), pl.grid, dim3(768), stream, q);
+    } else {
+        if (bf) STEP_LAUNCH((conv_wgrad16_lds12_kernel<bf16_t, 3>), pl.grid, dim3(768), stream, q);
+        else STEP_LAUNCH((conv_wgrad16_lds12_kernel<f16_t, 3>), pl.grid, dim3(768), stream, q);
+    }
+}
+
+// pointwise layers: the pixel-stream form (wgradpws_plan)
+static void wgradpws_run(const step_conv_desc* d, const WgradPlan& pl, const void* x, const void* dy, float* dw, float* ws, step_stream_t stream) {
+    const WgPwsPlan& pp = pl.pws;
+    WgradPwsParams q;
+    q.x = x; q.dy = dy; q.dw = dw; q.ws = ws;
+    q.M = (long long)d->N * d->D * d->H * d->W; q.ppj = pp.ppj;
+    q.Cin = d->Cin; q.Cout = d->Cout; q.x_cstride = d->x_cstride; q.x_coff = d->x_coff; q.dy_cstride = d->y_cstride; q.dy_coff = d->y_coff;
+    q.cot = pp.cot; q.cit = pp.cit; q.co_t = pp.co_t; q.ci_t = pp.ci_t;
+    if (d->dtype == STEP_BF16) STEP_LAUNCH((conv_wgrad16_pws_kernel<bf16_t>), pl.grid, dim3(512), stream, q);
+    else STEP_LAUNCH((conv_wgrad16_pws_kernel<f16_t>), pl.grid, dim3(512), stream, q);
+}
+
+// strict: a workspace that is given must be usable (the fp32 and the deferred entry points); else a short or misaligned one silently
+// means atomics.  defer != NULL: the fixed-order sum of the partial results is NOT launched; *defer describes it (step_wgrad_reduce_group
+// runs several layers' sums as one launch).  kind 0: nothing is pending (the atomics forms, an empty batch).
 static int conv_wgrad_impl(const step_conv_desc* d, const void* x, const void* dy, bool w16, float* dw, int accumulate, void* ws,
-                           size_t ws_bytes, step_stream_t stream, step_wgrad_reduce_item* defer = nullptr) {
-    reduce_item_none(defer);
+                           size_t ws_bytes, bool strict, step_stream_t stream, step_wgrad_reduce_item* defer = nullptr) {
+    if (defer) *defer = step_wgrad_reduce_item();
     if (!d) return STEP_E_NULL;
+    const bool aligned = ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0;
+    const WgradPlan pl = wgrad_plan(d, w16, aligned, dw, accumulate, ws, ws_bytes, false);
+    if (strict && ws) {
+        // short or misaligned is an error, not a silent return to atomics; the bound is what the workspace query answers, which assumes
+        // aligned operands (only for misaligned 16-bit ones can this call's own form need something else)
+        const size_t told = w16 && !aligned ? wgrad_plan(d, w16, true, dw, accumulate, nullptr, 0, true).need : pl.need;
+        if (ws_bytes < told || ((uintptr_t)ws % 16) != 0) return STEP_E_SHAPE;
+    }
     if (w16 && d->dtype != STEP_BF16 && d->dtype != STEP_F16) return STEP_E_UNSUPPORTED;
     if (d->N < 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return STEP_E_SHAPE;
     if (d->kd <= 0 || d->kh <= 0 || d->kw <= 0 || !(d->kd & 1) || !(d->kh & 1) || !(d->kw & 1)) return STEP_E_UNSUPPORTED;
     if (d->x_coff < 0 || d->x_coff + d->Cin > d->x_cstride || d->y_coff < 0 || d->y_coff + d->Cout > d->y_cstride) return STEP_E_SHAPE;
     if (!dw) return STEP_E_NULL;
-    const int ntaps = d->kd * d->kh * d->kw;
-    const bool pws_form = w16 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && d->N > 0 && wgradpws_plan(d).ok;
-    const bool lds_form = pws_form || (w16 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && wgrad16_plan(d).ok && d->N > 0);
-    // the per-tap kernel with a workspace: partial tiles + a fixed-order sum write every element of dw themselves; its jobs are
-    // shorter than the atomics form's (wgrad_min_pixels)
-    const WgJobs jws = wgrad_jobs(d, w16 ? WG_WS_16 : WG_WS_F32);
-    const bool tap_ws = !lds_form && d->N > 0 && ws && ((uintptr_t)ws % 16) == 0 && ws_bytes >= wgrad_jobs_ws_bytes(jws) && jws.jobs > 0;
-    const WgJobs jb = tap_ws ? jws : wgrad_jobs(d, WG_ATOMICS);
-    if (!accumulate && !tap_ws) {
-        const int e = (int)hipMemsetAsync(dw, 0, (size_t)d->Cout * d->Cin * ntaps * sizeof(float), (hipStream_t)stream);
+    if (!accumulate && pl.form != WGF_TAP_WS) {                // (the per-tap sum writes every element of dw itself; the other sums add to it)
+        const int e = (int)hipMemsetAsync(dw, 0, (size_t)d->Cout * d->Cin * d->kd * d->kh * d->kw * sizeof(float), (hipStream_t)stream);
         if (e != 0) return e;
     }
     if (d->N == 0) return STEP_OK;
     if (!x || !dy) return STEP_E_NULL;
-    WgradParams p;
-    p.x = x; p.dy = dy; p.dw = dw; p.ws = tap_ws ? (float*)ws : nullptr;
-    p.N = d->N; p.D = d->D; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.kd = d->kd; p.kh = d->kh; p.kw = d->kw;
-    p.x_cstride = d->x_cstride; p.x_coff = d->x_coff; p.dy_cstride = d->y_cstride; p.dy_coff = d->y_coff;
-    // pointwise layers: the pixel-stream form (wgradpws_plan)
-    if (pws_form) {
-        const WgPwsPlan pp = wgradpws_plan(d);
-        WgradPwsParams q;
-        q.x = x; q.dy = dy; q.dw = dw;
-        q.M = (long long)d->N * d->D * d->H * d->W; q.ppj = pp.ppj;
-        q.Cin = d->Cin; q.Cout = d->Cout; q.x_cstride = d->x_cstride; q.x_coff = d->x_coff; q.dy_cstride = d->y_cstride; q.dy_coff = d->y_coff;
-        q.cot = pp.cot; q.cit = pp.cit; q.co_t = pp.co_t; q.ci_t = pp.ci_t;
-        const size_t need = (size_t)pp.gx * d->Cout * d->Cin * sizeof(float);
-        q.ws = (ws && ws_bytes >= need && ((uintptr_t)ws % 16) == 0 && ((uintptr_t)dw % 16) == 0) ? (float*)ws : nullptr;
-        const dim3 gridp((unsigned)pp.gx, (unsigned)pp.gy);
-        if (d->dtype == STEP_BF16) STEP_LAUNCH((conv_wgrad16_pws_kernel<bf16_t>), gridp, dim3(512), stream, q);
-        else STEP_LAUNCH((conv_wgrad16_pws_kernel<f16_t>), gridp, dim3(512), stream, q);
-        if (q.ws && defer) {
-            defer->kind = 3; defer->ws = q.ws; defer->dw = dw; defer->jobs = pp.gx; defer->Cout = d->Cout; defer->Cin = d->Cin; defer->taps = 1; defer->accumulate = 1;
-        } else if (q.ws) {
-            const long long n4 = (long long)d->Cout * d->Cin / 4;
-            STEP_LAUNCH(wgradpws_reduce_kernel, dim3(flat_grid((n4 + 15) / 16 * 256, 256)), dim3(256), stream, (const float*)q.ws, dw, pp.gx, n4, 1);   // (dw was cleared above unless accumulate)
-        }
-        return STEP_LAUNCH_CHECK();
-    }
-    // the LDS-tiled form (transpose reads): 3x3 windows or pointwise, channel counts in 16-byte vectors (wgrad16_plan)
-    if (w16 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
-        const Wg16Plan pl = wgrad16_plan(d);
-        if (pl.ok) {
-            Wgrad16Params q;
-            q.x = x; q.dy = dy; q.dw = dw;
-            q.N = d->N; q.D = d->D; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.Cout = d->Cout; q.kd = d->kd;
-            q.x_cstride = d->x_cstride; q.x_coff = d->x_coff; q.dy_cstride = d->y_cstride; q.dy_coff = d->y_coff;
-            q.cot = pl.cot; q.cit = pl.cit; q.cpp = pl.cpp; q.rows = pl.rows; q.units = pl.units; q.upj = pl.upj;
-            q.wmagic = (unsigned)(((1u << 22) + d->W - 1) / d->W);
-            q.wmagic2 = (unsigned)(((1u << 22) + d->W + 1) / (d->W + 2));
-            const size_t need = (size_t)pl.gx * pl.gy * 6 * (pl.pw ? 8 : 24) * 64 * 16;
-            q.ws = (ws && ws_bytes >= need && ((uintptr_t)ws % 16) == 0) ? (float*)ws : nullptr;
-            dim3 grid16((unsigned)pl.gx, (unsigned)pl.gy);
-#ifdef WG16_NOPF            /* experiment builds (make EXP=... EXPFLAGS=-DWG16_NOPF): the two-workgroup form for the 3x3 windows too */
-#define WG16_K3 conv_wgrad16_lds2_kernel
-#else
-#define WG16_K3 conv_wgrad16_lds_kernel
-#endif
-            if (pl.pw) {
-                if (d->dtype == STEP_BF16) STEP_LAUNCH((conv_wgrad16_lds2_kernel<bf16_t, 1>), grid16, dim3(384), stream, q);
-                else STEP_LAUNCH((conv_wgrad16_lds2_kernel<f16_t, 1>), grid16, dim3(384), stream, q);
-            } else {
-                if (pl.wide && pl.nw12) {
-                    if (d->dtype == STEP_BF16) STEP_LAUNCH((conv_wgrad16_lds12_wide_kernel<bf16_t, 3>), grid16, dim3(768), stream, q);
-                    else STEP_LAUNCH((conv_wgrad16_lds12_wide_kernel<f16_t, 3>), grid16, dim3(768), stream, q);
-                } else if (pl.wide) {
-                    if (d->dtype == STEP_BF16) STEP_LAUNCH((conv_wgrad16_lds_wide_kernel<bf16_t, 3>), grid16, dim3(384), stream, q);
-                    else STEP_LAUNCH((conv_wgrad16_lds_wide_kernel<f16_t, 3>), grid16, dim3(384), stream, q);
-                } else if (pl.nw12) {
-                    if (d->dtype == STEP_BF16) STEP_LAUNCH((conv_wgrad16_lds12_kernel<bf16_t, 3>), grid16, dim3(768), stream, q);
-                    else STEP_LAUNCH((conv_wgrad16_lds12_kernel<f16_t, 3>), grid16, dim3(768), stream, q);
-                } else if (d->dtype == STEP_BF16) STEP_LAUNCH((WG16_K3<bf16_t, 3>), grid16, dim3(384), stream, q);
-                else STEP_LAUNCH((WG16_K3<f16_t, 3>), grid16, dim3(384), stream, q);
-            }
-#undef WG16_K3
-            if (q.ws && defer) {
-                defer->kind = 2; defer->ws = q.ws; defer->dw = dw; defer->jobs = pl.gx; defer->gy = (int)pl.gy; defer->cot = pl.cot; defer->cit = pl.cit;
-                defer->Cout = d->Cout; defer->Cin = d->Cin; defer->taps = d->kd; defer->accumulate = 1; defer->pw = pl.nw12 ? 2 : (int)pl.pw;
-            } else if (q.ws) {
-                const long long groups = pl.gy * 6 * (pl.pw ? 8 : 24) * 64;
-                STEP_LAUNCH(wgrad16_reduce_kernel, dim3(flat_grid(groups * 4, 256)), dim3(256), stream, (const float*)q.ws, dw, (int)pl.gx, (int)pl.gy,
-                            pl.cot, pl.cit, d->Cout, d->Cin, d->kd, 1, pl.nw12 ? 2 : (int)pl.pw);      // (dw was cleared above unless accumulate)
-            }
-            return STEP_LAUNCH_CHECK();
-        }
-    }
-    if (ntaps == 1) {
-        const long long M = (long long)d->N * d->D * d->H * d->W;
-        if (M > 0x7fffffffLL) return STEP_E_UNSUPPORTED;
-        const int chunk = jb.chunk;
-        const long long full = jb.full;
-        const int tail = jb.tail;
-        int rc = STEP_OK;
-        auto launch = [&](long long jobs, int W, size_t pix0) {
-            p.N = 1; p.D = (int)jobs; p.H = 1; p.W = W; p.jobs = jobs; p.rows = 1; p.total_rows = jobs;
-            p.x = (const char*)x + pix0 * d->x_cstride * (d->dtype == STEP_F32 ? 4 : 2);
-            p.dy = (const char*)dy + pix0 * d->y_cstride * (w16 ? 2 : 4);
-            const bool narrow = d->Cin <= 32;
-            p.cot = ceil_div(d->Cout, 64); p.cit = ceil_div(d->Cin, narrow ? 32 : 64);
-            dim3 grid((unsigned)ceil_div64(jobs, 4), (unsigned)(p.cot * p.cit));
-#define STEP_WG(T_) do { if (narrow) STEP_LAUNCH((conv_wgrad_kernel<T_, 2, 1>), grid, dim3(256), stream, p); \
-                         else STEP_LAUNCH((conv_wgrad_kernel<T_, 2, 2>), grid, dim3(256), stream, p); } while (0)
-#define STEP_WG16(T_) do { if (narrow) STEP_LAUNCH((conv_wgrad_kernel<T_, 2, 1, true>), grid, dim3(256), stream, p); \
-                           else STEP_LAUNCH((conv_wgrad_kernel<T_, 2, 2, true>), grid, dim3(256), stream, p); } while (0)
-            switch (d->dtype) {
-                case STEP_F32: STEP_WG(float); break;
-                case STEP_BF16: if (w16) STEP_WG16(bf16_t); else STEP_WG(bf16_t); break;
-                case STEP_F16: if (w16) STEP_WG16(f16_t); else STEP_WG(f16_t); break;
-                default: rc = STEP_E_DTYPE;
-            }
-        };
-        if (full) launch(full, chunk, 0);
-        if (rc == STEP_OK && tail) {
-            if (tap_ws) p.ws = (float*)ws + (size_t)ceil_div64(full, 4) * jb.gy * jb.per_tile;      // the tail job's tiles behind the full chunks
-            launch(1, tail, (size_t)full * chunk);
-        }
-        if (rc == STEP_OK && tap_ws && defer) {
-            defer->kind = 1; defer->ws = (const float*)ws; defer->dw = dw; defer->jobs = wgrad_ws_blocks(jb); defer->gy = (int)jb.gy; defer->nbw = jb.nbw;
-            defer->cot = jb.cot; defer->cit = jb.cit; defer->Cout = d->Cout; defer->Cin = d->Cin; defer->taps = 1; defer->accumulate = accumulate; defer->pw = 1;
-        } else if (rc == STEP_OK && tap_ws)
-            STEP_LAUNCH(wgrad_reduce_kernel, dim3(flat_grid(jb.gy * (long long)jb.per_tile * 4, 256)), dim3(256), stream, (const float*)ws, dw, wgrad_ws_blocks(jb),
-                        (int)jb.gy, 2, jb.nbw, jb.cot, jb.cit, d->Cout, d->Cin, 1, accumulate);
-        return rc != STEP_OK ? rc : STEP_LAUNCH_CHECK();
-    }
-    const bool narrow = d->Cin <= 32;
-    p.cot = jb.cot; p.cit = jb.cit;
-    // (a tap-row form -- a job owns a row of three kw taps and re-pairs ten loaded pixels in registers -- measured 1.3-2.6x SLOWER
-    // than this per-tap form: 424 VGPRs, one wave per SIMD; removed)
-    const long long gy = jb.gy;
-    p.total_rows = (long long)d->N * d->D * d->H;
-    p.rows = jb.rows;
-    p.jobs = jb.jobs;
-    if (gy > 65535) return STEP_E_UNSUPPORTED;
-    dim3 grid((unsigned)ceil_div64(p.jobs, 4), (unsigned)gy);
-    switch (d->dtype) {
-        case STEP_F32: STEP_WG(float); break;
-        case STEP_BF16: if (w16) STEP_WG16(bf16_t); else STEP_WG(bf16_t); break;
-        case STEP_F16: if (w16) STEP_WG16(f16_t); else STEP_WG(f16_t); break;
-        default: return STEP_E_DTYPE;
-    }
-#undef STEP_WG
-#undef STEP_WG16
-    if (tap_ws && defer) {
-        defer->kind = 1; defer->ws = (const float*)ws; defer->dw = dw; defer->jobs = wgrad_ws_blocks(jb); defer->gy = (int)jb.gy; defer->nbw = jb.nbw;
-        defer->cot = jb.cot; defer->cit = jb.cit; defer->Cout = d->Cout; defer->Cin = d->Cin; defer->taps = ntaps; defer->accumulate = accumulate; defer->pw = 0;
-    } else if (tap_ws)
-        STEP_LAUNCH(wgrad_reduce_kernel, dim3(flat_grid(jb.gy * (long long)jb.per_tile * 4, 256)), dim3(256), stream, (const float*)ws, dw, wgrad_ws_blocks(jb),
-                    (int)jb.gy, 2, jb.nbw, jb.cot, jb.cit, d->Cout, d->Cin, ntaps, accumulate);
+    if (pl.status != STEP_OK) return pl.status;
+    float* const wsp = pl.use_ws ? (float*)ws : nullptr;
+    int rc = STEP_OK;
+    if (pl.form == WGF_PWS) wgradpws_run(d, pl, x, dy, dw, wsp, stream);
+    else if (pl.form == WGF_LDS) wgrad16_lds_run(d, pl, x, dy, dw, wsp, stream);
+    else rc = wgrad_tap_run(d, pl, x, dy, dw, wsp, stream);
+    if (rc != STEP_OK) return rc;
+    // the one path to the sum: hand the item over, or run it
+    if (defer) *defer = pl.item;
+    else if (pl.item.kind != 0) return wgrad_item_launch(pl.item, stream);
     return STEP_LAUNCH_CHECK();
 }
 
-size_t step_conv_wgrad_workspace_bytes(const step_conv_desc* d) {
-    if (!d || d->N <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->kd <= 0 || d->kh <= 0 || d->kw <= 0) return 0;
-    return wgrad_jobs_ws_bytes(wgrad_jobs(d, WG_WS_F32));
+int step_conv_wgrad(const step_conv_desc* d, const void* x, const float* dy, float* dw, int accumulate, step_stream_t stream) {
+    return conv_wgrad_impl(d, x, dy, false, dw, accumulate, nullptr, 0, false, stream);
 }
 
 int step_conv_wgrad_ws(const step_conv_desc* d, const void* x, const float* dy, float* dw, int accumulate, void* ws, size_t ws_bytes,
                        step_stream_t stream) {
-    // a scratch that is given must be usable: a short or misaligned one is an error, not a silent return to atomics
-    if (ws && d && (ws_bytes < step_conv_wgrad_workspace_bytes(d) || ((uintptr_t)ws % 16) != 0)) return STEP_E_SHAPE;
-    return conv_wgrad_impl(d, x, dy, false, dw, accumulate, ws, ws_bytes, stream);
-}
-
-int step_conv_wgrad(const step_conv_desc* d, const void* x, const float* dy, float* dw, int accumulate, step_stream_t stream) {
-    return conv_wgrad_impl(d, x, dy, false, dw, accumulate, nullptr, 0, stream);
+    return conv_wgrad_impl(d, x, dy, false, dw, accumulate, ws, ws_bytes, true, stream);
 }
 
 int step_conv_wgrad16(const step_conv_desc* d, const void* x, const void* dy, float* dw, int accumulate, step_stream_t stream) {
-    return conv_wgrad_impl(d, x, dy, true, dw, accumulate, nullptr, 0, stream);
-}
-
-size_t step_conv_wgrad16_workspace_bytes(const step_conv_desc* d) {
-    if (!d || (d->dtype != STEP_BF16 && d->dtype != STEP_F16)) return 0;
-    const WgPwsPlan pp = wgradpws_plan(d);
-    if (pp.ok) return (size_t)pp.gx * d->Cout * d->Cin * sizeof(float);
-    const Wg16Plan pl = wgrad16_plan(d);
-    if (pl.ok) return (size_t)pl.gx * pl.gy * 6 * (pl.pw ? 8 : 24) * 64 * 16;
-    if (d->N <= 0 || d->D <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->kd <= 0 || d->kh <= 0 || d->kw <= 0) return 0;
-    return wgrad_jobs_ws_bytes(wgrad_jobs(d, WG_WS_16));         // the per-tap 16-bit form: partial tiles of its wavefront jobs
+    return conv_wgrad_impl(d, x, dy, true, dw, accumulate, nullptr, 0, false, stream);
 }
 
 int step_conv_wgrad16_ws(const step_conv_desc* d, const void* x, const void* dy, float* dw, int accumulate, void* ws, size_t ws_bytes,
                          step_stream_t stream) {
-    return conv_wgrad_impl(d, x, dy, true, dw, accumulate, ws, ws_bytes, stream);
-}
-
-
-int step_conv_wgrad_kernel_name(const step_conv_desc* d, int dy16, char* buf, int buflen) {
-    if (!d || !buf || buflen <= 0) return STEP_E_NULL;
-    const char* t = d->dtype == STEP_F32 ? "float" : (d->dtype == STEP_BF16 ? "step::bf16_t" : "step::f16_t");
-    const Wg16Plan pl = dy16 ? wgrad16_plan(d) : Wg16Plan();
-    if (dy16 && wgradpws_plan(d).ok) snprintf(buf, (size_t)buflen, "void step::conv_wgrad16_pws_kernel<%s>(step::WgradPwsParams)", t);
-    else if (dy16 && pl.ok) {
-        const bool pw = d->kd == 1 && d->kh == 1 && d->kw == 1;
-        snprintf(buf, (size_t)buflen, "void step::%s<%s, %d>(step::Wgrad16Params)",
-                 pw ? "conv_wgrad16_lds2_kernel" : (pl.nw12 ? (pl.wide ? "conv_wgrad16_lds12_wide_kernel" : "conv_wgrad16_lds12_kernel")
-                                                             : (pl.wide ? "conv_wgrad16_lds_wide_kernel" : "conv_wgrad16_lds_kernel")), t, pw ? 1 : 3);
-    } else
-        snprintf(buf, (size_t)buflen, "void step::conv_wgrad_kernel<%s, 2, %d, %s>(step::WgradParams)", t, d->Cin <= 32 ? 1 : 2, dy16 ? "true" : "false");
-    return STEP_OK;
+    return conv_wgrad_impl(d, x, dy, true, dw, accumulate, ws, ws_bytes, false, stream);
 }
 
 int step_conv_wgrad_partial(const step_conv_desc* d, const void* x, const void* dy, int dy16, float* dw, int accumulate, void* ws, size_t ws_bytes,
                             step_wgrad_reduce_item* item, step_stream_t stream) {
     if (!item) return STEP_E_NULL;
-    if (ws && d && ((uintptr_t)ws % 16) != 0) return STEP_E_SHAPE;
-    if (ws && d && ws_bytes < (dy16 ? step_conv_wgrad16_workspace_bytes(d) : step_conv_wgrad_workspace_bytes(d))) return STEP_E_SHAPE;
-    return conv_wgrad_impl(d, x, dy, dy16 != 0, dw, accumulate, ws, ws_bytes, stream, item);
+    return conv_wgrad_impl(d, x, dy, dy16 != 0, dw, accumulate, ws, ws_bytes, true, stream, item);
 }
 
-static int wgrad_reduce_group_launch(const WgradReduceGroup& g, int m, long long most, step_stream_t stream) {
-    STEP_LAUNCH(wgrad_reduce_group_kernel, dim3(flat_grid(most, 256), (unsigned)m), dim3(256), stream, g);
-    return STEP_LAUNCH_CHECK();
+// The three queries answer for 16-byte aligned operands (x, dy, dw) and a workspace that is accepted: what a call with such arguments
+// and step_conv_wgrad{,16}_workspace_bytes(d) bytes of scratch runs.
+static WgradPlan wgrad_plan_query(const step_conv_desc* d, bool w16) { return wgrad_plan(d, w16, true, nullptr, 0, nullptr, 0, true); }
+
+size_t step_conv_wgrad_workspace_bytes(const step_conv_desc* d) { return wgrad_plan_query(d, false).need; }
+
+size_t step_conv_wgrad16_workspace_bytes(const step_conv_desc* d) { return wgrad_plan_query(d, true).need; }
+
+int step_conv_wgrad_kernel_name(const step_conv_desc* d, int dy16, char* buf, int buflen) {
+    if (!d || !buf || buflen <= 0) return STEP_E_NULL;
+    const char* t = d->dtype == STEP_F32 ? "float" : (d->dtype == STEP_BF16 ? "step::bf16_t" : "step::f16_t");
+    const WgradPlan pl = wgrad_plan_query(d, dy16 != 0);
+    if (pl.form == WGF_PWS) snprintf(buf, (size_t)buflen, "void step::%s<%s>(step::WgradPwsParams)", pl.kernel, t);
+    else if (pl.form == WGF_LDS) snprintf(buf, (size_t)buflen, "void step::%s<%s, %d>(step::Wgrad16Params)", pl.kernel, t, pl.lds.pw ? 1 : 3);
+    else snprintf(buf, (size_t)buflen, "void step::%s<%s, 2, %d, %s>(step::WgradParams)", pl.kernel, t, pl.tap.nbw, dy16 ? "true" : "false");
+    return STEP_OK;
 }
 
 int step_wgrad_reduce_group(const step_wgrad_reduce_item* items, int n, step_stream_t stream) {
@@ -1532,7 +1529,7 @@ int step_wgrad_reduce_group(const step_wgrad_reduce_item* items, int n, step_str
     // The members of one launch run CONCURRENTLY (blockIdx.y) and each ends in a plain read-modify-write of its dw: two sums into the
     // same gradient (a unit used twice in one graph, leftovers of an earlier backward) must not share a launch.  A repeated dw closes the
     // launch; the stream then orders the two sums as separate launches did before the grouping.
-    WgradReduceGroup g;
+    WgradReduceGroup g = WgradReduceGroup();
     int m = 0;
     long long most = 0;
     for (int i = 0; i < n; ++i) {
@@ -1541,26 +1538,27 @@ int step_wgrad_reduce_group(const step_wgrad_reduce_item* items, int n, step_str
         bool dup = false;
         for (int q = 0; q < m; ++q) dup = dup || g.it[q].dw == it.dw;
         if (dup) {
-            for (int q = m; q < STEP_WGRAD_REDUCE_MAX; ++q) g.it[q] = step_wgrad_reduce_item();
             const int rc = wgrad_reduce_group_launch(g, m, most, stream);
             if (rc != STEP_OK) return rc;
             m = 0; most = 0;
         }
-        const long long work = it.kind == 1 ? (long long)it.gy * (2 * it.nbw * 16 * 64) * 4
-                             : (it.kind == 2 ? (long long)it.gy * 6 * (it.pw == 1 ? 8 : 24) * 64 * 4 : ((long long)it.Cout * it.Cin / 4 + 15) / 16 * 256);
-        if (work > most) most = work;
+        if (wgrad_item_work(it) > most) most = wgrad_item_work(it);
         g.it[m++] = it;
     }
-    if (m == 0) return STEP_OK;
-    for (int i = m; i < STEP_WGRAD_REDUCE_MAX; ++i) g.it[i] = step_wgrad_reduce_item();
-    return wgrad_reduce_group_launch(g, m, most, stream);
+    return m == 0 ? STEP_OK : wgrad_reduce_group_launch(g, m, most, stream);
 }
 
 
+
+// output extent of the stem (7 taps, stride 2, padding 2 + 3) along one axis
+static int stem_out(int n) { return (n + 5 - 7) / 2 + 1; }
+
 struct StemJobs { int To, Ho, Wo, cot, rows, hchunks; long long jobs; };
+// floats of one job's partial tiles: 49 (kd, kh) filter rows x cot tiles of 32 registers x 64 lanes (stem_wgrad_kernel's grid rows)
+static long long stem_wgrad_job_floats(const StemJobs& j) { return (long long)49 * j.cot * 32 * 64; }
 static StemJobs stem_wgrad_jobs(int N, int T, int H, int W, int Cout) {
     StemJobs j;
-    j.To = (T + 5 - 7) / 2 + 1; j.Ho = (H + 5 - 7) / 2 + 1; j.Wo = (W + 5 - 7) / 2 + 1;
+    j.To = stem_out(T); j.Ho = stem_out(H); j.Wo = stem_out(W);
     j.cot = ceil_div(Cout, 64);
     j.rows = 8; j.hchunks = ceil_div(j.Ho > 0 ? j.Ho : 1, j.rows);       // 8 output rows per wavefront job: enough jobs for one clip
     j.jobs = (long long)N * (j.To > 0 ? j.To : 0) * j.hchunks;
@@ -1571,7 +1569,7 @@ size_t step_stem_wgrad_workspace_bytes(int N, int T, int H, int W, int Cout) {
     if (N <= 0 || T <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
     const StemJobs j = stem_wgrad_jobs(N, T, H, W, Cout);
     if (j.To <= 0 || j.Ho <= 0 || j.Wo <= 0) return 0;
-    return (size_t)j.jobs * 49 * j.cot * 32 * 64 * sizeof(float);
+    return (size_t)j.jobs * (size_t)stem_wgrad_job_floats(j) * sizeof(float);
 }
 
 static int stem_wgrad_impl(int dtype, const void* x, int N, int T, int H, int W, const float* dy, int Cout, float* dw, int accumulate,
@@ -1601,7 +1599,7 @@ static int stem_wgrad_impl(int dtype, const void* x, int N, int T, int H, int W,
         default: return STEP_E_DTYPE;
     }
     if (ws)
-        STEP_LAUNCH(stem_wgrad_reduce_kernel, dim3(flat_grid((long long)49 * p.cot * 32 * 64, 256)), dim3(256), stream, (const float*)ws, dw,
+        STEP_LAUNCH(stem_wgrad_reduce_kernel, dim3(flat_grid(stem_wgrad_job_floats(sj), 256)), dim3(256), stream, (const float*)ws, dw,
                     p.jobs, 49 * p.cot, p.cot, Cout, accumulate);
     return STEP_LAUNCH_CHECK();
 }
@@ -1619,12 +1617,14 @@ int step_stem_wgrad_ws(int dtype, const void* x, int N, int T, int H, int W, con
 
 
 // launch plan of the 16-bit stem form: ok = false -> the caller keeps step_stem_wgrad
-struct Sw16Plan { bool ok; int P, tiles_h, tiles_w, gx, gy; long long tiles; };
+struct Sw16Plan { bool ok; int To, Ho, Wo, P, tiles_h, tiles_w, gx, gy; long long tiles; };
+// 16-byte groups of one pixel-axis workgroup's partial tiles: gy channel blocks x 7 waves x 5 accumulators x 4 groups x 64 lanes
+static long long stem_wgrad16_groups(const Sw16Plan& pl) { return (long long)pl.gy * 35 * 4 * 64; }
 static Sw16Plan stem_wgrad16_plan(int dtype, int N, int T, int H, int W, int Cout) {
-    Sw16Plan pl; pl.ok = false; pl.P = pl.tiles_h = pl.tiles_w = pl.gx = pl.gy = 0; pl.tiles = 0;
+    Sw16Plan pl; pl.ok = false; pl.To = pl.Ho = pl.Wo = pl.P = pl.tiles_h = pl.tiles_w = pl.gx = pl.gy = 0; pl.tiles = 0;
     if (dtype != STEP_BF16 && dtype != STEP_F16) return pl;
     if (N <= 0 || T <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (W % 8) || (Cout % 8)) return pl;      // 16-byte rows of the clip / the gradient
-    const int To = (T + 5 - 7) / 2 + 1, Ho = (H + 5 - 7) / 2 + 1, Wo = (W + 5 - 7) / 2 + 1;
+    const int To = pl.To = stem_out(T), Ho = pl.Ho = stem_out(H), Wo = pl.Wo = stem_out(W);
     if (To <= 0 || Ho <= 0 || Wo <= 0) return pl;
     pl.tiles_w = ceil_div(Wo, SW16_PMAX);
     pl.P = ceil_div(ceil_div(Wo, pl.tiles_w), 16) * 16;
@@ -1641,7 +1641,7 @@ static Sw16Plan stem_wgrad16_plan(int dtype, int N, int T, int H, int W, int Cou
 
 size_t step_stem_wgrad16_workspace_bytes(int dtype, int N, int T, int H, int W, int Cout) {
     const Sw16Plan pl = stem_wgrad16_plan(dtype, N, T, H, W, Cout);
-    return pl.ok ? (size_t)pl.gx * pl.gy * 35 * 4 * 64 * sizeof(f32x4) : 0;
+    return pl.ok ? (size_t)pl.gx * (size_t)stem_wgrad16_groups(pl) * sizeof(f32x4) : 0;
 }
 
 int step_stem_wgrad16(int dtype, const void* x, int N, int T, int H, int W, const void* dy, int Cout, float* dw, int accumulate,
@@ -1661,13 +1661,12 @@ int step_stem_wgrad16(int dtype, const void* x, int N, int T, int H, int W, cons
         return STEP_E_ALIGN;
     StemWgrad16Params p;
     p.x = x; p.dy = dy; p.ws = (float*)ws; p.N = N; p.T = T; p.H = H; p.W = W;
-    p.To = (T + 5 - 7) / 2 + 1; p.Ho = (H + 5 - 7) / 2 + 1; p.Wo = (W + 5 - 7) / 2 + 1;
+    p.To = pl.To; p.Ho = pl.Ho; p.Wo = pl.Wo;
     p.Cout = Cout; p.P = pl.P; p.tiles_h = pl.tiles_h; p.tiles_w = pl.tiles_w; p.tiles = pl.tiles;
     const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy);
     if (dtype == STEP_BF16) STEP_LAUNCH((stem_wgrad16_kernel<bf16_t>), grid, dim3(SW16_NT), stream, p);
     else STEP_LAUNCH((stem_wgrad16_kernel<f16_t>), grid, dim3(SW16_NT), stream, p);
-    const long long groups = (long long)pl.gy * 35 * 4 * 64;
-    STEP_LAUNCH(stem_wgrad16_reduce_kernel, dim3(flat_grid(groups, 256)), dim3(256), stream, (const float*)ws, dw, pl.gx, pl.gy, Cout,
+    STEP_LAUNCH(stem_wgrad16_reduce_kernel, dim3(flat_grid(stem_wgrad16_groups(pl), 256)), dim3(256), stream, (const float*)ws, dw, pl.gx, pl.gy, Cout,
                 accumulate);
     return STEP_LAUNCH_CHECK();
 }

@@ -418,10 +418,11 @@ def _grad_slice(gy, vec):
     return cs
 
 
-def _wgrad_setup(who, x, gy, Cout, k, into, w16):
+def _wgrad_setup(who, x, gy, Cout, k, into, w16, use_ws=True):
     """What conv_wgrad / conv_wgrad16 / conv_wgrad_partial (`who`, for the error text) share: gy in the kernel's gradient type (fp32, or
     with w16 the 16-bit activation type as it arrives), read in place where it lies on the kernel's vector grid and densified where it
-    does not; dw = the validated `into` or a new fp32 [Cout, Cin, kd, kh, kw]; the descriptor.  -> (gy, dw, desc)"""
+    does not; dw = the validated `into` or a new fp32 [Cout, Cin, kd, kh, kw]; the descriptor; the scratch for the partial tiles (their
+    fixed-order sum: no atomics, deterministic), none with use_ws = False.  -> (gy, dw, desc, ws, ws_bytes)"""
     Cin = x.shape[-1]
     if not w16 and gy.dtype != torch.float32:
         gy = gy.float()
@@ -434,7 +435,27 @@ def _wgrad_setup(who, x, gy, Cout, k, into, w16):
         dw = into
     else:
         dw = torch.empty((Cout, Cin) + tuple(k), dtype=torch.float32, device=x.device)
-    return gy, dw, _conv_desc(x, Cout, k, gcs)
+    d = _conv_desc(x, Cout, k, gcs)
+    L = _lib.lib()
+    wsb = (L.step_conv_wgrad16_workspace_bytes if w16 else L.step_conv_wgrad_workspace_bytes)(ctypes.byref(d)) if use_ws else 0
+    return gy, dw, d, _workspace(wsb, x.device), wsb
+
+
+def _conv_wgrad(x, gy, Cout, k, into, w16):
+    L = _lib.lib()
+    N, D, H, W, Cin = x.shape
+    who = "conv_wgrad16" if w16 else "conv_wgrad"
+    entry = "step_%s_ws" % who
+    gy, dw, d, ws, wsb = _wgrad_setup(who, x, gy, Cout, k, into, w16, WGRAD16_WS if w16 else WGRAD_WS)
+
+    def describe():
+        pix, taps = N * D * H * W, k[0] * k[1] * k[2]
+        # algorithmic: x and dy read once, dw written once (fp32); the kernel variant is chosen inside the library
+        return (_kernel_name(L.step_conv_wgrad_kernel_name, ctypes.byref(d), int(w16)), 2.0 * pix * Cout * Cin * taps,
+                pix * (Cin * x.element_size() + Cout * gy.element_size()) + 4.0 * Cout * Cin * taps)
+    _run(lambda: _capi.check(getattr(L, entry)(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(dw), int(into is not None),
+                                               _lib.dptr(ws), wsb, _lib.stream_ptr(x.device)), entry), describe, limited=False)
+    return dw
 
 
 def conv_wgrad(x, gy, Cout, k, into=None):
@@ -442,40 +463,15 @@ def conv_wgrad(x, gy, Cout, k, into=None):
     slice), gy fp32 channels-last [N,D,H,W,Cout] (gradient w.r.t. the conv output before the affine epilogue).
     Returns fp32 [Cout, Cin, kd, kh, kw]; with `into` (a dense fp32 tensor of that many elements, e.g. the parameter's
     .grad) the result is ACCUMULATED into it instead (the kernel's accumulate mode: no clear, no separate add)."""
-    L = _lib.lib()
-    N, D, H, W, Cin = x.shape
-    gy, dw, d = _wgrad_setup("conv_wgrad", x, gy, Cout, k, into, False)
-
-    def describe():
-        pix = N * D * H * W
-        # algorithmic: x and dy read once, dw written once (fp32); the kernel variant is chosen by Cin inside the library
-        return (_kernel_name(L.step_conv_wgrad_kernel_name, ctypes.byref(d), 0), 2.0 * pix * Cout * Cin * k[0] * k[1] * k[2],
-                pix * (Cin * x.element_size() + Cout * 4) + 4.0 * Cout * Cin * k[0] * k[1] * k[2])
-    wsb = L.step_conv_wgrad_workspace_bytes(ctypes.byref(d)) if WGRAD_WS else 0     # partial tiles + fixed-order sum: no atomics, deterministic
-    ws = _workspace(wsb, x.device)
-    _run(lambda: _capi.check(L.step_conv_wgrad_ws(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(dw), int(into is not None),
-                                                  _lib.dptr(ws), wsb, _lib.stream_ptr(x.device)), "step_conv_wgrad_ws"), describe, limited=False)
-    return dw
+    return _conv_wgrad(x, gy, Cout, k, into, False)
 
 
 def conv_wgrad16(x, gy, Cout, k, into=None):
     """conv_wgrad on the 16-bit matrix instructions: x and gy both in the 16-bit activation dtype (gy dense channels-last
     [N,D,H,W,Cout]); fp32 result / accumulation as conv_wgrad."""
-    L = _lib.lib()
-    N, D, H, W, Cin = x.shape
     if gy.dtype != x.dtype or x.dtype == torch.float32:
         raise RuntimeError("step_amd: conv_wgrad16 wants x and gy in the same 16-bit dtype")
-    gy, dw, d = _wgrad_setup("conv_wgrad16", x, gy, Cout, k, into, True)
-
-    def describe():
-        pix = N * D * H * W
-        return (_kernel_name(L.step_conv_wgrad_kernel_name, ctypes.byref(d), 1), 2.0 * pix * Cout * Cin * k[0] * k[1] * k[2],
-                pix * (Cin + Cout) * x.element_size() + 4.0 * Cout * Cin * k[0] * k[1] * k[2])
-    wsb = L.step_conv_wgrad16_workspace_bytes(ctypes.byref(d)) if WGRAD16_WS else 0   # > 0: the LDS-tiled form with a two-stage sum
-    ws = _workspace(wsb, x.device)
-    _run(lambda: _capi.check(L.step_conv_wgrad16_ws(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(dw), int(into is not None),
-                                                    _lib.dptr(ws), wsb, _lib.stream_ptr(x.device)), "step_conv_wgrad16_ws"), describe, limited=False)
-    return dw
+    return _conv_wgrad(x, gy, Cout, k, into, True)
 
 
 def conv_wgrad_partial(x, gy, Cout, k, into=None):
@@ -484,9 +480,7 @@ def conv_wgrad_partial(x, gy, Cout, k, into=None):
     `ws` alive until then.  item.kind == 0: nothing is pending."""
     L = _lib.lib()
     w16 = gy.dtype == x.dtype and x.dtype != torch.float32
-    gy, dw, d = _wgrad_setup("conv_wgrad_partial", x, gy, Cout, k, into, w16)
-    wsb = (L.step_conv_wgrad16_workspace_bytes if w16 else L.step_conv_wgrad_workspace_bytes)(ctypes.byref(d))
-    ws = _workspace(wsb, x.device)
+    gy, dw, d, ws, wsb = _wgrad_setup("conv_wgrad_partial", x, gy, Cout, k, into, w16)
     item = _capi.WgradReduceItem()
     _capi.check(L.step_conv_wgrad_partial(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), int(w16), _lib.dptr(dw), int(into is not None), _lib.dptr(ws), wsb,
                                           ctypes.byref(item), _lib.stream_ptr(x.device)), "step_conv_wgrad_partial")

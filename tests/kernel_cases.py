@@ -1487,6 +1487,92 @@ def case_wgrad_partial_and_grouped_reduce(bk, golden):
     assert np.array_equal(dwb.get(), dwa.get())
 
 
+def case_wgrad_workspace_is_what_is_used(bk, golden):
+    """The number the workspace queries answer is the number the kernels use, for every form that has a workspace: the queried scratch
+    followed by a 4 KiB guard, all NaN; the _ws entry and step_conv_wgrad_partial + step_wgrad_reduce_group must give the gradient (so
+    every partial the sum reads was written: a NaN left in place would reach dw) and leave the guard untouched (nothing is written past
+    the queried size); the deferred item's kind is the one of the form step_conv_wgrad_kernel_name names.  The stem's two workspace
+    forms get the same guard."""
+    rs = np.random.RandomState(37)
+    NAN32 = np.float32(np.nan).view(np.uint32)
+    GUARD = 4096
+
+    def guarded(nb):
+        assert nb > 0 and nb % 16 == 0, nb
+        return bk.dev(np.full((nb + GUARD) // 4, np.nan, np.float32))
+
+    def guard_intact(buf, nb):
+        return bool((buf.get().view(np.uint32)[nb // 4:] == NAN32).all())
+
+    # (dtype, 16-bit entry, wgrad16_lds, N, Cin, Cout, D, H, W, k, kernel, item kind): the small shapes of case_conv_wgrad / case_conv_wgrad16
+    forms = [(F32, False, 1, 2, 24, 40, 3, 5, 19, (3, 3, 3), "conv_wgrad_kernel<float, 2, 1, false>", 1),                  # per-tap fp32, window
+             (F32, False, 1, 1, 40, 70, 1, 9, 130, (1, 1, 1), "conv_wgrad_kernel<float, 2, 2, false>", 1),                 # per-tap fp32, pointwise: 18 chunks of 64 pixels + a tail of 18
+             (BF16, True, 0, 2, 24, 40, 3, 5, 19, (3, 3, 3), "conv_wgrad_kernel<step::bf16_t, 2, 1, true>", 1),            # per-tap 16-bit
+             (BF16, True, 1, 1, 64, 72, 3, 20, 14, (3, 3, 3), "conv_wgrad16_lds12_kernel<step::bf16_t, 3>", 2),            # LDS-tiled 3x3
+             (F16, True, 1, 2, 16, 32, 1, 3, 100, (3, 3, 3), "conv_wgrad16_lds12_wide_kernel<step::f16_t, 3>", 2),         # LDS-tiled, wide halo
+             (BF16, True, 2, 1, 392, 72, 2, 9, 40, (1, 1, 1), "conv_wgrad16_lds2_kernel<step::bf16_t, 1>", 2),             # LDS-tiled pointwise
+             (BF16, True, 1, 1, 72, 40, 2, 36, 40, (1, 1, 1), "conv_wgrad16_pws_kernel<step::bf16_t>", 3)]                 # pixel stream
+    try:
+        for (dt, w16, ldsopt, N, Cin, Cout, D, H, W, k, kernel, kind) in forms:
+            _capi.set_option(bk.lib, "wgrad16_lds", ldsopt)
+            x = rs.randn(N, Cin, D, H, W).astype(np.float32)
+            gy = rs.randn(N, Cout, D, H, W).astype(np.float32)
+            gdt = dt if w16 else F32
+            w = torch.zeros(Cout, Cin, *k, requires_grad=True)
+            F.conv3d(torch.from_numpy(quantize(x, dt)), w, padding=tuple(kk // 2 for kk in k)).backward(torch.from_numpy(quantize(gy, gdt)))
+            ref = w.grad.numpy()
+            xd, gd = bk.dev(encode(cl(x), dt)), bk.dev(encode(cl(gy), gdt))
+            d = _capi.ConvDesc(dtype=dt, N=N, D=D, H=H, W=W, Cin=Cin, Cout=Cout, kd=k[0], kh=k[1], kw=k[2], x_cstride=Cin, x_coff=0,
+                               y_cstride=Cout, y_coff=0, res_cstride=0, res_coff=0, relu=0, split=0, y2_cstride=0, y2_coff=0)
+            buf = ctypes.create_string_buffer(256)
+            assert bk.lib.step_conv_wgrad_kernel_name(ctypes.byref(d), int(w16), buf, 256) == 0
+            assert kernel in buf.value.decode(), (kernel, buf.value.decode())
+            nb = (bk.lib.step_conv_wgrad16_workspace_bytes if w16 else bk.lib.step_conv_wgrad_workspace_bytes)(ctypes.byref(d))
+            ws = guarded(nb)
+            dw = bk.dev(np.full((Cout, Cin) + k, 7.0, np.float32))
+            fn = bk.lib.step_conv_wgrad16_ws if w16 else bk.lib.step_conv_wgrad_ws
+            assert fn(ctypes.byref(d), xd.ptr, gd.ptr, dw.ptr, 0, ws.ptr, nb, bk.stream) == 0
+            err = np.abs(dw.get() - ref).max() / np.abs(ref).max()
+            assert err < 2e-5, (kernel, err)                       # (a NaN compares false)
+            assert guard_intact(ws, nb), kernel
+            ws2 = guarded(nb)
+            dw2 = bk.dev(np.full((Cout, Cin) + k, 7.0, np.float32))
+            item = _capi.WgradReduceItem()
+            assert bk.lib.step_conv_wgrad_partial(ctypes.byref(d), xd.ptr, gd.ptr, int(w16), dw2.ptr, 0, ws2.ptr, nb, ctypes.byref(item), bk.stream) == 0
+            assert item.kind == kind, (kernel, item.kind)
+            assert bk.lib.step_wgrad_reduce_group(ctypes.byref(item), 1, bk.stream) == 0
+            err = np.abs(dw2.get() - ref).max() / np.abs(ref).max()
+            assert err < 2e-5, (kernel, err)
+            assert guard_intact(ws2, nb), kernel
+    finally:
+        _capi.set_option(bk.lib, "wgrad16_lds", 1)
+
+    # the stem: shapes of case_stem_wgrad / case_stem_wgrad16
+    Cout = 40
+    for (N, T, H, W), dt, w16 in (((1, 6, 21, 70), F32, False), ((2, 6, 22, 72), BF16, True)):
+        x = rs.randn(N, T, 3, H, W).astype(np.float32)
+        To, Ho, Wo = (T - 2) // 2 + 1, (H - 2) // 2 + 1, (W - 2) // 2 + 1
+        gy = rs.randn(N, Cout, To, Ho, Wo).astype(np.float32)
+        gdt = dt if w16 else F32
+        w = torch.zeros(Cout, 3, 7, 7, 7, requires_grad=True, dtype=torch.float64)
+        y = F.conv3d(F.pad(torch.from_numpy(quantize(x, dt)).permute(0, 2, 1, 3, 4).double(), (2, 3, 2, 3, 2, 3)), w, stride=2)
+        y.backward(torch.from_numpy(quantize(gy, gdt)).double())
+        ref = w.grad.numpy()
+        xd, gd = bk.dev(encode(x, dt)), bk.dev(encode(np.ascontiguousarray(cl(gy)), gdt))
+        dw = bk.dev(np.full((Cout, 3, 7, 7, 7), -3.0, np.float32))
+        if w16:
+            nb = bk.lib.step_stem_wgrad16_workspace_bytes(dt, N, T, H, W, Cout)
+            ws = guarded(nb)
+            assert bk.lib.step_stem_wgrad16(dt, xd.ptr, N, T, H, W, gd.ptr, Cout, dw.ptr, 0, ws.ptr, nb, bk.stream) == 0
+        else:
+            nb = bk.lib.step_stem_wgrad_workspace_bytes(N, T, H, W, Cout)
+            ws = guarded(nb)
+            assert bk.lib.step_stem_wgrad_ws(dt, xd.ptr, N, T, H, W, gd.ptr, Cout, dw.ptr, 0, ws.ptr, nb, bk.stream) == 0
+        err = np.abs(dw.get() - ref).max() / np.abs(ref).max()
+        assert err < 2e-5, (dt, err)
+        assert guard_intact(ws, nb), dt
+
+
 def case_stem_pool_fused(bk, golden):
     """step_stem_pool_forward (the stem with maxPool3d_2a taken on its tiles, models/i3dpt.py:186-196) is BIT-IDENTICAL to step_stem_forward
     followed by step_maxpool3d_tf (1,3,3) / (1,2,2): maps of several tiles in both directions with partial last tiles (seams completed by
